@@ -20,9 +20,11 @@ Workloads (--workload):
                     launches the ranks and carries the 128-byte communicator id) -- strong scaling.
 
 The timed region holds exactly K steps between barrier + torch.cuda.synchronize(); rank 0 prints
-ONE JSON line.  `roofline` prices the render kernel against HBM (9 algorithmic bytes per ray; the
-kernel is fp64-VALU/latency bound, so the fraction is tiny by construction -- DESIGN.md) and
-`cpu_baseline` times the CPU oracle (oracle/, test infrastructure) on the host cores.
+ONE JSON line (`ms_per_step` = wall time of the timed region / K).  `roofline` prices the render kernel
+against HBM (9 algorithmic bytes per ray; the kernel is fp64-VALU/latency bound, so the fraction is tiny by
+construction -- DESIGN.md) and `cpu_baseline` times the CPU oracle (oracle/, test infrastructure) on the host cores.
+--dump-outputs DIR writes the last timed step's maps and frame stats to DIR/<name>.npy (dump_outputs); the inputs
+are fixed, so two builds of the project can be compared output for output.
 """
 from __future__ import annotations
 
@@ -126,6 +128,36 @@ def idle_team_pace(L, _native, scene_id, strat_id, cam14, W, H, iters_map, lip):
             "note": "wall time of one rm_march_rays_team call (copies included) over the frame's own >= 500-iteration pixels / iter_max"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 20   # pixels kept of a frame whose maps exceed the budget
+DUMP_SAMPLE_SEED = 1080
+
+
+def dump_outputs(out_dir, maps, st):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the depth map (fp32), the iteration
+    and hit maps (as float32, exact) and the frame's RmStats (float64, exact) -- as out_dir/<name>.npy.  A frame whose
+    three maps exceed the budget is written as a fixed sample of its pixels (seeded: the same pixels on every run of the
+    same workload), with pixel_index.npy holding their flat row-major indices.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    depth, iters, hit = maps
+    arrays = {}
+    if 3 * 4 * depth.size > DUMP_BUDGET_BYTES - (64 << 10):          # three float32 maps + room for the stats
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(depth.size, size=DUMP_SAMPLE_PIXELS, replace=False))
+        depth, iters, hit = (m.reshape(-1)[idx] for m in (depth, iters, hit))
+        arrays["pixel_index"] = idx.astype(np.float64)
+    arrays["depth"] = depth.astype(np.float32)
+    arrays["iters"] = iters.astype(np.float32)
+    arrays["hit"] = hit.astype(np.float32)
+    arrays["stats"] = np.array([st.total_rays, st.hit_count, st.sum_iters, st.iter_max, st.iter_min, st.sum_evals],
+                               dtype=np.float64)    # RmStats order (include/rm_hip.h), iter_hist apart
+    arrays["iter_hist"] = np.array(st.iter_hist[:], dtype=np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -138,7 +170,12 @@ def main():
     ap.add_argument("--grid-waves", type=int, default=0)
     ap.add_argument("--temporal-grid-waves", type=int, default=0,
                     help="persistent wavefronts for the temporal_order figure (0 = library default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (depth, iters, hit maps and the frame stats) to DIR/<name>.npy "
+                         "(bench_outputs/ is ignored by git)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -233,6 +270,12 @@ def main():
 
     st = _native.RmStats()
     _native.check(L.rm_read_stats(ctypes.c_void_p(d_stats.data_ptr()), sptr, ctypes.byref(st)))
+    # the last timed step's results, before anything below renders into the same buffers: the gathered frame when the
+    # ranks exchange their shards, else this rank's maps
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        maps = full if full is not None else (d_depth, d_iters, d_hit)
+        dumped = dump_outputs(args.dump_outputs, [m.cpu().numpy() for m in maps], st)
 
     # Secondary figure (never `value`): the same frames scheduled longest-tile-first from the per-tile
     # cost the previous frame left behind (tile_order_mode 1) on a smaller persistent grid.  Every ray
@@ -427,6 +470,8 @@ def main():
             line["throughput_8k"] = tp8k
         if batched is not None:
             line["batched_frames"] = batched
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if not args.no_cpu_baseline:
             try:
                 # rank 0 only, every N; with N > 1 a shorter sample (the other ranks wait at the end of the run)

@@ -85,6 +85,23 @@ def golden_frames(tag):
     return _cache[tag]
 
 
+_gpu_count = None
+
+
+def gpu_count() -> int:
+    """GPUs PyTorch sees, asked in a child process.  Asking here would initialise PyTorch's own HIP runtime (its wheel
+    bundles one) in the test process beside the copy librm_hip.so is bound to, and whichever of the two initialises
+    second finds no device: every later rm_init would fail with RM_E_NO_DEVICE."""
+    global _gpu_count
+    if _gpu_count is None:
+        import subprocess
+        cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [
+            "-c", "import torch; print(torch.cuda.device_count())"]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=120, check=True)
+        _gpu_count = int(out.stdout.split()[-1])
+    return _gpu_count
+
+
 @pytest.fixture(scope="session")
 def hip():
     """The ctypes binding, initialised on cuda:0 -- fails (does not skip) without the HIP library."""

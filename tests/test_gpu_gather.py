@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+from conftest import gpu_count
 from raymarch_algo_compare_amd import registry, sharding
 from raymarch_algo_compare_amd.camera import Camera
 
@@ -108,8 +109,7 @@ def test_gather_entry_points_on_a_communicator_of_one(hip):
 def test_two_rank_gather_over_rccl():
     """Two processes, one GPU each (torch.distributed.run only launches and carries the communicator id): band-cyclic
     and contiguous plans.  Skipped on a one-GPU box -- the multi-GPU leg has not run on hardware in this round."""
-    import torch
-    if torch.cuda.device_count() < 2:
+    if gpu_count() < 2:
         pytest.skip("needs two GPUs (the test box has one)")
     import socket
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
