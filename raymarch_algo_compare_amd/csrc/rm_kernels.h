@@ -38,6 +38,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "rm_camera.h"
 #include "rm_scenes.h"
@@ -905,20 +906,61 @@ struct TeamXch {
     double v[2][2 * kTeam][64];
 };
 
-// One trip for a team; `turn` counts the team's trips (buffer parity).  Wave-uniform call.
-template <class Scene>
-__device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, int part, int lane, TeamXch& x, int& turn)
+// One trip for a team; `turn` counts the team's trips (buffer parity).  Wave-uniform call.  The part is an int, or a
+// std::integral_constant<int, P> in a per-part trip loop (team_trips).
+template <class Scene, class PartT>
+__device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, PartT part, int lane, TeamXch& x, int& turn)
 {
     double o0 = 0.0, o1 = 0.0;
-    if (go) Scene::trip_part(ev, part, o0, o1);
+    if constexpr (std::is_same<PartT, int>::value) {
+        if (go) Scene::trip_part(ev, part, o0, o1);
+    } else {
+        if (go) Scene::template trip_part<PartT::value>(ev, o0, o1);
+    }
     double (*buf)[64] = x.v[turn & 1];
     ++turn;
-    buf[2 * part][lane] = o0;
-    buf[2 * part + 1][lane] = o1;
+    buf[2 * (int)part][lane] = o0;
+    buf[2 * (int)part + 1][lane] = o1;
     __syncthreads();
     bool done = true;
     if (go) done = Scene::trip_join(ev, buf[0][lane], buf[1][lane], buf[2][lane], buf[3][lane], buf[4][lane], buf[5][lane]);
     return done;
+}
+
+// Scene::kPartLoops: the team runs one trip loop per part (team_trips).  Set by the Mandelbulb, whose parts are long
+// chains of their own; the one-trip unions keep the single loop with the part chosen inside the trip (measured: per-part
+// loops made Sphere Cloud and Bumpy Sphere 4-6 % slower).
+template <class Scene, class = void>
+struct ScenePartLoops : std::false_type {};
+template <class Scene>
+struct ScenePartLoops<Scene, decltype((void)Scene::kPartLoops)> : std::integral_constant<bool, Scene::kPartLoops> {};
+
+// The trips of one evaluation of every live ray (ready: the lane's value is ready).  `trip(part, go)` is team_trip or
+// team_trip_lds (rm_pipeline.h) bound to the team's exchange and barrier.  With per-part loops the part is dispatched
+// once, outside the trip loop, on a wave-uniform scalar: each wave's loop holds only its own part's chain, with no
+// branch on the part per trip.
+template <int P, class Trip>
+__device__ __forceinline__ void team_trips_part(bool& ready, const Trip& trip)
+{
+    while (__any(!ready)) {
+        const bool fin = trip(std::integral_constant<int, P>(), !ready);
+        if (!ready) ready = fin;
+    }
+}
+template <class Scene, class Trip>
+__device__ __forceinline__ void team_trips(int part, bool& ready, const Trip& trip)
+{
+    if constexpr (ScenePartLoops<Scene>::value) {
+        part = __builtin_amdgcn_readfirstlane(part);
+        if (part == 0) team_trips_part<0>(ready, trip);
+        else if (part == 1) team_trips_part<1>(ready, trip);
+        else team_trips_part<2>(ready, trip);
+    } else {
+        while (__any(!ready)) {
+            const bool fin = trip(part, !ready);
+            if (!ready) ready = fin;
+        }
+    }
 }
 
 // rm_march_rays for a team: 64 rays per workgroup of kTeam waves (no lane refill)
@@ -953,10 +995,7 @@ __global__ __launch_bounds__(64 * kTeam) void march_rays_team_kernel(MarchCfg cf
     while (__any(!done)) {
         bool ready = true;
         if (!done) ready = Scene::begin(ev, o + d * s.te);
-        while (__any(!ready)) {
-            const bool fin = team_trip<Scene>(ev, !ready, part, lane, xch, turn);
-            if (!ready) ready = fin;
-        }
+        team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
         if (!done) done = s.step(Scene::value(ev), cfg);
     }
     if (have && part == 0) {
@@ -1057,10 +1096,7 @@ __global__ __launch_bounds__(64 * kTeam) void resume_team_kernel(const KernelArg
         // ---- one whole SDF evaluation for every live ray, trips shared by the team -------------------
         bool ready = true;
         if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-        while (__any(!ready)) {
-            const bool fin = team_trip<Scene>(ev, !ready, part, lane, xch, turn);
-            if (!ready) ready = fin;
-        }
+        team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
         bool park = false;
         if (active) {
             ++nev;

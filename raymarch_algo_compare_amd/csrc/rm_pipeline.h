@@ -296,16 +296,20 @@ __device__ __forceinline__ void team_barrier(PipeTeamLds& L, unsigned int& epoch
 }
 
 // team_trip (rm_kernels.h) with the team's own barrier
-template <class Scene>
-__device__ __forceinline__ bool team_trip_lds(typename Scene::Eval& ev, bool go, int part, int lane, PipeTeamLds& L, int& turn,
+template <class Scene, class PartT>
+__device__ __forceinline__ bool team_trip_lds(typename Scene::Eval& ev, bool go, PartT part, int lane, PipeTeamLds& L, int& turn,
                                               unsigned int& epoch)
 {
     double o0 = 0.0, o1 = 0.0;
-    if (go) Scene::trip_part(ev, part, o0, o1);
+    if constexpr (std::is_same<PartT, int>::value) {
+        if (go) Scene::trip_part(ev, part, o0, o1);
+    } else {
+        if (go) Scene::template trip_part<PartT::value>(ev, o0, o1);
+    }
     double (*buf)[64] = L.xch.v[turn & 1];
     ++turn;
-    buf[2 * part][lane] = o0;
-    buf[2 * part + 1][lane] = o1;
+    buf[2 * (int)part][lane] = o0;
+    buf[2 * (int)part + 1][lane] = o1;
     team_barrier(L, epoch);
     bool done = true;
     if (go) done = Scene::trip_join(ev, buf[0][lane], buf[1][lane], buf[2][lane], buf[3][lane], buf[4][lane], buf[5][lane]);
@@ -509,10 +513,7 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
             ++since_try;
             bool ready = true;
             if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-            while (__any(!ready)) {
-                const bool fin = team_trip_lds<Scene>(ev, !ready, part, lane, L, turn, epoch);
-                if (!ready) ready = fin;
-            }
+            team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip_lds<Scene>(ev, go, P, lane, L, turn, epoch); });
             const int live = a.trace ? __popcll(__ballot(active)) : 0;
             if (active) {
                 ++nev;

@@ -195,20 +195,30 @@ struct SceneMandelbulb {                                                        
     // trip(e) == trip_join(e, parts 0..2): same expressions, same order, same bits.
     // (wave-uniform band skipping inside acos / atan2 / sincos: a team wave is alone on its SIMD with few live
     // lanes, every instruction it does not issue shortens the frame's critical chain -- rm_math_trig.h)
-    static RM_HD void trip_part(const Eval& e, int part, double& o0, double& o1)
+    // trip_part<P>: the part as a template argument -- a team wave runs its trip loop for one part only (kPartLoops,
+    // rm_kernels.h team_trips), so the loop body holds that part's chain and no per-trip branch on the part
+    static constexpr bool kPartLoops = true;
+    template <int P>
+    static RM_HD void trip_part(const Eval& e, double& o0, double& o1)
     {
         const double power = 8.0;
-        if (part == 0) {
+        if constexpr (P == 0) {
             double theta = rm_acos<true>(py_max(-1.0, py_min(1.0, e.z.z / py_max(e.r, 1e-12))));
             theta *= power;
             rm_sincos<true>(theta, &o0, &o1);
-        } else if (part == 1) {
+        } else if constexpr (P == 1) {
             double phi = rm_atan2<true>(e.z.y, e.z.x);
             phi *= power;
             rm_sincos<true>(phi, &o0, &o1);
         } else {
             rm_pow2(e.r, power - 1.0, power, &o0, &o1);
         }
+    }
+    static RM_HD void trip_part(const Eval& e, int part, double& o0, double& o1)
+    {
+        if (part == 0) trip_part<0>(e, o0, o1);
+        else if (part == 1) trip_part<1>(e, o0, o1);
+        else trip_part<2>(e, o0, o1);
     }
     static RM_HD bool trip_join(Eval& e, double st, double ct, double sp, double cp, double r7, double zr)
     {
@@ -294,14 +304,21 @@ struct SceneSphereCloud {                                                       
     static RM_HD bool begin(Eval& e, vec3 p) { e.p = p; return false; }
     static RM_HD bool trip(Eval& e) { e.d = sdf(e.p); return true; }
     static RM_HD double value(const Eval& e) { return e.d; }
-    static RM_HD void trip_part(const Eval& e, int part, double& o0, double& o1)
+    template <int P>
+    static RM_HD void trip_part(const Eval& e, double& o0, double& o1)
     {
         const vec3 p = e.p;
         double d = 1e10;
 #define RM_X(cx, cy, cz, r) d = py_min(d, sd_sphere(p - v3(cx, cy, cz), r));
-        if (part == 0) { RM_CLOUD_LIST_A(RM_X) } else if (part == 1) { RM_CLOUD_LIST_B(RM_X) } else { RM_CLOUD_LIST_C(RM_X) }
+        if constexpr (P == 0) { RM_CLOUD_LIST_A(RM_X) } else if constexpr (P == 1) { RM_CLOUD_LIST_B(RM_X) } else { RM_CLOUD_LIST_C(RM_X) }
 #undef RM_X
         o0 = d; o1 = 0.0;
+    }
+    static RM_HD void trip_part(const Eval& e, int part, double& o0, double& o1)
+    {
+        if (part == 0) trip_part<0>(e, o0, o1);
+        else if (part == 1) trip_part<1>(e, o0, o1);
+        else trip_part<2>(e, o0, o1);
     }
     static RM_HD bool trip_join(Eval& e, double a, double, double b, double, double c, double)
     {
@@ -340,14 +357,21 @@ struct SceneBumpySphere {                                                       
     static RM_HD bool begin(Eval& e, vec3 p) { e.p = p; return false; }
     static RM_HD bool trip(Eval& e) { e.d = sdf(e.p); return true; }
     static RM_HD double value(const Eval& e) { return e.d; }
-    static RM_HD void trip_part(const Eval& e, int part, double& o0, double& o1)
+    template <int P>
+    static RM_HD void trip_part(const Eval& e, double& o0, double& o1)
     {
         const vec3 p = e.p;
         double d = 1e10;
 #define RM_X(cx, cy, cz) d = py_min(d, sd_sphere(p - v3(cx, cy, cz), 0.18));
-        if (part == 0) { d = sd_sphere(p, 1.4); RM_BUMP_LIST_A(RM_X) } else if (part == 1) { RM_BUMP_LIST_B(RM_X) } else { RM_BUMP_LIST_C(RM_X) }
+        if constexpr (P == 0) { d = sd_sphere(p, 1.4); RM_BUMP_LIST_A(RM_X) } else if constexpr (P == 1) { RM_BUMP_LIST_B(RM_X) } else { RM_BUMP_LIST_C(RM_X) }
 #undef RM_X
         o0 = d; o1 = 0.0;
+    }
+    static RM_HD void trip_part(const Eval& e, int part, double& o0, double& o1)
+    {
+        if (part == 0) trip_part<0>(e, o0, o1);
+        else if (part == 1) trip_part<1>(e, o0, o1);
+        else trip_part<2>(e, o0, o1);
     }
     static RM_HD bool trip_join(Eval& e, double a, double, double b, double, double c, double)
     {

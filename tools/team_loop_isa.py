@@ -1,0 +1,195 @@
+#!/usr/bin/env python3
+"""team_loop_isa.py -- static instruction mix of the wavefront-team trip loops of a kernel.
+
+A team wave's trip loop (rm_kernels.h team_trips, rm_pipeline.h team role) is the innermost loop that holds the
+team's exchange barrier (s_barrier).  For every such loop of the named kernels this prints the instruction counts of
+one pass: vector (of them fp64 and v_cndmask), LDS, scalar, literal s_mov (64-bit fp constants rebuilt in SGPRs),
+branches, s_nop, scratch accesses and SGPR spill lane moves (v_writelane / v_readlane).  The part column is read from
+the loop's exchange write; it is meaningful only for per-part loops (Scene::kPartLoops), not for a single loop whose part
+is a runtime value.
+
+Input: the assembly the build keeps next to each object with KEEP_ASM=1 (after the rm_peephole.py pass), e.g.
+
+  make -C raymarch_algo_compare_amd/csrc DEV=1 DEVSCENES=10 KEEP_ASM=1
+  python tools/team_loop_isa.py raymarch_algo_compare_amd/_build_dev/scene_10.s            # the bench kernel
+  python tools/team_loop_isa.py scene_10.s --kernel march_rays_team_kernel --kernel resume_team_kernel
+  python tools/team_loop_isa.py scene_10.s --json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import re
+import sys
+
+BENCH_KERNEL = "_ZN2rm15pipeline_kernelINS_15SceneMandelbulbENS_13StratStandardELi4ELb1ELb0EEEvNS_10KernelArgsE"
+XCH_WRITE = re.compile(r"^\s*ds_write2st64_b64\b.*?(?:offset0:(\d+))?\s+offset1:(\d+)")
+LITERAL = re.compile(r"^\s*s_mov_b32\s+s\d+,\s*(0x[0-9a-fA-F]+|-?\d+)\s*$")
+
+
+def functions(lines):
+    """name -> (first line, last line) of every function body in the file"""
+    out, name, start = {}, None, 0
+    for i, ln in enumerate(lines):
+        m = re.match(r"^(_Z\w+):", ln)
+        if m:
+            name, start = m.group(1), i
+        elif name and re.match(r"^\s*\.Lfunc_end\d+:", ln):
+            out[name] = (start, i)
+            name = None
+    return out
+
+
+def instructions(lines, a, b):
+    for ln in lines[a:b + 1]:
+        s = ln.split(";", 1)[0].strip()
+        if not s or s.endswith(":") or s.startswith("."):
+            continue
+        yield s
+
+
+def is_literal_mov(ins):
+    m = LITERAL.match(ins)
+    if not m:
+        return False
+    v = int(m.group(1), 0)
+    return not (-16 <= v <= 64)         # inline constants need no literal
+
+
+def loop_mix(lines, ranges):
+    c = dict(static=0, vector=0, fp64=0, cndmask=0, lds=0, scalar=0, literal_s_mov=0, branches=0, s_nop=0,
+             scratch=0, spill_lane_moves=0)
+    for ins in (x for a, b in ranges for x in instructions(lines, a, b)):
+        op = ins.split()[0]
+        c["static"] += 1
+        if op.startswith("v_"):
+            c["vector"] += 1
+            if "_f64" in op:
+                c["fp64"] += 1
+            if op.startswith("v_cndmask"):
+                c["cndmask"] += 1
+            if op in ("v_writelane_b32", "v_readlane_b32"):
+                c["spill_lane_moves"] += 1
+        elif op.startswith("ds_"):
+            c["lds"] += 1
+        elif op.startswith("scratch_") or (op.startswith("buffer_") and "off" in ins and "s[0:3]" in ins):
+            c["scratch"] += 1
+        elif op.startswith("s_"):
+            c["scalar"] += 1
+            if op.startswith("s_branch") or op.startswith("s_cbranch"):
+                c["branches"] += 1
+            if op == "s_nop":
+                c["s_nop"] += 1
+            if is_literal_mov(ins):
+                c["literal_s_mov"] += 1
+    return c
+
+
+BLOCK = re.compile(r"^(?:\.LBB(\d+_\d+):|; %bb\.(\d+):)(.*)$")
+IN_LOOP = re.compile(r"in Loop: Header=BB(\d+_\d+) Depth=(\d+)")
+HEADER = re.compile(r"=>\s*This (Inner )?Loop Header: Depth=(\d+)")
+
+
+def team_loops(lines, a, b):
+    """Innermost loops (the compiler's own loop annotations of the blocks) that hold an s_barrier: the line ranges
+    of their blocks, in layout order"""
+    blocks = []                 # (first line, last line, innermost loop header or None, is inner header)
+    cur = None
+    for i in range(a, b + 1):
+        m = BLOCK.match(lines[i])
+        if not m:
+            continue
+        if cur:
+            blocks.append((cur[0], i - 1, cur[1], cur[2]))
+        name = m.group(1) or None
+        loop, inner = None, False
+        lm = IN_LOOP.search(m.group(3))
+        if lm:
+            loop = lm.group(1)
+        nxt = lines[i + 1] if i + 1 <= b else ""
+        hm = HEADER.search(nxt)
+        if hm and name:
+            loop, inner = name, bool(hm.group(1))
+        cur = (i, loop, inner)
+    if cur:
+        blocks.append((cur[0], b, cur[1], cur[2]))
+    inner_headers = {blk[2] for blk in blocks if blk[3]}
+    loops = {}
+    for lo, hi, loop, _ in blocks:
+        if loop in inner_headers:
+            loops.setdefault(loop, []).append((lo, hi))
+    out = []
+    for h, ranges in loops.items():
+        if any(re.match(r"^\s*s_barrier\b", lines[k]) for lo, hi in ranges for k in range(lo, hi + 1)):
+            out.append((h, ranges))
+    return sorted(out, key=lambda t: t[1][0][0])
+
+
+def resources(lines, name):
+    """registers, spills and private segment of the kernel (its .amdhsa_kernel block and code object metadata)"""
+    out = {}
+    text = "\n".join(lines)
+    m = re.search(rf"^\s*\.amdhsa_kernel {re.escape(name)}\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M)
+    if m:
+        for key in ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size"):
+            k = re.search(rf"\.amdhsa_{key}\s+(\d+)", m.group(1))
+            if k:
+                out[key] = int(k.group(1))
+    m = re.search(rf"\.name:\s+{re.escape(name)}\n", text)
+    if m:
+        after = text[m.end():m.end() + 1000]          # the metadata map's keys after .name (alphabetical order)
+        for key in ("sgpr_spill_count", "vgpr_spill_count"):
+            k = re.search(rf"\.{key}:\s+(\d+)", after)
+            if k:
+                out[key] = int(k.group(1))
+    return out
+
+
+def exchange_part(lines, ranges):
+    """the team part a loop belongs to, from its exchange write: TeamXch.v[parity][2 * part][lane] and [2 * part + 1],
+    one ds_write2st64_b64 whose offsets (units of 64 doubles) are 2 * part and 2 * part + 1"""
+    for a, b in ranges:
+        for k in range(a, b + 1):
+            m = XCH_WRITE.match(lines[k])
+            if m:
+                o0 = int(m.group(1) or 0)
+                if int(m.group(2)) == o0 + 1 and o0 % 2 == 0:
+                    return o0 // 2
+    return None
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("asm", help="assembly of a scene object (KEEP_ASM=1 build)")
+    ap.add_argument("--kernel", action="append", default=None,
+                    help="mangled name or a substring of it (repeatable); default: the bench kernel")
+    ap.add_argument("--json", action="store_true", help="one JSON object instead of the table")
+    args = ap.parse_args(argv)
+    lines = open(args.asm).read().splitlines()
+    funcs = functions(lines)
+    wanted = args.kernel or [BENCH_KERNEL]
+    report = {}
+    for w in wanted:
+        for name, (a, b) in funcs.items():
+            if w == name or w in name:
+                loops = team_loops(lines, a, b)
+                report[name] = dict(resources=resources(lines, name),
+                                    loops=[dict(header="BB" + h, part=exchange_part(lines, r), **loop_mix(lines, r))
+                                           for h, r in loops])
+    if not report:
+        sys.exit(f"no kernel matches {wanted}")
+    if args.json:
+        print(json.dumps(report, indent=1))
+        return
+    cols = ["static", "vector", "fp64", "cndmask", "lds", "scalar", "literal_s_mov", "branches", "s_nop", "scratch",
+            "spill_lane_moves"]
+    for name, r in report.items():
+        print(f"{name}  {r['resources']}")
+        print("  loop header    part " + " ".join(f"{c[:8]:>8}" for c in cols))
+        for L in r["loops"]:
+            part = "?" if L["part"] is None else L["part"]
+            print(f"  {L['header']:<13} {part:>4} " + " ".join(f"{L[c]:>8}" for c in cols))
+
+
+if __name__ == "__main__":
+    main()
