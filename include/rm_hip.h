@@ -8,7 +8,8 @@
  * here falls back to a CPU implementation: every call fails with RM_E_NO_DEVICE /
  * RM_E_HIP when no gfx950 device is usable.
  *
- * Ids: scene_id = index in get_all_scenes() (scenes/catalog.py:640-663), 0..19;
+ * Ids: scene_id = index in get_all_scenes() (scenes/catalog.py:640-663), 0..19, or the id of a scene program
+ *      (rm_scene_program_create: RM_SCENE_PROGRAM_BASE and up);
  *      strategy_id = index in the STRATEGIES dict (strategies/__init__.py:16-28), 0..10.
  * Threading: every entry point may be called from any host thread; calls are serialised by one lock inside the
  * library (one in-flight CALL per device), calls are synchronous unless stated, and frames enqueued on different streams
@@ -19,6 +20,9 @@
  * rm_stream_create are accepted (anything else: RM_E_BAD_ARG, the handle is not touched); with one copy mapped every
  * hipStream_t of the process is that runtime's and is accepted (e.g. a torch stream when torch was imported first).
  * Hosts without a HIP binding of their own take streams from rm_stream_create.
+ * Scene programs: the registry of programs has a lock of its own; create / destroy may be called from any thread.
+ * Destroying a program while a frame that renders it is still in flight on a stream is the caller's error (the
+ * frame reads the program's device copy until it ends): synchronise the stream first.
  */
 #ifndef RM_HIP_H
 #define RM_HIP_H
@@ -254,6 +258,61 @@ int rm_sdf_eval(int scene_id, const double* xyz, size_t n, double* out);
  * Directions are normalised as Ray.__init__ does (core/ray.py:11-13). */
 int rm_march_rays(int scene_id, int strategy_id, const RmMarchConfig* cfg, const double* origins,
                   const double* dirs, size_t n, uint8_t* hit, double* t, int32_t* iters, double* final_sdf);
+
+/* ---- Scene programs: user-defined CSG scenes, evaluated by an interpreter on the device ---------------------------
+ * A program is a postfix list of the reference's scenes/primitives.py functions.  Primitives push a distance computed at
+ * the current point; combinators pop two distances (d1 pushed first, d2 second) and push one; distance modifiers replace
+ * the top distance; point transforms save the current point and replace it by the transformed point, which the ops up to
+ * the matching RM_SOP_POP_POINT read; RM_SOP_POP_POINT restores the saved point.  Evaluation starts at the query point;
+ * exactly one distance must be left at the end, and every transform must be matched.  Constants go in f[], in the
+ * order of the reference's arguments; a constant the reference computes with a transcendental function is passed
+ * already computed (the device never evaluates trigonometry).  `arg` is reserved (0), unused f[] entries too.
+ *   op                          f[]                                              primitives.py
+ *   RM_SOP_SPHERE               radius                                           :11-12
+ *   RM_SOP_BOX                  half_extents x, y, z                             :14-18
+ *   RM_SOP_PLANE                normal x, y, z, offset                           :20-21
+ *   RM_SOP_CYLINDER             radius, half_height                              :23-28
+ *   RM_SOP_TORUS                major_radius, minor_radius                       :30-32
+ *   RM_SOP_CAPSULE              a x, y, z, b x, y, z, radius                     :34-39
+ *   RM_SOP_CAPPED_TORUS         sc[0] = sin(half angle), sc[1] = cos(half angle), ra, rb     :41-50
+ *   RM_SOP_CONE                 cos(angle_rad), sin(angle_rad), height           :53-65
+ *   RM_SOP_UNION / SUBTRACT / INTERSECT                 (none)                   :70-77
+ *   RM_SOP_SMOOTH_UNION / SMOOTH_SUBTRACT / SMOOTH_INTERSECT   k (non-zero)      :80-92
+ *   RM_SOP_TRANSLATE            offset x, y, z                                   :99-100
+ *   RM_SOP_REPEAT               spacing x, y, z (an axis with spacing <= 0 is untouched)       :102-108
+ *   RM_SOP_POP_POINT            (none)
+ *   RM_SOP_ROUND                radius                                           :110-111
+ *   RM_SOP_ONION                thickness                                        :113-114
+ * Every result is bit-identical to the reference's functions (binary64, its evaluation order).
+ * Ids of programs start at RM_SCENE_PROGRAM_BASE, increase monotonically and are never reused within a process.  A
+ * program id is accepted by every frame entry point (rm_render*, rm_render_device, rm_bench_device, rm_render_batch*,
+ * rm_march_rays, rm_sdf_eval, rm_gather_frame*) until it is destroyed; afterwards they return RM_E_BAD_SCENE.  A program
+ * scene has no wavefront-team form (rm_march_rays_team: RM_E_BAD_SCENE) and never runs the single-launch pipeline
+ * (RmFrameDesc.pipeline is ignored); it takes the library's defaults of a cheap scene.  rm_num_scenes() stays 20. */
+#define RM_SCENE_PROGRAM_BASE 1024
+#define RM_SCENE_PROGRAM_MAX_OPS 256
+#define RM_SCENE_PROGRAM_MAX_VALUES 8   /* value stack depth */
+#define RM_SCENE_PROGRAM_MAX_POINTS 4   /* saved points (nested transforms) */
+enum {
+    RM_SOP_SPHERE = 0, RM_SOP_BOX = 1, RM_SOP_PLANE = 2, RM_SOP_CYLINDER = 3, RM_SOP_TORUS = 4, RM_SOP_CAPSULE = 5,
+    RM_SOP_CAPPED_TORUS = 6, RM_SOP_CONE = 7,
+    RM_SOP_UNION = 8, RM_SOP_SUBTRACT = 9, RM_SOP_INTERSECT = 10,
+    RM_SOP_SMOOTH_UNION = 11, RM_SOP_SMOOTH_SUBTRACT = 12, RM_SOP_SMOOTH_INTERSECT = 13,
+    RM_SOP_TRANSLATE = 14, RM_SOP_REPEAT = 15, RM_SOP_POP_POINT = 16,
+    RM_SOP_ROUND = 17, RM_SOP_ONION = 18,
+    RM_SOP_COUNT = 19
+};
+typedef struct RmSceneOp {
+    int32_t op;       /* RM_SOP_* */
+    int32_t arg;      /* reserved: 0 */
+    double f[8];      /* constants (table above) */
+} RmSceneOp;
+/* Validates the program on the host (opcodes, stack depths, length, finite constants; RM_E_BAD_ARG with the reason in
+ * rm_last_error) and registers it; needs no device (the device copy is made by the first frame that uses it).
+ * `lipschitz` (> 0) is kept with the program for the host's bookkeeping; a frame reads RmMarchConfig.lipschitz. */
+int rm_scene_program_create(const RmSceneOp* ops, int32_t nops, double lipschitz, int32_t* scene_id);
+/* Frees the program and its device copy; its id is never handed out again.  RM_E_BAD_SCENE for an unknown id. */
+int rm_scene_program_destroy(int32_t scene_id);
 
 /* Same contract, evaluated by wavefront TEAMS (scenes whose SDF is a loop of independent
  * transcendental chains -- Mandelbulb: three waves carry the same 64 rays and each evaluates one

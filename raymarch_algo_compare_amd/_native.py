@@ -32,8 +32,9 @@ EXPORTS = [
     "rm_bench_store_path", "rm_render_batch", "rm_render_batch_outputs", "rm_set_pass_timing", "rm_get_pass_ms", "rm_last_queue_marks", "rm_long_ray_marks", "rm_set_queue_capacity",
     "rm_comm_unique_id", "rm_comm_init", "rm_comm_destroy", "rm_shard_rows", "rm_gather_frame", "rm_assemble_frame", "rm_gather_frame_root",
     "rm_runtime_info", "rm_stream_create", "rm_stream_synchronize", "rm_stream_destroy", "rm_debug_poison_queues",
-    "rm_debug_set_trace", "rm_debug_get_trace",
+    "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy",
 ]
+RM_SCENE_PROGRAM_BASE = 1024
 
 
 class RmError(RuntimeError):
@@ -133,6 +134,11 @@ class RmTiming(ctypes.Structure):
                 ("ms_each", ctypes.c_float * RM_MAX_TIMED)]
 
 
+class RmSceneOp(ctypes.Structure):
+    """One instruction of a scene program (include/rm_hip.h; built by scene_program.py)."""
+    _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("f", ctypes.c_double * 8)]
+
+
 class RmDeviceInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 128), ("arch", ctypes.c_char * 64),
                 ("device_id", ctypes.c_int32), ("compute_units", ctypes.c_int32),
@@ -169,6 +175,9 @@ def load() -> ctypes.CDLL:
         L.rm_default_strategy_params.argtypes = [ctypes.POINTER(RmStrategyParams)]
         L.rm_default_strategy_params.restype = None
         L.rm_sdf_eval.argtypes = [ctypes.c_int, dp, ctypes.c_size_t, dp]
+        L.rm_scene_program_create.argtypes = [ctypes.POINTER(RmSceneOp), ctypes.c_int32, ctypes.c_double,
+                                              ctypes.POINTER(ctypes.c_int32)]
+        L.rm_scene_program_destroy.argtypes = [ctypes.c_int32]
         L.rm_march_rays.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(RmMarchConfig), dp, dp,
                                     ctypes.c_size_t, vp, dp, vp, dp]
         L.rm_march_rays_team.argtypes = L.rm_march_rays.argtypes
@@ -373,6 +382,18 @@ def render_batch(shape: RmFrameDesc, cams, configs=None, want_evals=False) -> di
     out["stats"] = [stats_dict(st[i]) for i in range(n)]
     out["ms_total"] = float(ms.value)
     return out
+
+
+def scene_program_create(ops, nops: int, lipschitz: float = 1.0) -> int:
+    """rm_scene_program_create: validate and register a program (RmSceneOp array); its scene id.  Needs no GPU."""
+    L = load()
+    sid = ctypes.c_int32(-1)
+    check(L.rm_scene_program_create(ops, int(nops), float(lipschitz), ctypes.byref(sid)))
+    return int(sid.value)
+
+
+def scene_program_destroy(scene_id: int) -> None:
+    check(load().rm_scene_program_destroy(int(scene_id)))
 
 
 def sdf_eval(scene_id: int, pts) -> np.ndarray:

@@ -12,12 +12,15 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #include "../../include/rm_hip.h"
 #include "rm_kernels.h"
 #include "rm_pipeline.h"
+#include "rm_scene_program.h"
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
 static_assert(RM_NUM_SCENES == 20 && RM_NUM_STRATEGIES == 11 && RM_NUM_STRATEGY_KERNELS == 13, "registry size");
@@ -31,6 +34,11 @@ namespace rm {
 #endif
 RM_SCENE_LIST(RM_X)
 #undef RM_X
+#if defined(RM_DEV_STRATEGIES)
+const SceneLaunchers* scene_launchers_program() __attribute__((weak));
+#else
+const SceneLaunchers* scene_launchers_program();
+#endif
 static const SceneLaunchers* scene(int id)
 {
     switch (id) {
@@ -131,6 +139,69 @@ struct State {
 
 std::mutex g_mu;
 
+// ---- scene programs (rm_scene_program.h) ----------------------------------------------------------------------------
+// A registered program: its validated device image on the host, and the device copy the first frame that renders it
+// makes (under g_mu; freed by rm_scene_program_destroy and rm_shutdown).
+struct Program {
+    std::unique_ptr<rm::ProgramImage> img;
+    void* dev = nullptr;
+    double lipschitz = 1.0;
+};
+std::mutex g_prog_mu;                          // guards g_programs and g_next_program; taken after g_mu where both are held
+std::map<int32_t, Program> g_programs;
+int32_t g_next_program = RM_SCENE_PROGRAM_BASE;   // ids are never reused: no per-scene cache can outlive its program
+
+bool is_program_id(int id) { return id >= RM_SCENE_PROGRAM_BASE; }
+
+const rm::SceneLaunchers* program_launchers()
+{
+#if defined(RM_DEV_STRATEGIES)
+    return rm::scene_launchers_program ? rm::scene_launchers_program() : nullptr;
+#else
+    return rm::scene_launchers_program();
+#endif
+}
+
+// The kernels of scene `id` (a catalogue scene or a program; check_scene has accepted the id)
+const rm::SceneLaunchers* launchers(int id) { return is_program_id(id) ? program_launchers() : rm::scene(id); }
+
+int check_scene(int id)
+{
+    if (is_program_id(id)) {
+        std::lock_guard<std::mutex> lk(g_prog_mu);
+        if (!g_programs.count(id)) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id);
+        if (!program_launchers()) return fail(RM_E_BAD_SCENE, "the scene-program kernels are not built into this (development) library");
+        return RM_OK;
+    }
+    if (id < 0 || id >= RM_NUM_SCENES) return fail(RM_E_BAD_SCENE, "scene_id %d out of range", id);
+    if (!rm::scene(id)) return fail(RM_E_BAD_SCENE, "scene %d is not built into this (development) library", id);
+    return RM_OK;
+}
+
+// The launch data of scene `id` (KernelArgs.scene_data; under g_mu with the device selected): a program's device image,
+// copied by its first frame; nullptr for a catalogue scene.
+int scene_data(int id, const void** data)
+{
+    *data = nullptr;
+    if (!is_program_id(id)) return RM_OK;
+    std::lock_guard<std::mutex> lk(g_prog_mu);
+    auto it = g_programs.find(id);
+    if (it == g_programs.end()) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id);
+    Program& p = it->second;
+    if (!p.dev) {
+        void* dev = nullptr;
+        HIP_TRY(hipMalloc(&dev, sizeof(rm::ProgramImage)));
+        const hipError_t e = hipMemcpy(dev, p.img.get(), sizeof(rm::ProgramImage), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(RM_E_HIP, "scene program %d: copy to the device failed: %s", id, hipGetErrorString(e));
+        }
+        p.dev = dev;
+    }
+    *data = p.dev;
+    return RM_OK;
+}
+
 constexpr size_t kStatsBlockBytes = sizeof(unsigned long long) * rm::kStatsWords;   // the canonical block (what the host reads)
 constexpr size_t kStatsBytes = kStatsBlockBytes * rm::kStatsBlocks;                 // + the partial blocks (device buffer size)
 
@@ -195,8 +266,7 @@ int check_stream(void* stream)
 int check_desc(const RmFrameDesc* d)
 {
     if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    if (d->scene_id < 0 || d->scene_id >= RM_NUM_SCENES) return fail(RM_E_BAD_SCENE, "scene_id %d out of range", d->scene_id);
-    if (!rm::scene(d->scene_id)) return fail(RM_E_BAD_SCENE, "scene %d is not built into this (development) library", d->scene_id);
+    if (int rc = check_scene(d->scene_id)) return rc;
     if (d->strategy_id < 0 || d->strategy_id >= RM_NUM_STRATEGY_KERNELS)
         return fail(RM_E_BAD_STRATEGY, "strategy_id %d out of range", d->strategy_id);
     if (d->width <= 0 || d->height <= 0 || d->row0 < 0 || d->rows < 0 ||
@@ -252,6 +322,7 @@ int make_args(const RmFrameDesc* d, float* depth, int32_t* iters, uint8_t* hit, 
 {
     const int th = d->tile_rows ? d->tile_rows : 4;
     memset(a, 0, sizeof *a);
+    if (int rc = scene_data(d->scene_id, &a->scene_data)) return rc;
     for (int i = 0; i < 14; ++i) a->single.cam.v[i] = d->cam[i];
     a->single.cfg = to_cfg(d->march);
     a->frames = nullptr;
@@ -288,7 +359,7 @@ int make_args(const RmFrameDesc* d, float* depth, int32_t* iters, uint8_t* hit, 
         wgs = (d->grid_waves + rm::kWavesPerWG - 1) / rm::kWavesPerWG;
     } else {
         int per_cu = 0;
-        hipError_t e = rm::scene(d->scene_id)->occupancy(d->strategy_id, th, a->interleave, 0, &per_cu);
+        hipError_t e = launchers(d->scene_id)->occupancy(d->strategy_id, th, a->interleave, 0, &per_cu);
         if (e != hipSuccess || per_cu <= 0) per_cu = 2;
         // three workgroups per CU at most: the cheap scenes fit four, and measured 10-16 % slower with
         // four (Sphere 0.50 -> 0.45 ms, Cube 0.40 -> 0.34) while the long-ray scenes are indifferent
@@ -389,6 +460,7 @@ long long g_queue_cap = kQueueCapMax;           // rm_set_queue_capacity
 // producer (52.5 ms without suspension, 59 with the pipeline).  Other scenes keep their measured pass schedules.
 int pipeline_mode(const RmFrameDesc* d, long long rays)
 {
+    if (is_program_id(d->scene_id)) return 1;      // a scene program has no single-launch form
     if (d->pipeline != 0) return d->pipeline;
     return (d->scene_id == 10 && rays <= 24000000ll && d->march.max_iterations > 128) ? 2 : 1;
 }
@@ -516,7 +588,7 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
     if (!(own_stats && g.stats_ready)) HIP_TRY(hipMemsetAsync(a.stats, 0, kStatsBytes, s));
     if (own_stats) g.stats_ready = a.fused_reduce != 0;
     if (d->rows == 0) return RM_OK;
-    const rm::SceneLaunchers* const sc = rm::scene(d->scene_id);
+    const rm::SceneLaunchers* const sc = launchers(d->scene_id);
     if (d->tile_rows == 1 && !(park[0] > 0 && mode == 2 && sc->has_teams))
         return fail(RM_E_BAD_ARG, "tile_rows = 1 exists for the single launch (pipeline = 2 with suspension) of scenes with a team form");
     if (park[0] > 0 && mode == 2 && sc->has_teams && (d->tile_rows == 1 || (d->tile_rows == 0 && d->tile_order_mode == 1))) {
@@ -577,7 +649,7 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
     if (park[0] > 0) {
         const long long total = (long long)a.rows * a.width * a.nframes;
         const long long cap = std::min<long long>(total, g_queue_cap);
-        const int stride = rm::scene(d->scene_id)->entry_bytes(d->strategy_id);
+        const int stride = launchers(d->scene_id)->entry_bytes(d->strategy_id);
         int rc;
         for (int q = 0; q < (park[1] > 0 ? 2 : 1); ++q) {
             const size_t need = (size_t)cap * (size_t)stride;
@@ -738,23 +810,23 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
         b.refill_min = 16;
         // one workgroup per compute unit: measured best for both the dense second pass and the sparse last one
         const int rgrid = d->resume_grid > 0 ? d->resume_grid : std::min(grid, g.prop.multiProcessorCount);
-        const bool team = rm::scene(d->scene_id)->resume_team != nullptr && d->resume_mode != 1;
+        const bool team = launchers(d->scene_id)->resume_team != nullptr && d->resume_mode != 1;
         // KEEP BUSY (rm_kernels.h): a team pass is followed by as many filler workgroups, which start when its queue is handed out
         b.team_wgs = rgrid;
         b.keep_busy = team ? (d->keep_busy > 0 ? d->keep_busy : (d->keep_busy == 0 ? 256 : 0)) : 0;
         const int tgrid = b.keep_busy > 0 ? 2 * rgrid : rgrid;
         if (team && (park[1] == 0 || d->resume_mode == 3))
-            HIP_TRY(rm::scene(d->scene_id)->resume_team(d->strategy_id, 0, b, tgrid, s));
+            HIP_TRY(launchers(d->scene_id)->resume_team(d->strategy_id, 0, b, tgrid, s));
         else
-            HIP_TRY(rm::scene(d->scene_id)->resume(d->strategy_id, 0, b, rgrid, s));
+            HIP_TRY(launchers(d->scene_id)->resume(d->strategy_id, 0, b, rgrid, s));
         if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
         if (park[1] > 0) {
             b.suspend_after = 0;
             b.interleave = 0;       // a sparse pass of very long rays is latency-bound: whole evaluations per turn
             if (team)
-                HIP_TRY(rm::scene(d->scene_id)->resume_team(d->strategy_id, 1, b, tgrid, s));
+                HIP_TRY(launchers(d->scene_id)->resume_team(d->strategy_id, 1, b, tgrid, s));
             else
-                HIP_TRY(rm::scene(d->scene_id)->resume(d->strategy_id, 1, b, rgrid, s));
+                HIP_TRY(launchers(d->scene_id)->resume(d->strategy_id, 1, b, rgrid, s));
             if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
         }
     }
@@ -955,6 +1027,41 @@ extern "C" {
 
 const char* rm_last_error(void) { return g_err; }
 int rm_num_scenes(void) { return RM_NUM_SCENES; }
+
+int rm_scene_program_create(const RmSceneOp* ops, int32_t nops, double lipschitz, int32_t* scene_id)
+{
+    if (!scene_id) return fail(RM_E_BAD_ARG, "scene_id is NULL");
+    if (!(lipschitz > 0.0) || !(lipschitz - lipschitz == 0.0)) return fail(RM_E_BAD_ARG, "lipschitz must be finite and > 0");
+    std::unique_ptr<rm::ProgramImage> img(new rm::ProgramImage());
+    char why[256];
+    if (!rm::program_encode(ops, nops, img.get(), why, sizeof why)) return fail(RM_E_BAD_ARG, "scene program: %s", why);
+    std::lock_guard<std::mutex> lk(g_prog_mu);
+    if (g_next_program == INT32_MAX) return fail(RM_E_BAD_ARG, "scene program ids exhausted");
+    const int32_t id = g_next_program++;
+    Program& p = g_programs[id];
+    p.img = std::move(img);
+    p.lipschitz = lipschitz;
+    *scene_id = id;
+    return RM_OK;
+}
+
+int rm_scene_program_destroy(int32_t scene_id)
+{
+    std::lock_guard<std::mutex> lk(g_mu);       // no call of this library is enqueueing a frame of the program meanwhile
+    void* dev = nullptr;
+    {
+        std::lock_guard<std::mutex> lp(g_prog_mu);
+        auto it = g_programs.find(scene_id);
+        if (it == g_programs.end()) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", scene_id);
+        dev = it->second.dev;
+        g_programs.erase(it);
+    }
+    if (dev) {
+        if (g.ready) (void)hipSetDevice(g.device);
+        HIP_TRY(hipFree(dev));
+    }
+    return RM_OK;
+}
 int rm_num_strategies(void) { return RM_NUM_STRATEGIES; }
 
 void rm_default_strategy_params(RmStrategyParams* out)
@@ -1009,6 +1116,15 @@ void rm_shutdown(void)
     if (g.pev_ready) for (auto& e : g.pev) (void)hipEventDestroy(e);
     g.pev_ready = false;
     g.pass_timing = false;
+    {
+        // programs stay registered; their device copies are made again by the next frame after rm_init
+        std::lock_guard<std::mutex> lp(g_prog_mu);
+        for (auto& kv : g_programs)
+            if (kv.second.dev) {
+                (void)hipFree(kv.second.dev);
+                kv.second.dev = nullptr;
+            }
+    }
 
     (void)hipStreamDestroy(g.stream);
     g.stream = nullptr;
@@ -1036,14 +1152,16 @@ int rm_sdf_eval(int scene_id, const double* xyz, size_t n, double* out)
 {
     int rc = check_ready();
     if (rc) return rc;
-    if (scene_id < 0 || scene_id >= RM_NUM_SCENES || !rm::scene(scene_id)) return fail(RM_E_BAD_SCENE, "scene_id %d out of range", scene_id);
+    if ((rc = check_scene(scene_id))) return rc;
     if (n == 0) return RM_OK;
     if (!xyz || !out) return fail(RM_E_BAD_ARG, "NULL buffer");
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g.device));
+    const void* data = nullptr;
+    if ((rc = scene_data(scene_id, &data))) return rc;
     if ((rc = g.in0.ensure(n * 24)) || (rc = g.out0.ensure(n * 8))) return rc;
     HIP_TRY(hipMemcpyAsync(g.in0.p, xyz, n * 24, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(rm::scene(scene_id)->sdf_eval((const double*)g.in0.p, n, (double*)g.out0.p, g.stream));
+    HIP_TRY(launchers(scene_id)->sdf_eval((const double*)g.in0.p, n, (double*)g.out0.p, data, g.stream));
     HIP_TRY(hipMemcpyAsync(out, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return RM_OK;
@@ -1054,15 +1172,17 @@ static int march_rays_impl(bool team, int scene_id, int strategy_id, const RmMar
 {
     int rc = check_ready();
     if (rc) return rc;
-    if (scene_id < 0 || scene_id >= RM_NUM_SCENES || !rm::scene(scene_id)) return fail(RM_E_BAD_SCENE, "scene_id %d out of range", scene_id);
+    if ((rc = check_scene(scene_id))) return rc;
     if (strategy_id < 0 || strategy_id >= RM_NUM_STRATEGY_KERNELS)
         return fail(RM_E_BAD_STRATEGY, "strategy_id %d out of range", strategy_id);
     if (!cfg) return fail(RM_E_BAD_ARG, "cfg is NULL");
-    if (team && !rm::scene(scene_id)->march_rays_team) return fail(RM_E_BAD_SCENE, "scene %d has no wavefront-team form", scene_id);
+    if (team && !launchers(scene_id)->march_rays_team) return fail(RM_E_BAD_SCENE, "scene %d has no wavefront-team form", scene_id);
     if (n == 0) return RM_OK;
     if (!origins || !dirs || !hit || !t || !iters || !final_sdf) return fail(RM_E_BAD_ARG, "NULL buffer");
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g.device));
+    const void* data = nullptr;
+    if ((rc = scene_data(scene_id, &data))) return rc;
     if ((rc = g.in0.ensure(n * 24)) || (rc = g.in1.ensure(n * 24)) || (rc = g.out0.ensure(n)) ||
         (rc = g.out1.ensure(n * 8)) || (rc = g.out2.ensure(n * 4)) || (rc = g.out3.ensure(n * 8)))
         return rc;
@@ -1077,12 +1197,12 @@ static int march_rays_impl(bool team, int scene_id, int strategy_id, const RmMar
         HIP_TRY(hipMemsetAsync(g.busy.p, 0, sizeof(unsigned long long), g.stream));
         const long long nteams = (long long)((n + 63) / 64);
         const int fillers = (int)std::max<long long>(0, 2ll * g.prop.multiProcessorCount - nteams);
-        HIP_TRY(rm::scene(scene_id)->march_rays_team(strategy_id, c, (const double*)g.in0.p, (const double*)g.in1.p, n, (uint8_t*)g.out0.p,
+        HIP_TRY(launchers(scene_id)->march_rays_team(strategy_id, c, (const double*)g.in0.p, (const double*)g.in1.p, n, (uint8_t*)g.out0.p,
                                                      (double*)g.out1.p, (int32_t*)g.out2.p, (double*)g.out3.p,
                                                      (unsigned long long*)g.busy.p, fillers, g.stream));
     } else {
-        HIP_TRY(rm::scene(scene_id)->march_rays(strategy_id, c, (const double*)g.in0.p, (const double*)g.in1.p, n, (uint8_t*)g.out0.p,
-                                                (double*)g.out1.p, (int32_t*)g.out2.p, (double*)g.out3.p, g.stream));
+        HIP_TRY(launchers(scene_id)->march_rays(strategy_id, c, (const double*)g.in0.p, (const double*)g.in1.p, n, (uint8_t*)g.out0.p,
+                                                (double*)g.out1.p, (int32_t*)g.out2.p, (double*)g.out3.p, data, g.stream));
     }
     HIP_TRY(hipMemcpyAsync(hit, g.out0.p, n, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipMemcpyAsync(t, g.out1.p, n * 8, hipMemcpyDeviceToHost, g.stream));
@@ -1270,7 +1390,7 @@ int rm_render_batch_outputs(const RmFrameDesc* shape, int32_t nframes, const dou
     if (d.grid_waves <= 0) {      // the batch is one big launch: size the persistent grid for all its tiles
         const long long ntiles = (long long)a.tiles_per_frame * nframes;
         int per_cu = 0;
-        if (rm::scene(d.scene_id)->occupancy(d.strategy_id, tile_h, a.interleave, 1, &per_cu) != hipSuccess || per_cu <= 0) per_cu = 2;
+        if (launchers(d.scene_id)->occupancy(d.strategy_id, tile_h, a.interleave, 1, &per_cu) != hipSuccess || per_cu <= 0) per_cu = 2;
         per_cu = std::min(per_cu, 3);
         grid = (int)std::max<long long>(1, std::min<long long>((long long)g.prop.multiProcessorCount * per_cu,
                                                                 (ntiles + rm::kWavesPerWG - 1) / rm::kWavesPerWG));

@@ -172,6 +172,9 @@ struct KernelArgs {
     uint32_t trace_cap;
     uint32_t* trace_start;
     uint32_t* trace_detach;
+    // Scenes with launch data (SceneProgram, rm_scene_program.h): the device image of the program the launch renders;
+    // nullptr for the catalogue scenes.
+    const void* scene_data;
 };
 
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -228,6 +231,18 @@ template <class T>
 __device__ __forceinline__ void copy_table(T* dst, const T* src, int n)
 {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
+// Scenes whose SDF reads data of the launch (Scene::kLaunchData: SceneProgram, rm_scene_program.h) copy it into LDS in the
+// prologue; rm_load_tables() that follows ends with the barrier.  Nothing for the catalogue scenes.
+template <class Scene, class = void>
+struct SceneLaunchData : std::false_type {};
+template <class Scene>
+struct SceneLaunchData<Scene, decltype((void)Scene::kLaunchData)> : std::integral_constant<bool, Scene::kLaunchData> {};
+template <class Scene>
+__device__ __forceinline__ void rm_load_scene_data(const void* data)
+{
+    if constexpr (SceneLaunchData<Scene>::value) Scene::load(data);
 }
 
 template <class Scene>
@@ -455,6 +470,7 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void render_kernel(const Kerne
     const int ntiles = a.tiles_per_frame * a.nframes;
 
     for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) s_hist[b] = 0u;
+    rm_load_scene_data<Scene>(a.scene_data);
     rm_load_tables<Scene>();
     __syncthreads();
 
@@ -738,6 +754,7 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void resume_kernel(const Kerne
     __shared__ unsigned int s_hist[kHistBins];
     const int lane = lane_id();
     for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) s_hist[b] = 0u;
+    rm_load_scene_data<Scene>(a.scene_data);
     rm_load_tables<Scene>();
     __syncthreads();
 
@@ -866,18 +883,22 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void resume_kernel(const Kerne
 
 // ---- test entry points: explicit points / rays, one per thread ----------------------
 
+// (launch bounds: the block sizes the launchers use -- the register budget of a scene program's interpreter needs more
+// than the 128 VGPRs of the 1024-thread default)
 template <class Scene>
-__global__ void sdf_eval_kernel(const double* __restrict__ xyz, size_t n, double* __restrict__ out)
+__global__ __launch_bounds__(256) void sdf_eval_kernel(const double* __restrict__ xyz, size_t n, double* __restrict__ out, const void* scene_data)
 {
+    rm_load_scene_data<Scene>(scene_data);
     rm_load_tables<Scene>();
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = Scene::sdf(v3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]));
 }
 
 template <class Scene, class Strat>
-__global__ void march_rays_kernel(MarchCfg cfg, const double* __restrict__ origins, const double* __restrict__ dirs,
-                                  size_t n, uint8_t* hit, double* t, int32_t* iters, double* final_sdf)
+__global__ __launch_bounds__(64) void march_rays_kernel(MarchCfg cfg, const double* __restrict__ origins, const double* __restrict__ dirs,
+                                  size_t n, uint8_t* hit, double* t, int32_t* iters, double* final_sdf, const void* scene_data)
 {
+    rm_load_scene_data<Scene>(scene_data);
     rm_load_tables<Scene>();
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1165,9 +1186,10 @@ struct SceneLaunchers {
     bool has_teams;
     int (*entry_bytes)(int strategy);   // sizeof(QEntry<Strat>)
     hipError_t (*occupancy)(int strategy, int tile_h, int interleave, int batch, int* blocks_per_cu);
-    hipError_t (*sdf_eval)(const double* xyz, size_t n, double* out, hipStream_t s);
+    // scene_data: KernelArgs.scene_data (nullptr for the catalogue scenes)
+    hipError_t (*sdf_eval)(const double* xyz, size_t n, double* out, const void* scene_data, hipStream_t s);
     hipError_t (*march_rays)(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,
-                             uint8_t* hit, double* t, int32_t* iters, double* fs, hipStream_t s);
+                             uint8_t* hit, double* t, int32_t* iters, double* fs, const void* scene_data, hipStream_t s);
     // nullptr: no team form.  busy: a zeroed device word -> `fillers` more workgroups keep the chip busy until the teams are through
     hipError_t (*march_rays_team)(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,
                                   uint8_t* hit, double* t, int32_t* iters, double* fs, unsigned long long* busy, int fillers, hipStream_t s);

@@ -1,0 +1,345 @@
+// rm_scene_program.h -- user-defined CSG scenes: a postfix program of the reference's scenes/primitives.py functions,
+// validated and encoded on the host, evaluated by an interpreter on the device (SceneProgram::sdf).
+//
+// Format (RmSceneOp, include/rm_hip.h): primitives push a distance, combinators pop two and push one, distance
+// modifiers replace the top one, point transforms save the current point and replace it, RM_SOP_POP_POINT restores
+// it.  The host resolves every stack position once (program_encode): each instruction word carries its opcode, the
+// value slot it writes (a binary combinator reads that slot and the next), the point slot it saves to / restores from,
+// and the offset of its constants.  The device never tracks a stack pointer and never indexes an array by a runtime
+// value: the eight value slots and four saved points are named registers, selected by selects on the slot number,
+// which is wave-uniform (no scratch: a runtime-indexed private array would live there).
+//
+// Where the program lives: the launch passes the device copy of its ProgramImage (KernelArgs.scene_data); the
+// kernel's prologue copies the used part into LDS next to the libm tables (rm_load_scene_data, rm_kernels.h), and
+// every instruction word is read with a wave-uniform address and moved to a scalar register (readfirstlane), so the
+// opcode dispatch is a chain of scalar branches, not a waterfall over lanes.
+//
+// Arithmetic: the helpers of rm_scenes.h (py_max / py_min, pow_half, rm_pow(x, 2.0) where the reference writes `** 2`),
+// the reference's evaluation order, no contraction; op_repeat uses CPython's float.__mod__ (exact fmod + float_rem's
+// sign fix), which equals py_mod_pow2 on the power-of-two spacings of the catalogue (and uses it there).
+#pragma once
+
+#include "../../include/rm_hip.h"
+#include "rm_scenes.h"
+
+#include <stdio.h>
+#include <string.h>
+
+namespace rm {
+
+constexpr int kProgMaxOps = RM_SCENE_PROGRAM_MAX_OPS;
+constexpr int kProgMaxArgs = 7;                        // RM_SOP_CAPSULE
+constexpr int kProgMaxConst = kProgMaxArgs * kProgMaxOps;
+constexpr uint32_t kProgTranslated = 1u << 13;
+
+// The device image of a program (what a launch's scene_data points to).  code[i]: bits 0-5 opcode, 6-9 value slot,
+// 10-12 point slot, 13-15 axes of RM_SOP_REPEAT with a positive spacing, 16-31 offset of the constants in k[].  Two
+// flags reuse bits a word's opcode leaves free:
+//  * a primitive with bit 13 set is `translate, primitive, pop point` fused (its first three constants are the offset):
+//    the same arithmetic, p - offset then the primitive, without the trip through the point stack;
+//  * RM_SOP_REPEAT: bits 6-8 mark the axes whose spacing is a power of two in [2^-64, 2^64]; there py_mod_pow2 (the
+//    catalogue's exact division-free remainder) replaces fmod for |x| < 2^900.
+struct ProgramImage {
+    int32_t nops, nconst;
+    uint32_t code[kProgMaxOps];
+    double k[kProgMaxConst];
+};
+
+// constants each opcode reads (RmSceneOp.f)
+RM_HD int program_op_args(int op)
+{
+    switch (op) {
+        case RM_SOP_SPHERE: return 1;
+        case RM_SOP_BOX: return 3;
+        case RM_SOP_PLANE: return 4;
+        case RM_SOP_CYLINDER: return 2;
+        case RM_SOP_TORUS: return 2;
+        case RM_SOP_CAPSULE: return 7;
+        case RM_SOP_CAPPED_TORUS: return 4;
+        case RM_SOP_CONE: return 3;
+        case RM_SOP_SMOOTH_UNION: case RM_SOP_SMOOTH_SUBTRACT: case RM_SOP_SMOOTH_INTERSECT: return 1;
+        case RM_SOP_TRANSLATE: case RM_SOP_REPEAT: return 3;
+        case RM_SOP_ROUND: case RM_SOP_ONION: return 1;
+        default: return 0;
+    }
+}
+
+// ---- scenes/primitives.py functions rm_scenes.h does not already hold ---------------------------------------------
+
+RM_HD double sd_capsule(vec3 p, vec3 a, vec3 b, double radius)                          // :34-39
+{
+    vec3 ab = b - a;
+    vec3 ap = p - a;
+    double t = py_max(0.0, py_min(1.0, dot(ap, ab) / py_max(dot(ab, ab), 1e-12)));
+    vec3 closest = a + ab * t;
+    return length(p - closest) - radius;
+}
+
+// c = math.cos(angle_rad), s = math.sin(angle_rad): computed by the host (the reference's libm), not here
+RM_HD double sd_cone(vec3 p, double c, double s, double height)                         // :53-65
+{
+    double q_len = pow_half(p.x * p.x + p.z * p.z);
+    // q = (q_len, p.y, 0); tip_dist (:61) is computed by the reference and never used
+    double d1 = p.y - (-height);
+    double d2 = q_len * c + p.y * s;
+    return py_max(-d1, d2);
+}
+
+RM_HD double op_smooth_subtract(double d1, double d2, double k) { return -op_smooth_union(-d1, d2, k); }    // :88-89
+RM_HD double op_smooth_intersect(double d1, double d2, double k) { return -op_smooth_union(-d1, -d2, k); }  // :91-92
+
+// float.__mod__ (CPython float_rem) for b > 0: fmod is exact; a non-zero remainder takes the divisor's sign, a zero
+// one is +0.0
+RM_HD double py_mod(double a, double b)
+{
+    double m = fmod(a, b);
+    if (m != 0.0) {
+        if ((b < 0.0) != (m < 0.0)) m += b;
+    } else {
+        m = 0.0;
+    }
+    return m;
+}
+
+// op_repeat (:102-108), one axis with spacing > 0; pow2: the spacing is a power of two in [2^-64, 2^64] (wave-uniform).
+// py_mod_pow2's quotient is exact unless it overflows, which |x| < 2^900 excludes; the guard is a per-lane branch that
+// no lane of a ray march takes.
+RM_HD double repeat_axis_any(double x, double spacing, bool pow2)
+{
+    const double a = x + spacing * 0.5;
+    double m;
+    if (pow2 && rm_fabs(a) < 0x1p900)
+        m = py_mod_pow2(a, spacing);
+    else
+        m = py_mod(a, spacing);
+    return m - spacing * 0.5;
+}
+
+// ---- the interpreter ----------------------------------------------------------------------------------------------
+
+// The register stacks are plain local variables of program_eval -- eight value slots v0..v7, four saved points
+// (x0, y0, z0) .. (x3, y3, z3) -- and slot i (wave-uniform) is reached by selects on i (v_cndmask with a scalar mask).
+// No access has a computed address, so nothing can move them to scratch: a struct of slots read through a switch or a
+// chain of selects is turned back into a load from a selected address by the compiler, and then lives in scratch.
+// Out-of-range slots cannot occur after program_encode; they would read the last slot and write nothing.
+#define RM_PV_GET(i, r)                                                                                               \
+    do {                                                                                                              \
+        r = v7; r = (i) == 6 ? v6 : r; r = (i) == 5 ? v5 : r; r = (i) == 4 ? v4 : r;                                  \
+        r = (i) == 3 ? v3_ : r; r = (i) == 2 ? v2 : r; r = (i) == 1 ? v1 : r; r = (i) == 0 ? v0 : r;                  \
+    } while (0)
+#define RM_PV_SET(i, x)                                                                                               \
+    do {                                                                                                              \
+        v0 = (i) == 0 ? (x) : v0; v1 = (i) == 1 ? (x) : v1; v2 = (i) == 2 ? (x) : v2; v3_ = (i) == 3 ? (x) : v3_;     \
+        v4 = (i) == 4 ? (x) : v4; v5 = (i) == 5 ? (x) : v5; v6 = (i) == 6 ? (x) : v6; v7 = (i) == 7 ? (x) : v7;       \
+    } while (0)
+#define RM_PP_SET1(j, i, q)                                                                                           \
+    do {                                                                                                              \
+        x##j = (i) == j ? q.x : x##j; y##j = (i) == j ? q.y : y##j; z##j = (i) == j ? q.z : z##j;                     \
+    } while (0)
+
+// Src: nops(), word(i) (wave-uniform), k(i)
+template <class Src>
+RM_HD double program_eval(const Src& src, vec3 p)
+{
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3_ = 0.0, v4 = 0.0, v5 = 0.0, v6 = 0.0, v7 = 0.0;
+    double x0 = p.x, y0 = p.y, z0 = p.z, x1 = p.x, y1 = p.y, z1 = p.z;
+    double x2 = p.x, y2 = p.y, z2 = p.z, x3 = p.x, y3 = p.y, z3 = p.z;
+    const int n = src.nops();
+    for (int pc = 0; pc < n; ++pc) {
+        const uint32_t w = src.word(pc);
+        const int slot = (int)((w >> 6) & 15u);
+        const int pslot = (int)((w >> 10) & 7u);
+        const int ko = (int)(w >> 16);
+        const int op = (int)(w & 63u);
+        if (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) {
+            if (op == RM_SOP_POP_POINT) {
+                vec3 r = v3(x3, y3, z3);
+                r = pslot == 2 ? v3(x2, y2, z2) : r;
+                r = pslot == 1 ? v3(x1, y1, z1) : r;
+                r = pslot == 0 ? v3(x0, y0, z0) : r;
+                p = r;
+            } else {
+                RM_PP_SET1(0, pslot, p); RM_PP_SET1(1, pslot, p); RM_PP_SET1(2, pslot, p); RM_PP_SET1(3, pslot, p);
+                const double kx = src.k(ko), ky = src.k(ko + 1), kz = src.k(ko + 2);
+                if (op == RM_SOP_TRANSLATE) {
+                    p = p - v3(kx, ky, kz);                                          // :99-100
+                } else {                                                             // :102-108
+                    if (w & (1u << 13)) p.x = repeat_axis_any(p.x, kx, (w & (1u << 6)) != 0);
+                    if (w & (1u << 14)) p.y = repeat_axis_any(p.y, ky, (w & (1u << 7)) != 0);
+                    if (w & (1u << 15)) p.z = repeat_axis_any(p.z, kz, (w & (1u << 8)) != 0);
+                }
+            }
+            continue;
+        }
+        double r;
+        if (op <= RM_SOP_CONE) {                                                     // primitives: push
+            vec3 p0 = p;
+            int ko = (int)(w >> 16);
+            if (w & kProgTranslated) {                                               // fused op_translate (:99-100)
+                p = p - v3(src.k(ko), src.k(ko + 1), src.k(ko + 2));
+                ko += 3;
+            }
+            switch (op) {
+                case RM_SOP_SPHERE: r = sd_sphere(p, src.k(ko)); break;
+                case RM_SOP_BOX: r = sd_box(p, v3(src.k(ko), src.k(ko + 1), src.k(ko + 2))); break;
+                case RM_SOP_PLANE: r = sd_plane(p, v3(src.k(ko), src.k(ko + 1), src.k(ko + 2)), src.k(ko + 3)); break;
+                case RM_SOP_CYLINDER: r = sd_cylinder(p, src.k(ko), src.k(ko + 1)); break;
+                case RM_SOP_TORUS: r = sd_torus(p, src.k(ko), src.k(ko + 1)); break;
+                case RM_SOP_CAPSULE:
+                    r = sd_capsule(p, v3(src.k(ko), src.k(ko + 1), src.k(ko + 2)), v3(src.k(ko + 3), src.k(ko + 4), src.k(ko + 5)),
+                                   src.k(ko + 6));
+                    break;
+                case RM_SOP_CAPPED_TORUS: r = sd_capped_torus(p, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
+                default: r = sd_cone(p, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
+            }
+            p = p0;
+        } else {
+            double a, b;
+            RM_PV_GET(slot, a);
+            if (op >= RM_SOP_ROUND) {                                                // distance modifiers
+                r = op == RM_SOP_ROUND ? a - src.k(ko) : rm_fabs(a) - src.k(ko);     // :110-111, :113-114
+            } else {                                                                 // combinators: d1 = a, d2 = b
+                RM_PV_GET(slot + 1, b);
+                switch (op) {
+                    case RM_SOP_UNION: r = py_min(a, b); break;                                     // :70
+                    case RM_SOP_SUBTRACT: r = py_max(a, -b); break;                                 // :73
+                    case RM_SOP_INTERSECT: r = py_max(a, b); break;                                 // :77
+                    case RM_SOP_SMOOTH_UNION: r = op_smooth_union(a, b, src.k(ko)); break;          // :80-86
+                    case RM_SOP_SMOOTH_SUBTRACT: r = op_smooth_subtract(a, b, src.k(ko)); break;    // :88-89
+                    default: r = op_smooth_intersect(a, b, src.k(ko)); break;                       // :91-92
+                }
+            }
+        }
+        RM_PV_SET(slot, r);
+    }
+    return v0;
+}
+#undef RM_PV_GET
+#undef RM_PV_SET
+#undef RM_PP_SET1
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// the program of the launch, copied by SceneProgram::load (used only by the SceneProgram kernels)
+__shared__ uint32_t rm_s_prog_code[kProgMaxOps];
+__shared__ double rm_s_prog_k[kProgMaxConst];
+__shared__ int32_t rm_s_prog_nops;
+struct ProgSrc {
+    __device__ __forceinline__ int nops() const { return __builtin_amdgcn_readfirstlane(rm_s_prog_nops); }
+    __device__ __forceinline__ uint32_t word(int i) const { return (uint32_t)__builtin_amdgcn_readfirstlane((int)rm_s_prog_code[i]); }
+    __device__ __forceinline__ double k(int i) const { return rm_s_prog_k[i]; }
+};
+#else
+// host builds (tests/native): the program SceneProgram::sdf evaluates on this thread
+inline thread_local const ProgramImage* rm_host_program = nullptr;
+struct ProgSrc {
+    const ProgramImage* img;
+    int nops() const { return img ? img->nops : 0; }
+    uint32_t word(int i) const { return img->code[i]; }
+    double k(int i) const { return img->k[i]; }
+};
+#endif
+
+struct SceneProgram {
+    static constexpr bool kLaunchData = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // prologue of a kernel (all threads of the workgroup; the barrier follows in rm_load_tables).  The bounds are
+    // program_encode's; the clamps only keep a corrupt image inside the LDS arrays.
+    static __device__ __forceinline__ void load(const void* data)
+    {
+        const ProgramImage* img = static_cast<const ProgramImage*>(data);
+        const int n = min(max(img->nops, 0), kProgMaxOps), nk = min(max(img->nconst, 0), kProgMaxConst);
+        for (int i = threadIdx.x; i < n; i += blockDim.x) rm_s_prog_code[i] = img->code[i];
+        for (int i = threadIdx.x; i < nk; i += blockDim.x) rm_s_prog_k[i] = img->k[i];
+        if (threadIdx.x == 0) rm_s_prog_nops = n;
+    }
+    static __device__ __forceinline__ double sdf(vec3 p) { return program_eval(ProgSrc{}, p); }
+#else
+#if defined(__HIPCC__)
+    static __device__ void load(const void*) {}      // (hipcc's host pass; the device pass has the body above)
+#endif
+    static inline double sdf(vec3 p) { return program_eval(ProgSrc{ rm_host_program }, p); }
+#endif
+};
+
+// (host code) Validates a program and writes its device image.  false with the reason in `why` for a malformed program: opcode out
+// of range, reserved field set, non-finite or (for unused entries) non-zero constant, smooth k == 0 (a division by zero
+// in the reference), value stack deeper than RM_SCENE_PROGRAM_MAX_VALUES or popped when empty, more than
+// RM_SCENE_PROGRAM_MAX_POINTS nested transforms or a pop without a transform, not exactly one value left, a transform
+// left open, length outside 1..RM_SCENE_PROGRAM_MAX_OPS.
+inline bool program_encode(const RmSceneOp* ops, int32_t nops, ProgramImage* img, char* why, size_t why_len)
+{
+    if (!ops) return snprintf(why, why_len, "ops is NULL"), false;
+    if (nops <= 0 || nops > kProgMaxOps) return snprintf(why, why_len, "program length %d outside 1..%d", nops, kProgMaxOps), false;
+    memset(img, 0, sizeof *img);
+    uint32_t word[kProgMaxOps];       // per op: opcode and slot fields (validation pass)
+    int vsp = 0, psp = 0;
+    for (int i = 0; i < nops; ++i) {
+        const RmSceneOp& o = ops[i];
+        if (o.op < 0 || o.op >= RM_SOP_COUNT) return snprintf(why, why_len, "op %d: opcode %d out of range", i, o.op), false;
+        if (o.arg != 0) return snprintf(why, why_len, "op %d: reserved field arg is %d, must be 0", i, o.arg), false;
+        const int na = program_op_args(o.op);
+        for (int j = 0; j < 8; ++j) {
+            const double f = o.f[j];
+            if (!(f - f == 0.0)) return snprintf(why, why_len, "op %d: constant f[%d] is not finite", i, j), false;
+            if (j >= na && f != 0.0) return snprintf(why, why_len, "op %d: unused constant f[%d] must be 0", i, j), false;
+        }
+        uint32_t slot = 0, pslot = 0, axes = 0;
+        switch (o.op) {
+            case RM_SOP_UNION: case RM_SOP_SUBTRACT: case RM_SOP_INTERSECT:
+            case RM_SOP_SMOOTH_UNION: case RM_SOP_SMOOTH_SUBTRACT: case RM_SOP_SMOOTH_INTERSECT:
+                if (vsp < 2) return snprintf(why, why_len, "op %d: combinator needs two values, the stack holds %d", i, vsp), false;
+                if (o.op >= RM_SOP_SMOOTH_UNION && o.f[0] == 0.0) return snprintf(why, why_len, "op %d: smooth k must not be 0", i), false;
+                slot = (uint32_t)(vsp - 2);
+                --vsp;
+                break;
+            case RM_SOP_ROUND: case RM_SOP_ONION:
+                if (vsp < 1) return snprintf(why, why_len, "op %d: modifier needs a value, the stack is empty", i), false;
+                slot = (uint32_t)(vsp - 1);
+                break;
+            case RM_SOP_TRANSLATE: case RM_SOP_REPEAT:
+                if (psp >= RM_SCENE_PROGRAM_MAX_POINTS)
+                    return snprintf(why, why_len, "op %d: more than %d nested transforms", i, RM_SCENE_PROGRAM_MAX_POINTS), false;
+                pslot = (uint32_t)psp++;
+                if (o.op == RM_SOP_REPEAT)
+                    for (int j = 0; j < 3; ++j)
+                        if (o.f[j] > 0.0) {
+                            axes |= 1u << j;
+                            int e = 0;
+                            const double m = frexp(o.f[j], &e);
+                            if (m == 0.5 && e >= -63 && e <= 65) slot |= 1u << j;      // a power of two in [2^-64, 2^64]
+                        }
+                break;
+            case RM_SOP_POP_POINT:
+                if (psp < 1) return snprintf(why, why_len, "op %d: pop point without a transform", i), false;
+                pslot = (uint32_t)--psp;
+                break;
+            default:   // primitives
+                if (vsp >= RM_SCENE_PROGRAM_MAX_VALUES)
+                    return snprintf(why, why_len, "op %d: value stack deeper than %d", i, RM_SCENE_PROGRAM_MAX_VALUES), false;
+                slot = (uint32_t)vsp++;
+                break;
+        }
+        word[i] = (uint32_t)o.op | slot << 6 | pslot << 10 | axes << 13;
+    }
+    if (vsp != 1) return snprintf(why, why_len, "program leaves %d values, must leave exactly 1", vsp), false;
+    if (psp != 0) return snprintf(why, why_len, "program leaves %d transforms without a pop point", psp), false;
+    // emit: `translate, primitive, pop point` becomes one word; constants in op order (at most kProgMaxArgs per op)
+    int n = 0, nk = 0;
+    for (int i = 0; i < nops; ++i) {
+        const RmSceneOp& o = ops[i];
+        if (o.op == RM_SOP_TRANSLATE && i + 2 < nops && ops[i + 1].op <= RM_SOP_CONE && ops[i + 2].op == RM_SOP_POP_POINT) {
+            img->code[n++] = word[i + 1] | kProgTranslated | (uint32_t)nk << 16;
+            for (int j = 0; j < 3; ++j) img->k[nk++] = o.f[j];
+            for (int j = 0; j < program_op_args(ops[i + 1].op); ++j) img->k[nk++] = ops[i + 1].f[j];
+            i += 2;
+            continue;
+        }
+        img->code[n++] = word[i] | (uint32_t)nk << 16;
+        for (int j = 0; j < program_op_args(o.op); ++j) img->k[nk++] = o.f[j];
+    }
+    img->nops = n;
+    img->nconst = nk;
+    return true;
+}
+
+}  // namespace rm

@@ -1,20 +1,30 @@
 // rm_scene_tu.hip -- one translation unit per scene (compile with -DRM_SCENE_ID=<0..19>).
 // Instantiates render / march_rays kernels for every strategy and the sdf_eval kernel
 // of that scene, and exports their launchers through rm::scene_launchers_<id>().
+// With -DRM_SCENE_PROGRAM instead: the same kernels for the scene-program interpreter (rm_scene_program.h), exported
+// through rm::scene_launchers_program(); no single-launch pipeline and no team forms.
 #include "rm_kernels.h"
+#if defined(RM_SCENE_PROGRAM)
+#include "rm_scene_program.h"
+#else
 #include "rm_pipeline.h"
+#endif
 
-#ifndef RM_SCENE_ID
-#error "compile with -DRM_SCENE_ID=<scene id>"
+#if !defined(RM_SCENE_ID) && !defined(RM_SCENE_PROGRAM)
+#error "compile with -DRM_SCENE_ID=<scene id> or -DRM_SCENE_PROGRAM"
 #endif
 
 namespace rm {
 
+#if defined(RM_SCENE_PROGRAM)
+using SceneT = SceneProgram;
+#else
 template <int ID> struct SceneById;
 #define RM_X(id, S) template <> struct SceneById<id> { using type = S; };
 RM_SCENE_LIST(RM_X)
 #undef RM_X
 using SceneT = SceneById<RM_SCENE_ID>::type;
+#endif
 
 constexpr bool kIter = SceneIterative<SceneT>::value;
 
@@ -58,6 +68,7 @@ static hipError_t occ_render(int interleave, int batch, int* blocks)
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, render_kernel<SceneT, Strat, TH, false, false>, 64 * kWavesPerWG, 0);
 }
 
+#if !defined(RM_SCENE_PROGRAM)
 // One-row tiles (TILE_H = 1) are built for the scenes with a team form only: there a frame ends with its longest
 // ray, and with 64x4 tiles that ray may sit in its tile's pixel pool for milliseconds behind lanes that older rays hold.
 template <class Strat, int TH>
@@ -118,6 +129,8 @@ static hipError_t occupancy_pipeline(int strategy, int interleave, int batch, in
     }
     return hipErrorInvalidValue;
 }
+
+#endif  // !RM_SCENE_PROGRAM
 
 static hipError_t render(int strategy, int tile_h, const KernelArgs& a, int grid, hipStream_t s)
 {
@@ -180,22 +193,22 @@ static hipError_t occupancy(int strategy, int tile_h, int interleave, int batch,
     return hipErrorInvalidValue;
 }
 
-static hipError_t sdf_eval(const double* xyz, size_t n, double* out, hipStream_t s)
+static hipError_t sdf_eval(const double* xyz, size_t n, double* out, const void* scene_data, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL((sdf_eval_kernel<SceneT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xyz, n, out);
+    hipLaunchKernelGGL((sdf_eval_kernel<SceneT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xyz, n, out, scene_data);
     return hipGetLastError();
 }
 
 static hipError_t march_rays(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,
-                             uint8_t* hit, double* t, int32_t* iters, double* fs, hipStream_t s)
+                             uint8_t* hit, double* t, int32_t* iters, double* fs, const void* scene_data, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
     dim3 grid((unsigned)((n + 63) / 64)), block(64);
     switch (strategy) {
 #define RM_X(id, S)                                                                                        \
     case id:                                                                                               \
-        hipLaunchKernelGGL((march_rays_kernel<SceneT, S>), grid, block, 0, s, cfg, o, d, n, hit, t, iters, fs); \
+        hipLaunchKernelGGL((march_rays_kernel<SceneT, S>), grid, block, 0, s, cfg, o, d, n, hit, t, iters, fs, scene_data); \
         return hipGetLastError();
         RM_STRATEGY_LIST(RM_X)
 #undef RM_X
@@ -223,6 +236,15 @@ static hipError_t march_rays_team_impl(int strategy, const MarchCfg& cfg, const 
     return hipErrorInvalidValue;
 }
 
+#if defined(RM_SCENE_PROGRAM)
+static_assert(!kIter, "a scene program has no resumable evaluation");
+const SceneLaunchers* scene_launchers_program()
+{
+    static const SceneLaunchers l = { render, resume, nullptr, nullptr, nullptr, false,
+                                      entry_bytes, occupancy, sdf_eval, march_rays, nullptr };
+    return &l;
+}
+#else
 #define RM_CAT2(a, b) a##b
 #define RM_CAT(a, b) RM_CAT2(a, b)
 // a host function (not a const global: hipcc would try to emit that for the device too)
@@ -232,5 +254,6 @@ const SceneLaunchers* RM_CAT(scene_launchers_, RM_SCENE_ID)()
                                       entry_bytes, occupancy, sdf_eval, march_rays, kIter ? march_rays_team_impl<kIter> : nullptr };
     return &l;
 }
+#endif
 
 }  // namespace rm

@@ -109,7 +109,14 @@ def cli(argv: Optional[list] = None) -> int:
                    help="give every scene a fresh RenderConfig (the reference CLI leaks the previous scene's camera)")
     p.add_argument("--no-gpu-columns", action="store_true", help="skip the separate timed GPU pass (gpu_* columns)")
     p.add_argument("--device", type=int, default=None)
+    p.add_argument("--scene-file", action="append", default=[], metavar="SCENES.json",
+                   help="register the user-defined scenes of a scene file (scene_program.py) so --scene can name them; "
+                        "repeatable ('all' stays the 20 catalogue scenes)")
     args = p.parse_args(argv)
+    if args.scene_file:
+        from .scene_program import load_scene_file
+        for path in args.scene_file:
+            load_scene_file(path)
 
     rc = RenderConfig(width=args.width, height=args.height)
     if args.gpu_width is not None or args.gpu_height is not None:

@@ -159,21 +159,74 @@ def _make_strategy(i: int, **ctor) -> StrategyInfo:
     return st
 
 
+# Scenes registered at run time (scene_program.register_scene): scene programs of the library, ids from
+# RM_SCENE_PROGRAM_BASE.  Not part of SCENES / get_all_scenes(), which stay the 20 catalogue scenes.
+_PROGRAM_SCENES: List[SceneInfo] = []
+
+
+def _norm(name: str) -> str:
+    return name.lower().replace(" ", "")
+
+
 def get_all_scenes() -> List[SceneInfo]:
     return list(SCENES)
 
 
 def get_scene_by_name(name: str) -> Optional[SceneInfo]:
     """Reference lookup rule (catalog.py:666-681): lower-case, strip SPACES only, exact then
-    starts-with; None on a miss ("Pillar_Forest" does not match, "Menger" does)."""
-    low = name.lower().replace(" ", "")
-    for s in SCENES:
-        if s.name.lower().replace(" ", "") == low:
+    starts-with; None on a miss ("Pillar_Forest" does not match, "Menger" does).  Registered scenes
+    come after the catalogue in both passes."""
+    low = _norm(name)
+    scenes = SCENES + list(_PROGRAM_SCENES)
+    for s in scenes:
+        if _norm(s.name) == low:
             return s
-    for s in SCENES:
-        if s.name.lower().replace(" ", "").startswith(low):
+    for s in scenes:
+        if _norm(s.name).startswith(low):
             return s
     return None
+
+
+def get_scene_by_id(scene_id: int) -> Optional[SceneInfo]:
+    """A catalogue scene by index, or a registered scene by its program id."""
+    sid = int(scene_id)
+    if 0 <= sid < len(SCENES):
+        return SCENES[sid]
+    return next((s for s in _PROGRAM_SCENES if s.id == sid), None)
+
+
+def find_scene_exact(name: str) -> Optional[SceneInfo]:
+    """Exact-name lookup (catalogue first): what the reference's GPU runner does (runner.py:275-280)."""
+    return next((s for s in SCENES + list(_PROGRAM_SCENES) if s.name == name), None)
+
+
+def find_program_scene(name: str) -> Optional[SceneInfo]:
+    """A registered scene by exact name, else by normalised name."""
+    return next((s for s in _PROGRAM_SCENES if s.name == name), None) or \
+        next((s for s in _PROGRAM_SCENES if _norm(s.name) == _norm(name)), None)
+
+
+def check_new_scene_name(name: str) -> None:
+    """ValueError if `name` normalises to a catalogue or registered scene's name."""
+    low = _norm(name)
+    for s in SCENES:
+        if _norm(s.name) == low:
+            raise ValueError(f"scene name {name!r} clashes with the catalogue scene {s.name!r}")
+    for s in _PROGRAM_SCENES:
+        if _norm(s.name) == low:
+            raise ValueError(f"scene name {name!r} clashes with the registered scene {s.name!r}")
+
+
+def add_program_scene(info: SceneInfo) -> None:
+    _PROGRAM_SCENES.append(info)
+
+
+def remove_program_scene(name: str) -> SceneInfo:
+    info = find_program_scene(name)
+    if info is None:
+        raise KeyError(f"no registered scene {name!r}")
+    _PROGRAM_SCENES.remove(info)
+    return info
 
 
 def get_strategy_by_name(name: str, **ctor) -> Optional[StrategyInfo]:

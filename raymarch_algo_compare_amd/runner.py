@@ -15,12 +15,12 @@ import numpy as np
 from . import _native
 from .camera import Camera
 from .config import MarchConfig, RenderConfig
-from .registry import SCENES, get_shader_strategy, get_strategy_by_name
+from .registry import SCENES, find_scene_exact, get_scene_by_id, get_shader_strategy, get_strategy_by_name
 
 
 def run_gpu_benchmark(scene_name: str, strategy_name: str, render_cfg: RenderConfig, march_cfg: MarchConfig, *,
                       gpu_warmup: int = 3, gpu_repeats: int = 7, device_id: int | None = None):
-    scene = next((s for s in SCENES if s.name == scene_name), None)      # exact name (runner.py:275-280)
+    scene = find_scene_exact(scene_name)      # exact name (runner.py:275-280); registered scenes too
     if scene is None:
         return None
     strategy = get_strategy_by_name(strategy_name)
@@ -125,8 +125,8 @@ class GPURunner:
         return out
 
     def _frame(self, scene_id, strategy, render_cfg, march_cfg, lipschitz, timed, want_evals, params=None):
-        if not 0 <= int(scene_id) < len(SCENES):
-            raise ValueError(f"scene id {scene_id} out of range")
+        if get_scene_by_id(scene_id) is None:
+            raise ValueError(f"scene id {scene_id} is neither a catalogue scene nor a registered scene")
         cam = Camera(render_cfg.camera_position, render_cfg.camera_target, render_cfg.camera_up,
                      render_cfg.fov_degrees, render_cfg.width, render_cfg.height)
         _native.init(self.device_id)
