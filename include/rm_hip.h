@@ -485,6 +485,35 @@ int rm_debug_set_trace(int enable);
 int rm_debug_get_trace(uint32_t* records, int64_t max_records, int64_t* nrecords, uint32_t* start_ticks,
                        uint32_t* detach_ticks, int64_t npix, uint32_t* launch_tick);
 
+/* Routines of the device math (csrc/rm_math_*.h) that rm_debug_math_eval evaluates; out0 / out1 per routine.  _U: the
+ * wave-uniform band-skipping forms the wavefront teams call; POW_HALF_SPARSE: the guarded square root of waves with at
+ * most 16 live lanes (pow for the lanes the guard refuses). */
+enum RmMathFn {
+    RM_MATH_POW = 0,            /* rm_pow(a, b) */
+    RM_MATH_POW2 = 1,           /* rm_pow2(a, 7.0, 8.0): a^7 / a^8 */
+    RM_MATH_POW_HALF_DENSE = 2, /* rm_pow_half<false>(a) */
+    RM_MATH_POW_HALF_SPARSE = 3,/* rm_pow_half<true>(a) */
+    RM_MATH_POW_HALF_GUARD = 4, /* rm_pow_half_guard(a): rounded root / safe flag as 0.0 or 1.0 */
+    RM_MATH_SQRT = 5,           /* rm_sqrt(a) */
+    RM_MATH_SIN = 6,            /* rm_sin(a) */
+    RM_MATH_COS = 7,            /* rm_cos(a) */
+    RM_MATH_SINCOS = 8,         /* rm_sincos<false>(a): sin / cos */
+    RM_MATH_SINCOS_U = 9,       /* rm_sincos<true>(a): sin / cos */
+    RM_MATH_ACOS = 10,          /* rm_acos<false>(a) */
+    RM_MATH_ACOS_U = 11,        /* rm_acos<true>(a) */
+    RM_MATH_ATAN2 = 12,         /* rm_atan2<false>(a, b) */
+    RM_MATH_ATAN2_U = 13,       /* rm_atan2<true>(a, b) */
+    RM_MATH_LOG = 14,           /* rm_log(a) */
+    RM_MATH_COUNT = 15
+};
+/* Development / tests: evaluates one RmMathFn routine on the device, one element per live lane, in the render kernels'
+ * 256-thread workgroups with the libm tables in LDS.  a, b, out0, out1 are host arrays of n doubles (b is read only by
+ * POW and ATAN2*, out1 written only by POW2, POW_HALF_GUARD and SINCOS*; either may be NULL otherwise).  lane_mask selects
+ * the live lanes of every wavefront (bit l = lane l): element e goes to the (e mod p)-th live lane of wavefront e / p,
+ * p = popcount(lane_mask); the other lanes take part in loading the tables and leave before the routine runs.
+ * Synchronous.  RM_E_BAD_ARG for fn out of range, lane_mask == 0 or a NULL buffer the routine needs. */
+int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1);
+
 /* Store-path probe: writes the 9 B/ray outputs with the render kernel's flush code and no
  * marching, to measure the isolated HBM write bandwidth of the path. */
 int rm_bench_store_path(int32_t width, int32_t rows, void* d_depth, void* d_iters, void* d_hit,

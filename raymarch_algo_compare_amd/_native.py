@@ -32,9 +32,14 @@ EXPORTS = [
     "rm_bench_store_path", "rm_render_batch", "rm_render_batch_outputs", "rm_set_pass_timing", "rm_get_pass_ms", "rm_last_queue_marks", "rm_long_ray_marks", "rm_set_queue_capacity",
     "rm_comm_unique_id", "rm_comm_init", "rm_comm_destroy", "rm_shard_rows", "rm_gather_frame", "rm_assemble_frame", "rm_gather_frame_root",
     "rm_runtime_info", "rm_stream_create", "rm_stream_synchronize", "rm_stream_destroy", "rm_debug_poison_queues",
-    "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy",
+    "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy", "rm_debug_math_eval",
 ]
 RM_SCENE_PROGRAM_BASE = 1024
+# RmMathFn (include/rm_hip.h): the device math routines rm_debug_math_eval evaluates
+MATH_FNS = {"POW": 0, "POW2": 1, "POW_HALF_DENSE": 2, "POW_HALF_SPARSE": 3, "POW_HALF_GUARD": 4, "SQRT": 5, "SIN": 6,
+            "COS": 7, "SINCOS": 8, "SINCOS_U": 9, "ACOS": 10, "ACOS_U": 11, "ATAN2": 12, "ATAN2_U": 13, "LOG": 14}
+MATH_TWO_ARGS = {"POW", "ATAN2", "ATAN2_U"}                          # read b
+MATH_TWO_OUTS = {"POW2", "POW_HALF_GUARD", "SINCOS", "SINCOS_U"}     # write out1
 
 
 class RmError(RuntimeError):
@@ -218,6 +223,7 @@ def load() -> ctypes.CDLL:
         L.rm_debug_set_trace.argtypes = [ctypes.c_int]
         L.rm_debug_get_trace.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), vp, vp, ctypes.c_int64,
                                          ctypes.POINTER(ctypes.c_uint32)]
+        L.rm_debug_math_eval.argtypes = [ctypes.c_int32, dp, dp, ctypes.c_size_t, ctypes.c_uint64, dp, dp]
         for name in EXPORTS:
             if name not in ("rm_shutdown", "rm_last_error", "rm_stats_device_bytes", "rm_default_strategy_params"):
                 getattr(L, name).restype = ctypes.c_int
@@ -419,3 +425,22 @@ def march_rays(scene_id, strategy_id, origins, dirs, max_iterations=512, hit_thr
     check(fn(int(scene_id), int(strategy_id), ctypes.byref(cfg), origins.ctypes.data_as(dp),
              dirs.ctypes.data_as(dp), n, _ptr(hit), t.ctypes.data_as(dp), _ptr(iters), fs.ctypes.data_as(dp)))
     return hit, t, iters, fs
+
+
+def debug_math_eval(fn, a, b=None, lane_mask=(1 << 64) - 1):
+    """rm_debug_math_eval: the device math routine `fn` (a MATH_FNS name or id) on every element of `a` (and `b`), one
+    element per live lane of `lane_mask`.  Returns (out0, out1); out1 is None for routines with one result."""
+    L = init()
+    name = fn if isinstance(fn, str) else {v: k for k, v in MATH_FNS.items()}.get(int(fn))
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+        if len(b) != len(a):
+            raise ValueError("a and b differ in length")
+    out0 = np.empty_like(a)
+    out1 = np.empty_like(a) if name in MATH_TWO_OUTS else None
+    dp = ctypes.POINTER(ctypes.c_double)
+    ptr = lambda x: None if x is None else x.ctypes.data_as(dp)      # noqa: E731
+    check(L.rm_debug_math_eval(MATH_FNS[name] if name in MATH_FNS else int(fn), ptr(a), ptr(b), len(a),
+                               int(lane_mask), ptr(out0), ptr(out1)))
+    return out0, out1

@@ -39,6 +39,9 @@ const SceneLaunchers* scene_launchers_program() __attribute__((weak));
 #else
 const SceneLaunchers* scene_launchers_program();
 #endif
+// rm_math_check.hip: the device math routines one by one (rm_debug_math_eval)
+hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1,
+                             hipStream_t s);
 static const SceneLaunchers* scene(int id)
 {
     switch (id) {
@@ -1777,6 +1780,31 @@ int rm_debug_poison_queues(uint32_t word_offset, uint32_t* next_generation)
     }
     HIP_TRY(hipDeviceSynchronize());
     if (next_generation) *next_generation = next;
+    return RM_OK;
+}
+
+int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1)
+{
+    int rc = check_ready();
+    if (rc) return rc;
+    if (fn < 0 || fn >= RM_MATH_COUNT) return fail(RM_E_BAD_ARG, "fn %d out of range [0, %d)", (int)fn, (int)RM_MATH_COUNT);
+    if (lane_mask == 0) return fail(RM_E_BAD_ARG, "lane_mask is 0: no live lane");
+    const bool two_in = fn == RM_MATH_POW || fn == RM_MATH_ATAN2 || fn == RM_MATH_ATAN2_U;
+    const bool two_out = fn == RM_MATH_POW2 || fn == RM_MATH_POW_HALF_GUARD || fn == RM_MATH_SINCOS || fn == RM_MATH_SINCOS_U;
+    if (n == 0) return RM_OK;
+    if (!a || !out0 || (two_in && !b) || (two_out && !out1)) return fail(RM_E_BAD_ARG, "NULL buffer");
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g.device));
+    if ((rc = g.in0.ensure(n * 8)) || (two_in && (rc = g.in1.ensure(n * 8))) || (rc = g.out0.ensure(n * 8)) ||
+        (two_out && (rc = g.out1.ensure(n * 8))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(g.in0.p, a, n * 8, hipMemcpyHostToDevice, g.stream));
+    if (two_in) HIP_TRY(hipMemcpyAsync(g.in1.p, b, n * 8, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(rm::launch_math_check(fn, (const double*)g.in0.p, two_in ? (const double*)g.in1.p : nullptr, n, lane_mask,
+                                  (double*)g.out0.p, two_out ? (double*)g.out1.p : nullptr, g.stream));
+    HIP_TRY(hipMemcpyAsync(out0, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
+    if (two_out) HIP_TRY(hipMemcpyAsync(out1, g.out1.p, n * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
     return RM_OK;
 }
 

@@ -15,11 +15,14 @@
 // longest ray -- DESIGN.md).
 //
 // STATUS: EXACT for x >= +0 (zero, subnormal, normal, +inf), NaN, and y > 0 with
-// 2^-65 <= y < 2^63 whose result neither overflows nor is subnormal -- every call site of
+// 2^-65 <= y < 2^63 and |y log x| < 512 (results 2^-738 .. 2^738) -- every call site of
 // the path: `** 0.5` (vec3.py:46-47, primitives.py:24-32,49-50), `** 2` (primitives.py:26),
 // `r ** 7.0`, `r ** 8.0` (catalog.py:280,283).  Not claimed: negative x (NaN is returned;
 // CPython returns a complex number or raises), results below 2^-1022 (0 is returned;
-// CPython raises OverflowError for a subnormal result), overflow (+inf).
+// CPython raises OverflowError for a subnormal result), overflow (+inf), and
+// 512 <= |y log x| where the result is normal: glibc's specialcase() rescales there and this
+// does not -- 1 ulp apart on ~0.07 % of arguments, NaN where the result lies within a few
+// ulps of 2^1024 (tests/test_math_cases.py).
 #pragma once
 
 #include "rm_tables.h"

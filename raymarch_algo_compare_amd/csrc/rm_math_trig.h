@@ -13,10 +13,12 @@
 // Shape: branch-free (every range/band is evaluated and the result selected) so a wavefront
 // never diverges inside these routines and independent calls interleave -- DESIGN.md section 3.
 //
-// STATUS: rm_sin / rm_cos / rm_sincos EXACT for |x| < 105414350 (the path needs |x| <= 8*pi for
-// Mandelbulb, <= ~320 for Gyroid), NaN for larger or non-finite arguments (unclaimed: glibc uses
-// __branred there); rm_log EXACT for positive finite x (normal or subnormal).  Verified against
-// libm by tests/test_math_exact.py.
+// STATUS: rm_sin / rm_cos / rm_sincos EXACT for |x| < 0x1.921fbp+26 = 105414336 (high word
+// below 0x419921fb, s_sin.c's own cut, which its comment rounds to 105414350; the path needs
+// |x| <= 8*pi for Mandelbulb, <= ~320 for Gyroid), NaN for larger or non-finite arguments
+// (unclaimed: glibc uses __branred there); rm_log EXACT for positive finite x (normal or
+// subnormal).  Verified against libm by tests/test_math_exact.py, on the device by
+// tests/test_gpu_math_exact.py.
 #pragma once
 
 namespace rm {

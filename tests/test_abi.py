@@ -6,6 +6,7 @@ import re
 import subprocess
 import tempfile
 
+import numpy as np
 import pytest
 
 from conftest import ROOT, gpu_count
@@ -72,6 +73,10 @@ def test_no_cpu_fallback_without_device():
     d = _native.make_desc(0, 0, [0.0] * 14, 8, 8)
     assert lib.rm_render(ctypes.byref(d), None, None, None, None, None, None, None, None) == -4
     assert b"rm_init" in lib.rm_last_error()
+    x = np.ones(4)
+    dp = ctypes.POINTER(ctypes.c_double)
+    assert lib.rm_debug_math_eval(_native.MATH_FNS["LOG"], x.ctypes.data_as(dp), None, 4, (1 << 64) - 1,
+                                  x.ctypes.data_as(dp), None) == -4
     with pytest.raises(_native.RmError):
         _native.init(0)
     from raymarch_algo_compare_amd import run_once
