@@ -19,6 +19,7 @@
 
 #include "../../include/rm_hip.h"
 #include "rm_kernels.h"
+#include "rm_launch_plan.h"
 #include "rm_pipeline.h"
 #include "rm_scene_program.h"
 
@@ -319,11 +320,29 @@ rm::MarchCfg to_cfg(const RmMarchConfig& m)
     return c;
 }
 
-// Fill kernel arguments + choose the persistent grid.
-int make_args(const RmFrameDesc* d, float* depth, int32_t* iters, uint8_t* hit, double* traw, double* fs,
-              long long* bvar, unsigned long long* stats, rm::KernelArgs* a, int* tile_h, int* grid)
+// The launch plan of `d` (rm_launch_plan.h) with this device's and this scene's facts.
+rm::LaunchPlan plan_for(const RmFrameDesc* d, int batch_frames = 0, const RmMarchConfig* configs = nullptr)
 {
-    const int th = d->tile_rows ? d->tile_rows : 4;
+    const rm::SceneLaunchers* const sc = launchers(d->scene_id);
+    const int strategy = d->strategy_id;
+    rm::DeviceFacts f;
+    f.cus = g.prop.multiProcessorCount;
+    f.has_teams = sc->has_teams;
+    f.has_resume_team = sc->resume_team != nullptr;
+    f.entry_bytes = sc->entry_bytes(strategy);
+    f.per_cu = [sc, strategy](rm::OccKernel k, int tile_h, int interleave, int batch) {
+        int n = 0;
+        const hipError_t e = k == rm::OccKernel::pipeline ? sc->occupancy_pipeline(strategy, interleave, batch, &n)
+                                                          : sc->occupancy(strategy, tile_h, interleave, batch, &n);
+        return e == hipSuccess ? n : 0;
+    };
+    return rm::plan_launch(*d, f, batch_frames, configs);
+}
+
+// Kernel arguments of one frame of `d` (a batch sets frames / nframes / full / evals itself): pointers and plan fields.
+int make_args(const RmFrameDesc* d, const rm::LaunchPlan& p, float* depth, int32_t* iters, uint8_t* hit, double* traw, double* fs,
+              long long* bvar, unsigned long long* stats, rm::KernelArgs* a)
+{
     memset(a, 0, sizeof *a);
     if (int rc = scene_data(d->scene_id, &a->scene_data)) return rc;
     for (int i = 0; i < 14; ++i) a->single.cam.v[i] = d->cam[i];
@@ -332,44 +351,43 @@ int make_args(const RmFrameDesc* d, float* depth, int32_t* iters, uint8_t* hit, 
     a->nframes = 1;
     a->full = d->march.full ? 1 : 0;
     a->width = d->width; a->height = d->height; a->row0 = d->row0; a->rows = d->rows;
-    a->tiles_x = (d->width + rm::kTileW - 1) / rm::kTileW;
-    a->tiles_y = (d->rows + th - 1) / th;
+    a->tiles_x = p.tiles_x;
+    a->tiles_y = p.tiles_y;
     a->tiles_per_frame = a->tiles_x * a->tiles_y;
-    a->tile_h = th;
-    // refill batching: ray set-up (~250 instructions) is amortised over the idle lanes it serves.  8 idle lanes is the
-    // default (Pillar Forest 1.93 -> 1.69 ms against the 24 used earlier); the scenes whose rays are short -- set-up is a
-    // larger share of a ray -- measured better at 16 under the centre-out order (Cube 0.182 -> 0.174 ms, Cylinder
-    // 0.366 -> 0.346, Hollow Cube 0.250 -> 0.244, Box Lattice 0.377 -> 0.370, Sphere 0.353 -> 0.345, Metaballs
-    // 1.52 -> 1.49, Thin Torus 0.666 -> 0.655), the others not (Menger 0.675 -> 0.702, Pillar Forest 1.70 -> 1.74).
-    int refill_default = 8;
-    switch (d->scene_id) { case 0: case 2: case 3: case 4: case 6: case 18: case 19: refill_default = 16; break; default: break; }
-    a->refill_min = (d->refill_min > 0 && d->refill_min <= 64) ? d->refill_min : refill_default;
+    a->tile_h = p.tile_h;
+    a->refill_min = p.refill_min;
     a->hist_bins = rm::kHistBins;
-    // one trip per turn pays where the trip count varies (Mandelbulb); the one-trip union scenes run whole evaluations
-    a->interleave = d->eval_mode == 2 || (d->eval_mode == 0 && d->scene_id == 10);
+    a->interleave = p.interleave;
     a->age_prio = d->age_priority > 0 ? d->age_priority : 0;
     if (d->band_rows > 0 && d->band_stride > 1) {
         a->band_rows = d->band_rows; a->band_stride = d->band_stride; a->band_offset = d->band_offset;
     }
     a->depth = depth; a->iters = iters; a->hit = hit; a->t_raw = traw; a->final_sdf = fs;
     a->block_var = bvar; a->stats = stats;
-    *tile_h = th;
-    // persistent grid of 4-wave workgroups; every wave pulls tiles on its own
-    const long long ntiles = (long long)a->tiles_x * a->tiles_y;
-    const long long max_wgs = (ntiles + rm::kWavesPerWG - 1) / rm::kWavesPerWG;
-    long long wgs;
-    if (d->grid_waves > 0) {
-        wgs = (d->grid_waves + rm::kWavesPerWG - 1) / rm::kWavesPerWG;
-    } else {
-        int per_cu = 0;
-        hipError_t e = launchers(d->scene_id)->occupancy(d->strategy_id, th, a->interleave, 0, &per_cu);
-        if (e != hipSuccess || per_cu <= 0) per_cu = 2;
-        // three workgroups per CU at most: the cheap scenes fit four, and measured 10-16 % slower with
-        // four (Sphere 0.50 -> 0.45 ms, Cube 0.40 -> 0.34) while the long-ray scenes are indifferent
-        per_cu = std::min(per_cu, 3);
-        wgs = (long long)g.prop.multiProcessorCount * per_cu;
+    a->fused_reduce = p.fused_reduce;
+    if (p.park[0] > 0) {
+        a->suspend_after = p.park[0];
+        a->suspend_queue = 0;
     }
-    *grid = (int)std::max<long long>(1, std::min<long long>(wgs, max_wgs));
+    if (p.single) {
+        a->team_wgs = p.team_wgs;
+        a->producer_waves = p.producer_waves;
+        a->late_team_first = p.late_team_first;
+        a->early_exit_wgs = p.early_exit_wgs;
+        a->exit_backlog = p.exit_backlog;
+        a->keep_busy = p.keep_busy;
+        a->early_trips = p.early_trips;
+        a->early_handover = p.early_handover;
+        a->suspend_after2 = p.suspend_after2;
+        a->q0_detach = p.q0_detach;
+        a->q0_first = p.q0_first;
+        a->q0_refill_min = p.q0_refill_min;
+        a->q0_retry = p.q0_retry;
+        a->team_retry = p.team_retry;
+        a->team_steal = p.team_steal;
+        a->max_spins = p.max_spins;
+        a->team_prio = p.team_prio;
+    }
     return RM_OK;
 }
 
@@ -454,117 +472,22 @@ __global__ void stats_reduce_kernel(unsigned long long* __restrict__ stats)
 constexpr long long kQueueCapMax = 1ll << 22;   // default entries per suspended-ray queue (a full queue leaves rays in place)
 long long g_queue_cap = kQueueCapMax;           // rm_set_queue_capacity
 
-// Trip budgets of pass 1 / pass 2 (0 = that pass does not park).  desc->suspend_after: 0 = library
-// default, < 0 = off, > 0 = explicit.
-// Which launch structure a frame with long-ray suspension uses (RmFrameDesc.pipeline; 0 leaves it to the library).
-// Measured on Mandelbulb, every strategy, 640x360 ... 5120x2880: the single launch is
-// 4-27 % faster than one launch per pass (1080p Standard 11.0-12.4 -> 9.9 ms, Enhanced 9.7 -> 7.9, Hybrid 6.2 ->
-// 5.0, 3840x2160 21.4 -> 15.7 ms); at 7680x4320 the frame is throughput-bound and wants every workgroup as a
-// producer (52.5 ms without suspension, 59 with the pipeline).  Other scenes keep their measured pass schedules.
-int pipeline_mode(const RmFrameDesc* d, long long rays)
-{
-    if (is_program_id(d->scene_id)) return 1;      // a scene program has no single-launch form
-    if (d->pipeline != 0) return d->pipeline;
-    return (d->scene_id == 10 && rays <= 24000000ll && d->march.max_iterations > 128) ? 2 : 1;
-}
-
-void suspend_levels(const RmFrameDesc* d, long long rays, int mode, int* park)
-{
-    // Default: on for Mandelbulb launches of up to ~16 M rays -- those are bound by the latency of a few
-    // hundred 512-trip rays (1080p: 15.2 -> 11.1 ms at 32 / 128 trips; 3840x2160: 22.8 -> 20.2 and
-    // 5120x2880: 30.3 -> 28.4 ms at 48 / 192); larger launches are throughput-bound (7680x4320: 50 ms
-    // without, 53-58 with), every other scene's SDF is too cheap for the extra passes to pay, and the
-    // strategies whose rays end early or whose loop index restarts (Overstep-Bisect, Skipping-Spheres)
-    // measured no faster or slower with it.
-    const bool strat_ok = d->strategy_id != 6 && d->strategy_id != 7;
-    const bool dflt = d->scene_id == 10 && strat_ok && rays <= 16000000ll && d->march.max_iterations > 128;
-    // Segment and RevAA evaluate the SDF twice per loop trip: half the trip budgets (Segment 19.7 -> 16.4 ms,
-    // RevAA 22.2 -> 19.5 ms at 16 / 64)
-    const int two = (d->strategy_id == 10 || d->strategy_id == 8) ? 2 : 1;
-    const int d0 = (rays <= 3000000ll ? 32 : 48) / two, d1 = (rays <= 3000000ll ? 128 : 192) / two;
-    park[0] = d->suspend_after[0] > 0 ? d->suspend_after[0] : (d->suspend_after[0] == 0 && dflt ? d0 : 0);
-    park[1] = d->suspend_after[1] > 0 ? d->suspend_after[1] : (d->suspend_after[1] == 0 && dflt && d->suspend_after[0] == 0 ? d1 : 0);
-    // Grazing Plane and Thin Planes Stack: a large share of the frame runs hundreds of trips (whole pixel rows
-    // skim the planes; mean 40-68 trips).  Parking at 128 trips turns those rays into dense wavefronts of
-    // their own instead of dragging them along with short rays -- lane compaction: 20-45 % faster for every strategy but
-    // Skipping-Spheres (Grazing Plane / Segment 2.16 -> 1.22 ms, Thin Planes / Hybrid 2.23 -> 1.49).  No other
-    // scene gains (17 scenes x 4 strategies measured).
-    if ((d->scene_id == 1 || d->scene_id == 13) && d->strategy_id != 7 && d->suspend_after[0] == 0 && rays <= 16000000ll &&
-        d->march.max_iterations > 128)
-        park[0] = 128;
-    // Sphere Cloud and Bumpy Sphere (unions of 24 / 31 spheres: a pow per sphere and evaluation).  The long rays are
-    // parked at 16 trips and finished by TEAMS, each wave taking a third of the sphere list: 3.8 -> 3.0 ms and
-    // 6.4 -> 5.0-5.2 ms (Curvature 6.7 -> 5.6, Segment 7.3 -> 5.7).  Not for Adaptive-Hybrid, whose rays end early
-    // (2.33 vs 1.88 ms and 3.23 vs 3.10 without).
-    if ((d->scene_id == 14 || d->scene_id == 15) && strat_ok && d->strategy_id != 9 && d->suspend_after[0] == 0 &&
-        rays <= 16000000ll && d->march.max_iterations > 128)
-        park[0] = 16 / two;
-    // Gyroid (three sincos per evaluation, long skimming rays inside the ball) parked at 24 trips in round 1 (1.88 ->
-    // 1.63 ms in natural tile order).  With the centre-out order its long rays start early anyway: parking measured
-    // 1.63 vs 1.60 ms without (Adaptive-Hybrid 1.17 vs 1.05), so it no longer parks.
-    // Single launch (Mandelbulb): rays are struck from their tile at 16 trips (the tile slot is free again) and handed
-    // to the teams at 48; larger frames, and Segment whose trips evaluate twice, at 32 / 64.  Every strategy gains,
-    // Overstep-Bisect and Skipping-Spheres included (3.56 -> 3.08 ms, 11.3 -> 10.2 ms).
-    if (mode == 2 && d->scene_id == 10 && d->march.max_iterations > 128) {
-        // (with the previous frame's tile costs the long rays start first: 24 / 56 with 7/16 of the grid as teams measured
-        // 7.3-7.5 ms, 32 / 64 7.5-7.6, 16 / 48 8.5)
-        const bool small = rays <= 3000000ll && d->strategy_id != 10 && d->tile_order_mode != 1;
-        const bool ordered = rays <= 3000000ll && d->strategy_id != 10 && d->tile_order_mode == 1;
-        // (a strike at 24 measured the same as 16 over the Mandelbulb's three curated viewpoints x Standard / Enhanced / Adaptive-Hybrid
-        // -- sums 28.98 / 21.30 / 17.00 ms against 28.96 / 21.32 / 16.93, profiles/r03/viewpoint_budgets.jsonl)
-        // (with the early hand-over of near-surface rays the strike is back at 16: those rays leave the producer as soon as they
-        // are struck)
-        if (d->suspend_after[0] == 0) park[0] = small ? 16 : (ordered ? 24 : 32);
-        if (d->suspend_after[1] == 0 && d->suspend_after[0] == 0) park[1] = small ? 48 : (ordered ? 56 : 64);
-    }
-    if (park[0] == 0) park[1] = 0;
-    if (park[1] > 0 && park[1] <= park[0]) park[1] = 0;
-}
-
 void frame_key(const RmFrameDesc* d, int tile_h, long long* k)
 {
     k[0] = d->scene_id; k[1] = d->strategy_id; k[2] = d->width; k[3] = d->height; k[4] = d->row0; k[5] = d->rows;
     k[6] = d->band_rows; k[7] = d->band_stride; k[8] = d->band_offset; k[9] = tile_h;
 }
 
-// The library's tile order (RmFrameDesc.tile_order_mode = 0).  A frame ends with its longest ray, and that ray starts
-// when the order reaches its tile; the registry's cameras look at their object, so handing tiles out from the image
-// centre outwards starts the object -- and its grazing / fractal rays -- first.  Measured at 1920x1080, Standard
-// (natural -> centre-out): Sphere 0.46 -> 0.40 ms, Cube 0.239 -> 0.219, Menger 0.87 -> 0.74, Near Miss 0.66 -> 0.58,
-// Cylinder 0.51 -> 0.39, Hollow Cube 0.35 -> 0.28, Box Lattice 0.52 -> 0.38, Metaballs 1.78 -> 1.47, Mandelbulb single
-// launch 10.5 -> 9.7 (16 of 20 scenes gain, 3-27 %); worse where the long rays are NOT in the middle -- planes and
-// pillars to the horizon: Grazing Plane 0.58 -> 0.70, Thin Planes Stack 0.92 -> 1.05, Pillar Forest 1.95 -> 2.10 --
-// which keep the natural order (Bad Lipschitz Sphere: no difference) -- except that Pillar Forest, whose long rays lie along
-// the horizon line in the middle rows, takes the middle-rows-first order (4): Standard 1.76 -> 1.72, Segment 2.24 -> 2.00
-// (Grazing Plane 0.58 -> 0.63 and Thin Planes Stack 0.90 -> 0.91 do not gain: their horizon is not the middle row / the
-// natural order already reaches it in time).  The permutation is cached
-// per frame shape.  Batches keep the natural order (their tiles run frame-major).
-int default_tile_order(const RmFrameDesc* d, int nframes)
-{
-    if (nframes > 1) return d->scene_id == 10 ? 2 : 3;     // Mandelbulb sweeps: centre-out within every frame
-    // Round 3 held the choice against EVERY curated viewpoint of the reference (viewpoints.py:41-123; 53 cameras at
-    // 1920x1080, Standard, profiles/r03/viewpoint_orders.jsonl): centre-out is within 5 % of the best static order for all
-    // viewpoints of 15 scenes; the plane scenes want the natural order from every camera (centre-out +15...26 %); Pillar
-    // Forest, Thin Torus (ring seen edge-on: -13 %, -8 %, -4 %) and Near Miss (the gap between the spheres: -13 %, -10 %,
-    // -4 %) the middle rows first.  Intermediate ellipses (horizontal weight 1/4, 1/2) were measured too: never the best.
-    // No single static order is within 5 % everywhere (centre-out: 17 of 53 cameras behind, natural 35, middle rows 29).
-    switch (d->scene_id) {
-        case 1: case 13: return 3;
-        case 3: case 5: case 12: return 4;
-        default: return 2;
-    }
-}
-
-int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, hipStream_t s);
+int launch_frame(const RmFrameDesc* d, const rm::LaunchPlan& p, rm::KernelArgs a, hipStream_t s);
 
 // One frame: (optional) longest-first tile order from the previous frame's costs, stats reset, render.
-int launch(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, hipStream_t s)
+int launch(const RmFrameDesc* d, const rm::LaunchPlan& p, const rm::KernelArgs& a, hipStream_t s)
 {
     // The parked-ray queues, tile costs / orders, the control block and the pass events are ONE workspace: frames
     // are serialised on the device.  A frame enqueued on another stream than the previous one first waits for it
     // (callers may still overlap their own copies and other kernels with a frame).
     if (g.frame_ev_valid && g.frame_stream != s) HIP_TRY(hipStreamWaitEvent(s, g.frame_ev, 0));
-    const int rc_frame = launch_frame(d, a, tile_h, grid, s);
+    const int rc_frame = launch_frame(d, p, a, s);
     if (rc_frame) return rc_frame;
     if (!g.frame_ev_valid) {
         HIP_TRY(hipEventCreateWithFlags(&g.frame_ev, hipEventDisableTiming));
@@ -575,46 +498,26 @@ int launch(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, hipStre
     return RM_OK;
 }
 
-int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, hipStream_t s)
+// Performs the plan `p` (rm_launch_plan.h) of one launch: workspace, caches and enqueues in the order it dictates.
+int launch_frame(const RmFrameDesc* d, const rm::LaunchPlan& p, rm::KernelArgs a, hipStream_t s)
 {
     a.raw_outputs = (a.t_raw || a.final_sdf || a.evals) ? 1 : 0;
-    // launch structure and trip budgets first: the single launch of a scene with teams uses one-row tiles
-    const long long rays_total = (long long)a.rows * a.width * a.nframes;
-    int park[2];
-    const int mode = pipeline_mode(d, rays_total);
-    suspend_levels(d, rays_total, mode, park);
-    // One-pass frames fold their statistics in the render kernel itself (frame_reduce_by_last_workgroup) and leave the
-    // buffer zeroed where the next frame needs it: no reduce launch, and -- for the library's own buffer, which nobody
-    // else writes -- no memset either.  A caller's buffer is always cleared (its contents are not ours to trust).
+    // A fused-reduce frame leaves the statistics buffer zeroed where the next frame needs it: no reduce launch, and --
+    // for the library's own buffer, which nobody else writes -- no memset either.  A caller's buffer is always cleared
+    // (its contents are not ours to trust).
     const bool own_stats = a.stats == (unsigned long long*)g.stats.p;
-    a.fused_reduce = (park[0] == 0 && a.nframes == 1 && d->rows > 0) ? 1 : 0;
     if (!(own_stats && g.stats_ready)) HIP_TRY(hipMemsetAsync(a.stats, 0, kStatsBytes, s));
     if (own_stats) g.stats_ready = a.fused_reduce != 0;
     if (d->rows == 0) return RM_OK;
+    if (p.refuse) return fail(RM_E_BAD_ARG, "%s", p.refuse);
     const rm::SceneLaunchers* const sc = launchers(d->scene_id);
-    if (d->tile_rows == 1 && !(park[0] > 0 && mode == 2 && sc->has_teams))
-        return fail(RM_E_BAD_ARG, "tile_rows = 1 exists for the single launch (pipeline = 2 with suspension) of scenes with a team form");
-    if (park[0] > 0 && mode == 2 && sc->has_teams && (d->tile_rows == 1 || (d->tile_rows == 0 && d->tile_order_mode == 1))) {
-        // 64x1 tiles: all 64 pixels of a tile start when the tile is opened.  With 64x4 tiles the last pixels of a
-        // tile wait in its pixel pool for lanes that rays of 16-48 trips hold (~1 ms each).  Default only with the
-        // previous frame's tile costs (tile_order_mode 1: the long rays' tiles are opened first, so their pixels
-        // should not queue inside them -- 1080p 9.6 -> 8.5 ms); with a static order 64x4 tiles measured better
-        // (9.9 against 10.9 ms: the tile order does not know where the long rays are).
-        tile_h = 1;
-        a.tile_h = 1;
-        a.tiles_y = a.rows;
-        a.tiles_per_frame = a.tiles_x * a.tiles_y;
-    }
     const int ntiles = a.tiles_per_frame * a.nframes;
-    // Tile order: 1 = longest-first from the previous frame's costs, 2 = centre-out, 3 = natural, 4 = middle rows first,
-    // 0 = the library's choice
-    int order = d->tile_order_mode;
-    if (order == 0) order = default_tile_order(d, a.nframes);
+    int order = p.tile_order;
     if (order == 1) {
         int rc;
         if ((rc = g.tcost.ensure((size_t)ntiles * 4)) || (rc = g.torder.ensure((size_t)ntiles * 4))) return rc;
         long long key[10];
-        frame_key(d, tile_h, key);
+        frame_key(d, p.tile_h, key);
         if (g.cost_valid && memcmp(key, g.cost_key, sizeof key) == 0) {
             hipLaunchKernelGGL(order_tiles_kernel, dim3(1), dim3(1024), 0, s, (const int32_t*)g.tcost.p,
                                (int32_t*)g.torder.p, ntiles);
@@ -624,12 +527,12 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
         a.tile_cost = (int32_t*)g.tcost.p;      // this frame's costs feed the next frame's order
         memcpy(g.cost_key, key, sizeof key);
         g.cost_valid = true;
-        if (!a.tile_order) order = default_tile_order(d, a.nframes);    // no costs yet: the first frame takes the static order
+        if (!a.tile_order) order = p.static_order;    // no costs yet: the first frame takes the static order
     }
     if (order == 2 || order == 4) {
         // A static permutation of the frame shape, computed once and kept until the shape changes: no extra launch per frame.
         long long key[12];
-        frame_key(d, tile_h, key);
+        frame_key(d, p.tile_h, key);
         key[0] = key[1] = 0;                    // pure geometry: the same permutation for every scene and strategy
         key[10] = a.nframes; key[11] = order;
         int rc2;
@@ -637,7 +540,7 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
         if (!g.corder_valid || memcmp(key, g.corder_key, sizeof key) != 0) {
             if ((rc2 = g.ccost.ensure((size_t)ntiles * 4))) return rc2;
             hipLaunchKernelGGL(center_cost_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, s, (int32_t*)g.ccost.p, a.tiles_x,
-                               a.tiles_y, a.nframes, tile_h, a.width, a.height, a.row0, a.band_rows, a.band_stride, a.band_offset,
+                               a.tiles_y, a.nframes, p.tile_h, a.width, a.height, a.row0, a.band_rows, a.band_stride, a.band_offset,
                                order == 4 ? 1.0f / 16.0f : 1.0f);
             hipLaunchKernelGGL(order_tiles_kernel, dim3(1), dim3(1024), 0, s, (const int32_t*)g.ccost.p, (int32_t*)g.corder.p, ntiles);
             HIP_TRY(hipGetLastError());
@@ -646,15 +549,14 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
         }
         a.tile_order = (const int32_t*)g.corder.p;
     }
-    // long-ray suspension: pass 1 parks rays beyond suspend_after[0] trips, pass 2 restarts them all at
-    // once and parks those beyond suspend_after[1], pass 3 finishes the few that remain
+    // long-ray suspension: the queues of the parked rays
     long long* const block_var = a.block_var;
-    if (park[0] > 0) {
+    if (p.park[0] > 0) {
         const long long total = (long long)a.rows * a.width * a.nframes;
         const long long cap = std::min<long long>(total, g_queue_cap);
-        const int stride = launchers(d->scene_id)->entry_bytes(d->strategy_id);
+        const int stride = p.queue_entry_bytes;
         int rc;
-        for (int q = 0; q < (park[1] > 0 ? 2 : 1); ++q) {
+        for (int q = 0; q < (p.park[1] > 0 ? 2 : 1); ++q) {
             const size_t need = (size_t)cap * (size_t)stride;
             State::QueueKey& key = g.qkey[q];
             if (need > g.queue[q].cap) {
@@ -663,7 +565,7 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
                 HIP_TRY(hipMemsetAsync(g.queue[q].p, 0, need, s));
                 key.used = 0;
             }
-            const int writer = mode == 2 ? 2 : 1;
+            const int writer = p.single ? 2 : 1;
             if (writer == 2 && key.used > 0 && (key.writer != 2 || key.stride != stride)) {
                 // another layout wrote here: stale payload words now sit at this launch's `ready` offsets
                 HIP_TRY(hipMemsetAsync(g.queue[q].p, 0, std::min(key.used, g.queue[q].cap), s));
@@ -676,92 +578,14 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
         }
         a.queue_cap = (int32_t)cap;
         a.queue_stride = stride;
-        a.suspend_after = park[0];
-        a.suspend_queue = 0;
         a.block_var = nullptr;      // parked pixels are missing at flush time: reduced from the finished map below
     }
     const bool pt = g.pass_timing && g.pev_ready;
     g.pass_count = 0;
     g.last_was_pipeline = false;
     if (pt) HIP_TRY(hipEventRecord(g.pev[0], s));
-    if (park[0] > 0 && mode == 2) {
+    if (p.single) {
         // ---- the whole frame in ONE launch (rm_pipeline.h): producers + queue-0 consumers + teams side by side
-        const bool teams = sc->has_teams && park[1] > 0 && d->resume_mode != 1;
-        int per_cu = 0;
-        if (sc->occupancy_pipeline(d->strategy_id, a.interleave, a.frames != nullptr, &per_cu) != hipSuccess || per_cu <= 0) per_cu = 2;
-        per_cu = std::min(per_cu, 3);
-        const long long resident = (long long)g.prop.multiProcessorCount * per_cu;
-        // producers and teams wait for one another (bounded), so the grid never exceeds what is resident at once.
-        // A team workgroup also carries kSharedProducers producer waves when rm::kTeamShare (rm_pipeline.h).
-        const long long team_pw = rm::kTeamShare ? rm::kSharedProducers : 0;      // producer waves of a team workgroup
-        long long team_wgs = 0;
-        if (teams) {
-            // Share of the resident workgroups that run as teams (512 resident at 2 per CU).  Measured after the guarded
-            // square root made a team's trip shorter (Mandelbulb / Standard, ms per frame by team workgroups):
-            //   960x540     128: 8.9   192: 8.4   224: 8.1            1280x720   128: 8.4   192: 8.0   224: 8.1
-            //   1920x1080   128: 9.8   160: 9.4   192: 9.4   224: 10.1  (previous frame's costs: 128: 8.5  192: 7.7  240: 7.3-7.5)
-            //   2560x1440    64: 11.7   96: 10.8  128: 11.3  192: 11.3   3840x2160  64: 19.2   96: 15.1  128: 15.2  192: 17.9
-            //   5120x2880    64: 27.6   96: 24.4  128: 26.2  192: 31.0
-            // Small frames are all tail (the chains of the long rays): more teams; large frames are fresh-pixel
-            // throughput with a short tail: more producers.
-            long long share16 = rays_total <= 1000000ll ? 7 : (rays_total <= 3000000ll ? 6 : 3);      // sixteenths of the grid
-            // (with keep_busy, over the three curated viewpoints: 1280x720 wants 128-160 teams, not 224 -- Enhanced 17.6 -> 15.6 ms in
-            // the sum at 128, Relaxed / Auto-Relaxed / Slope / Curvature 2-5 % at 160, Standard flat; 960x540 and 1920x1080 stay)
-            if (rays_total > 600000ll && rays_total <= 1000000ll) share16 = d->strategy_id == 4 ? 4 : 5;
-            if (d->tile_order_mode == 1 && rays_total <= 3000000ll) share16 = 7;                      // (15/32 measured 2 % better still)
-            if (a.nframes > 1 && rays_total > 3000000ll) share16 = 4;        // sweeps: 64 x 384^2 viewpoints 29.0 ms (96: 31, 192: 34.6)
-            // Strategies whose rays end early hand few rays to the teams: Overstep-Bisect 2.95 / 3.03 / 3.32 ms and
-            // Adaptive-Hybrid 4.67 / 4.69 / 4.71 at 96 / 128 / 192 teams (with the previous frame's costs 2.81 vs 3.46
-            // and 3.79 vs 4.81 at 128 vs 224; Skipping-Spheres 6.6 vs 6.8).  The other eight gain from the larger share
-            // like Standard (Enhanced 7.26 -> 7.1, RevAA 15.1 -> 14.2; ordered: Enhanced 6.3 -> 5.6, RevAA 12.1 -> 10.4).
-            if (d->strategy_id == 6 || d->strategy_id == 9) share16 = d->tile_order_mode == 1 ? 4 : 3;
-            if (d->strategy_id == 7 && d->tile_order_mode == 1) share16 = 4;
-            if (rm::kTeamShare) share16 = 8;
-            team_wgs = d->team_grid > 0 ? d->team_grid : std::max<long long>(1, resident * share16 / 16);
-            team_wgs = std::min<long long>(team_wgs, std::max<long long>(1, rm::kTeamShare ? resident : resident / 2));
-        }
-        // Late teams (rm_pipeline.h): by default a third of the team workgroups are resident from the start and the
-        // others are put behind the resident grid -- their places are held by producers until queue 1 fills.
-        long long late = 0;
-        const bool detach_mode = d->queue_first == 3 || (d->queue_first == 0 && teams);
-        if (teams && detach_mode && !rm::kTeamShare && d->grid_waves == 0) {
-            // measured at 1080p (Mandelbulb / Standard, trace of round 3): with 64 resident + 128 late teams the tile counter
-            // runs out at 3.8 instead of 4.6 ms and the last long ray enters queue 1 a millisecond earlier (2.5 vs 3.5 ms),
-            // but a producer workgroup only leaves when it would open its next tile (every 1-2 ms per wave in the object's
-            // tiles), the late teams arrive at 1.8-2.5 ms and the rays pushed meanwhile wait ~1.3 ms: 9.6 vs 9.8 ms.  Off by
-            // default; the demand for teams jumps from 0 to ~140 workgroups within 0.5 ms.
-            if (d->late_teams > 0) late = d->late_teams;
-        }
-        const long long want_pw = d->grid_waves > 0 ? d->grid_waves : (long long)resident * rm::kPipeWaves;   // producer waves asked for
-        long long pure = (std::min<long long>(want_pw, ntiles) - team_wgs * team_pw + rm::kPipeWaves - 1) / rm::kPipeWaves;
-        pure = std::max<long long>(team_pw > 0 && team_wgs > 0 ? 0 : 1, std::min<long long>(pure, resident - team_wgs));
-        late = std::min<long long>(late, std::max<long long>(0, pure - 1));      // one producer workgroup at least stays to the end
-        const long long pwgs = pure + late;       // grid = static teams + producers + late teams
-        a.team_wgs = (int32_t)team_wgs;
-        a.producer_waves = (int32_t)(team_wgs * team_pw + pure * rm::kPipeWaves);
-        a.late_team_first = (int32_t)(team_wgs + pure);
-        a.early_exit_wgs = (int32_t)late;
-        a.exit_backlog = d->exit_backlog > 0 ? d->exit_backlog : 64;
-        // KEEP BUSY (rm_kernels.h): finished producer workgroups stay until the teams are through -- 1080p Mandelbulb / Standard
-        // 9.4 -> 8.1 ms, Enhanced 7.0 -> 6.2 (burst 16 ... 2048 alike; fp64, fp32 and integer filler alike; s_sleep in the same
-        // place: nothing).  Not with late teams, which need the producers' places.
-        a.keep_busy = (teams && late == 0) ? (d->keep_busy > 0 ? d->keep_busy : (d->keep_busy == 0 ? 256 : 0)) : 0;
-        // EARLY HAND-OVER (rm_pipeline.h): struck near-surface rays go to the teams at once.  Over the Mandelbulb's three curated
-        // viewpoints at 1080p with the strike at 16: Standard 8.19 / 13.19 / 7.84 -> 7.81 / 13.02 / 7.81 ms, Enhanced 6.33 / 9.18 / 6.30
-        // -> 6.34 / 9.06 / 6.38 (sums -2.0 % / -0.1 %; strikes of 8 ... 24 alike, a regular hand-over later than 48 worse)
-        // By strategy (default camera, on / off): Relaxed 7.90 / 8.36, Auto-Relaxed 7.92 / 8.19, Slope 6.67 / 7.10, Curvature 7.65 / 8.12,
-        // Segment 10.6 / 11.9, Safe-Relaxed 7.75 / 8.08; RevAA and Dense-March alike; the three whose rays end early or whose loop
-        // index restarts lose 1-2 % (Overstep-Bisect 3.09 / 3.03, Skipping-Spheres 8.77 / 8.66, Adaptive-Hybrid 4.74 / 4.69): off there.
-        // early_trips: how many of the eight fractal iterations make an evaluation "near-surface".  Six, together with a regular
-        // hand-over at 64 instead of 48 trips, measured Standard 7.75 / 11.81 / 7.96 ms against 7.85 / 12.88 / 7.77 from the three
-        // curated cameras (Auto-Relaxed 7.83 / 11.99 / 7.54 against 8.01 / 12.61 / 7.71; the bench line 266-270 Mrays/s instead of
-        // 261-264) -- but twice as many rays go through the queue: 88.9 MB of HBM traffic per frame instead of 58.2, for 1-2 % from
-        // the default camera and a loss from the angled one.  The default stays 8 of 8; the knob is there.
-        a.early_trips = d->early_trips > 0 ? d->early_trips : 8;
-        const bool eh_default = d->strategy_id != 6 && d->strategy_id != 7 && d->strategy_id != 9;
-        a.early_handover = (teams && detach_mode)
-            ? (d->early_handover > 0 ? d->early_handover : (d->early_handover == 0 && eh_default ? std::max(1, park[0]) : 0)) : 0;
-        a.suspend_after2 = teams ? park[1] : 0;
         {
             int rc2;
             if ((rc2 = g.ctl.ensure(sizeof(unsigned long long) * rm::kCtlWords))) return rc2;
@@ -770,15 +594,6 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
         }
         if (++g.generation == 0) g.generation = 1;
         a.generation = g.generation;
-        // default: with teams, rays below suspend_after[1] never leave their lane (no queue-0 traffic); without
-        // teams queue 0 is the lane-compaction queue, parked rays first
-        a.q0_detach = d->queue_first == 3 || (d->queue_first == 0 && teams);
-        a.q0_first = d->queue_first == 0 ? 1 : (d->queue_first == 1 ? 1 : 0);
-        a.q0_refill_min = d->queue_refill_min > 0 ? d->queue_refill_min : 16;
-        a.q0_retry = d->queue_retry > 0 ? d->queue_retry : 16;
-        a.team_retry = d->team_retry > 0 ? d->team_retry : 8;      // (with keep_busy: 2: 8.29, 4: 8.19, 8: 7.97, 16: 8.12, 32: 8.33 ms; other strategies flat)
-        a.team_steal = d->team_steal == 0 ? 1 : (d->team_steal == 1 ? 1 : 0);
-        a.max_spins = 50000;
         a.marks = (g.pass_timing || g.tracing) ? 1 : 0;      // device-clock marks only when somebody will read them (rm_get_pass_ms)
         if (g.tracing) {
             constexpr size_t kTraceRecords = 1u << 20;
@@ -796,44 +611,39 @@ int launch_frame(const RmFrameDesc* d, rm::KernelArgs a, int tile_h, int grid, h
             a.trace_detach = (uint32_t*)g.trace_detach.p;
             g.trace_pix = npix;
         }
-        a.team_prio = 3;      // 0 / 1 / 3 measured alike (10.0-10.4 ms): what slows a ray next to producers is not the issue slot      // ~50 ms of polling: only reached when part of the grid is not resident
         if (a.tile_cost) HIP_TRY(hipMemsetAsync(a.tile_cost, 0, (size_t)ntiles * 4, s));   // resumed rays may report before the tile flush
-        HIP_TRY(sc->pipeline(d->strategy_id, a, (int)(pwgs + team_wgs), s));
+        HIP_TRY(sc->pipeline(d->strategy_id, a, p.pipeline_grid, s));
         if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
         g.last_was_pipeline = true;
         g.last_stats = a.stats;
     } else {
-    HIP_TRY(sc->render(d->strategy_id, tile_h, a, grid, s));
-    if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
-    }
-    if (park[0] > 0 && mode != 2) {
-        rm::KernelArgs b = a;
-        b.suspend_after = park[1];
-        b.suspend_queue = 1;
-        b.refill_min = 16;
-        // one workgroup per compute unit: measured best for both the dense second pass and the sparse last one
-        const int rgrid = d->resume_grid > 0 ? d->resume_grid : std::min(grid, g.prop.multiProcessorCount);
-        const bool team = launchers(d->scene_id)->resume_team != nullptr && d->resume_mode != 1;
-        // KEEP BUSY (rm_kernels.h): a team pass is followed by as many filler workgroups, which start when its queue is handed out
-        b.team_wgs = rgrid;
-        b.keep_busy = team ? (d->keep_busy > 0 ? d->keep_busy : (d->keep_busy == 0 ? 256 : 0)) : 0;
-        const int tgrid = b.keep_busy > 0 ? 2 * rgrid : rgrid;
-        if (team && (park[1] == 0 || d->resume_mode == 3))
-            HIP_TRY(launchers(d->scene_id)->resume_team(d->strategy_id, 0, b, tgrid, s));
-        else
-            HIP_TRY(launchers(d->scene_id)->resume(d->strategy_id, 0, b, rgrid, s));
+        HIP_TRY(sc->render(d->strategy_id, p.tile_h, a, p.render_grid, s));
         if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
-        if (park[1] > 0) {
+    }
+    if (p.park[0] > 0 && !p.single) {
+        // passes 2 and 3: the parked rays of queue 0, then those parked again in queue 1
+        rm::KernelArgs b = a;
+        b.suspend_after = p.park[1];
+        b.suspend_queue = 1;
+        b.refill_min = p.resume_refill_min;
+        b.team_wgs = p.resume_grid;
+        b.keep_busy = p.pass_keep_busy;
+        if (p.pass_team[0])
+            HIP_TRY(sc->resume_team(d->strategy_id, 0, b, p.team_pass_grid, s));
+        else
+            HIP_TRY(sc->resume(d->strategy_id, 0, b, p.resume_grid, s));
+        if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
+        if (p.park[1] > 0) {
             b.suspend_after = 0;
             b.interleave = 0;       // a sparse pass of very long rays is latency-bound: whole evaluations per turn
-            if (team)
-                HIP_TRY(launchers(d->scene_id)->resume_team(d->strategy_id, 1, b, tgrid, s));
+            if (p.pass_team[1])
+                HIP_TRY(sc->resume_team(d->strategy_id, 1, b, p.team_pass_grid, s));
             else
-                HIP_TRY(launchers(d->scene_id)->resume(d->strategy_id, 1, b, rgrid, s));
+                HIP_TRY(sc->resume(d->strategy_id, 1, b, p.resume_grid, s));
             if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
         }
     }
-    if (park[0] > 0 && block_var) {
+    if (p.park[0] > 0 && block_var) {
         const long long nb = (long long)(a.width >> 3) * (a.rows >> 2) * a.nframes;
         if (nb > 0) {
             hipLaunchKernelGGL(block_var_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, a.iters, a.width,
@@ -888,18 +698,18 @@ int ensure_events()
 }
 
 // Launch warmup + repeats times; each timed launch bracketed by events on the launch stream.
-int timed_launches(const RmFrameDesc* d, const rm::KernelArgs& a, int tile_h, int grid, RmTiming* t)
+int timed_launches(const RmFrameDesc* d, const rm::LaunchPlan& p, const rm::KernelArgs& a, RmTiming* t)
 {
     if (t->repeats < 1 || t->repeats > RM_MAX_TIMED || t->warmup < 0)
         return fail(RM_E_BAD_ARG, "timing: repeats must be 1..%d, warmup >= 0", RM_MAX_TIMED);
     int rc = ensure_events();
     if (rc) return rc;
     for (int i = 0; i < t->warmup; ++i)
-        if ((rc = launch(d, a, tile_h, grid, g.stream))) return rc;
+        if ((rc = launch(d, p, a, g.stream))) return rc;
     for (int i = 0; i < t->repeats; ++i) {
         // events bracket one whole frame: stats reset, optional tile ordering, render kernel
         HIP_TRY(hipEventRecord(g.ev[2 * i], g.stream));
-        if ((rc = launch(d, a, tile_h, grid, g.stream))) return rc;
+        if ((rc = launch(d, p, a, g.stream))) return rc;
         HIP_TRY(hipEventRecord(g.ev[2 * i + 1], g.stream));
     }
     HIP_TRY(hipStreamSynchronize(g.stream));
@@ -1244,17 +1054,17 @@ int rm_render_outputs(const RmFrameDesc* d, const RmOutputs* o, RmStats* stats, 
     if (o->final_sdf && (rc = g.fs.ensure(n * 8 + 16))) return rc;
     if (o->block_var && (rc = g.bvar.ensure(nblk * 8 + 16))) return rc;
     if (o->evals && (rc = g.evals.ensure(n * 4 + 16))) return rc;
+    const rm::LaunchPlan p = plan_for(d);
     rm::KernelArgs a;
-    int tile_h = 0, grid = 0;
-    if ((rc = make_args(d, (float*)g.depth.p, (int32_t*)g.iters.p, (uint8_t*)g.hit.p, o->t_raw ? (double*)g.traw.p : nullptr,
+    if ((rc = make_args(d, p, (float*)g.depth.p, (int32_t*)g.iters.p, (uint8_t*)g.hit.p, o->t_raw ? (double*)g.traw.p : nullptr,
                         o->final_sdf ? (double*)g.fs.p : nullptr, o->block_var ? (long long*)g.bvar.p : nullptr,
-                        (unsigned long long*)g.stats.p, &a, &tile_h, &grid)))
+                        (unsigned long long*)g.stats.p, &a)))
         return rc;
     a.evals = o->evals ? (int32_t*)g.evals.p : nullptr;
     if (timing) {
-        if ((rc = timed_launches(d, a, tile_h, grid, timing))) return rc;
+        if ((rc = timed_launches(d, p, a, timing))) return rc;
     } else {
-        if ((rc = launch(d, a, tile_h, grid, g.stream))) return rc;
+        if ((rc = launch(d, p, a, g.stream))) return rc;
     }
     if (n) {
         HIP_TRY(hipMemcpyAsync(o->depth, g.depth.p, n * 4, hipMemcpyDeviceToHost, g.stream));
@@ -1291,12 +1101,12 @@ int rm_render_device(const RmFrameDesc* d, void* d_depth, void* d_iters, void* d
     std::lock_guard<std::mutex> lk(g_mu);     // the enqueue touches the shared workspace (queues, tile order, pass events)
     HIP_TRY(hipSetDevice(g.device));
     if ((rc = check_stream(stream))) return rc;
+    const rm::LaunchPlan p = plan_for(d);
     rm::KernelArgs a;
-    int tile_h = 0, grid = 0;
-    if ((rc = make_args(d, (float*)d_depth, (int32_t*)d_iters, (uint8_t*)d_hit, nullptr, nullptr, nullptr,
-                        (unsigned long long*)(d_stats ? d_stats : g.stats.p), &a, &tile_h, &grid)))
+    if ((rc = make_args(d, p, (float*)d_depth, (int32_t*)d_iters, (uint8_t*)d_hit, nullptr, nullptr, nullptr,
+                        (unsigned long long*)(d_stats ? d_stats : g.stats.p), &a)))
         return rc;
-    return launch(d, a, tile_h, grid, stream ? (hipStream_t)stream : g.stream);
+    return launch(d, p, a, stream ? (hipStream_t)stream : g.stream);
 }
 
 int rm_read_stats(const void* d_stats, void* stream, RmStats* out)
@@ -1324,12 +1134,12 @@ int rm_bench_device(const RmFrameDesc* d, void* d_depth, void* d_iters, void* d_
     if (!d_depth || !d_iters || !d_hit || !timing) return fail(RM_E_BAD_ARG, "device outputs and timing are required");
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g.device));
+    const rm::LaunchPlan p = plan_for(d);
     rm::KernelArgs a;
-    int tile_h = 0, grid = 0;
-    if ((rc = make_args(d, (float*)d_depth, (int32_t*)d_iters, (uint8_t*)d_hit, nullptr, nullptr, nullptr,
-                        (unsigned long long*)g.stats.p, &a, &tile_h, &grid)))
+    if ((rc = make_args(d, p, (float*)d_depth, (int32_t*)d_iters, (uint8_t*)d_hit, nullptr, nullptr, nullptr,
+                        (unsigned long long*)g.stats.p, &a)))
         return rc;
-    if ((rc = timed_launches(d, a, tile_h, grid, timing))) return rc;
+    if ((rc = timed_launches(d, p, a, timing))) return rc;
     if (stats) {
         unsigned long long w[rm::kStatsWords];
         HIP_TRY(hipMemcpy(w, g.stats.p, kStatsBlockBytes, hipMemcpyDeviceToHost));
@@ -1374,32 +1184,19 @@ int rm_render_batch_outputs(const RmFrameDesc* shape, int32_t nframes, const dou
         fp[f].cfg = to_cfg(configs ? configs[f] : shape->march);
     }
     HIP_TRY(hipMemcpyAsync(g.bstats.p, fp.data(), sizeof(rm::FrameParams) * (size_t)nframes, hipMemcpyHostToDevice, g.stream));
-    rm::KernelArgs a;
-    int tile_h = 0, grid = 0;
+    const rm::LaunchPlan p = plan_for(shape, nframes, configs);
     RmFrameDesc d = *shape;
-    if (configs) {
-        // the launch-wide scheduling policy (long-ray suspension) looks at the largest budget of the batch
-        d.march = configs[0];
-        for (int f = 1; f < nframes; ++f)
-            if (configs[f].max_iterations > d.march.max_iterations) d.march = configs[f];
-    }
-    if ((rc = make_args(&d, (float*)g.depth.p, (int32_t*)g.iters.p, (uint8_t*)g.hit.p, nullptr, nullptr, nullptr,
-                        (unsigned long long*)g.stats.p, &a, &tile_h, &grid)))
+    if (p.march_frame >= 0) d.march = configs[p.march_frame];      // (KernelArgs.single: the configuration the plan looked at)
+    rm::KernelArgs a;
+    if ((rc = make_args(&d, p, (float*)g.depth.p, (int32_t*)g.iters.p, (uint8_t*)g.hit.p, nullptr, nullptr, nullptr,
+                        (unsigned long long*)g.stats.p, &a)))
         return rc;
     a.frames = (const rm::FrameParams*)g.bstats.p;
     a.nframes = nframes;
     a.full = full;
     a.evals = evals ? (int32_t*)g.evals.p : nullptr;
-    if (d.grid_waves <= 0) {      // the batch is one big launch: size the persistent grid for all its tiles
-        const long long ntiles = (long long)a.tiles_per_frame * nframes;
-        int per_cu = 0;
-        if (launchers(d.scene_id)->occupancy(d.strategy_id, tile_h, a.interleave, 1, &per_cu) != hipSuccess || per_cu <= 0) per_cu = 2;
-        per_cu = std::min(per_cu, 3);
-        grid = (int)std::max<long long>(1, std::min<long long>((long long)g.prop.multiProcessorCount * per_cu,
-                                                                (ntiles + rm::kWavesPerWG - 1) / rm::kWavesPerWG));
-    }
     HIP_TRY(hipEventRecord(g.ev[0], g.stream));
-    if ((rc = launch(&d, a, tile_h, grid, g.stream))) return rc;
+    if ((rc = launch(&d, p, a, g.stream))) return rc;
     HIP_TRY(hipEventRecord(g.ev[1], g.stream));
     HIP_TRY(hipMemcpyAsync(depth, g.depth.p, total * 4, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipMemcpyAsync(iters, g.iters.p, total * 4, hipMemcpyDeviceToHost, g.stream));

@@ -42,11 +42,11 @@
 
 #include "rm_camera.h"
 #include "rm_scenes.h"
+#include "rm_shape.h"
 #include "rm_strategies.h"
 
 namespace rm {
 
-constexpr int kTileW = 64;          // one tile row == one wavefront-wide store
 constexpr int kHistBins = 544;      // iterations <= max_iterations + 9 (Segment 521, RevAA 520) for 512
 constexpr int kStatsHead = 24;
 constexpr int kStatsWords = kStatsHead + kHistBins;  // u64 words, layout below
@@ -198,8 +198,6 @@ __device__ __forceinline__ void store_raw(const KernelArgs& a, uint32_t gi, cons
     if (a.evals) a.evals[gi] = nev;
 #endif
 }
-
-constexpr int kWavesPerWG = 4;         // 256-thread workgroups: four waves share one LDS copy of the libm tables
 
 // KEEP BUSY (RmFrameDesc.keep_busy, include/rm_hip.h).  This chip runs the same instruction stream at two speeds: the full
 // one while most compute units execute vector instructions, a 15-60 % slower one when few wavefronts are live -- the state

@@ -239,23 +239,7 @@ __device__ __forceinline__ void element_pixel(const KernelArgs& a, uint32_t gi, 
                          : a.row0 + y;
 }
 
-// Workgroup shape of the pipeline kernel (1080p Mandelbulb / Standard figures):
-//  kPipeWaves 4, kTeamShare false   256-thread workgroups, two per compute unit: a team workgroup (three waves, the
-//        fourth exits) shares its CU -- and every one of its SIMDs -- with a producer workgroup: 9.6-10.0 ms.
-//  kPipeWaves 8, kTeamsPerWG 1 | 2, kTeamShare false   512-thread workgroups, one per CU, of which `team_grid` carry
-//        one or two teams and nothing else: chains at the speed of an idle CU (13 us per evaluation against 17-20
-//        next to producers), but 48-96 such CUs cannot absorb the rays that cross the threshold: 11.1-12.0 ms.
-//  kPipeWaves 8, kTeamShare true    512-thread workgroups, one per CU; a team workgroup is waves {0,1,2} = the team,
-//        wave 4 exits and waves {3,5,6,7} are producers.  Waves i and i + 4 of a workgroup share a SIMD, so the team's
-//        critical wave (part 0: length -> divide -> acos -> sincos, the longest dependent chain of a trip) has its
-//        SIMD to itself while the compute unit still renders tiles with four waves: 10.2-10.4 ms -- no better, so
-//        what holds the longest rays back next to producers is not the issue slot they share.  The marks
-//        (rm_get_pass_ms) say what is: when the producers are done the longest ray still has > 400 of its 464 team
-//        evaluations ahead -- it sat in queue 1 behind the burst of rays that cross the threshold while the object's
-//        tiles are rendered (90 000 at 48 trips, of which 133 run to 512 and nothing tells them apart).
-// The first shape is built: it is the simplest and measured best.
-constexpr int kPipeWaves = 4;
-constexpr bool kTeamShare = false;
+// Workgroup shape of the pipeline kernel: kPipeWaves (rm_shape.h, with the rejected shapes and their figures).
 
 // Role-specific LDS of the pipeline kernel (one allocation: a workgroup has exactly one role).
 template <int TILE_PIX>
@@ -263,42 +247,18 @@ struct PipeProducerLds {
     float depth[kPipeWaves][kSlots][TILE_PIX];
     uint32_t ih[kPipeWaves][kSlots][TILE_PIX];
 };
-// With kTeamsPerWG = 2 (512-thread workgroups only) a team workgroup carries two teams (waves {0,1,2} and {3,5,6};
-// waves 4 and 7 exit): with the hardware's cyclic wave -> SIMD placement each team's critical wave (part 0: length
-// -> divide -> acos -> sincos) is then alone on its SIMD.  Two teams are independent of one another, so they cannot
-// use s_barrier (it spans the workgroup): a team then synchronises through an arrival counter in its own LDS block.
-constexpr int kTeamsPerWG = 1;
-static_assert(kTeamsPerWG == 1 || kPipeWaves == 8, "two teams need a 512-thread workgroup");
-static_assert(!kTeamShare || (kPipeWaves == 8 && kTeamsPerWG == 1), "a shared team workgroup is 3 team + 1 idle + 4 producer waves");
-// producer waves of a team workgroup when it is shared, and their rank among them
-constexpr int kSharedProducers = 4;
+// The team of a team workgroup: its exchange, histogram and mailbox.  The team is alone in its workgroup (the fourth
+// wave exits), so the hardware barrier -- it counts live waves only -- synchronises its three waves.
 struct PipeTeamLds {
     TeamXch xch;
     unsigned int hist[kHistBins];
-    unsigned int bar;                     // arrivals of this team's waves, monotonic
     unsigned int base, count, queue, done;
     unsigned int ok_lo, ok_hi;            // lanes whose popped entry was published in time (part 0 polls for the team)
 };
 
-// Barrier of one team: LDS operations of a wave execute in order, so a wave's exchange writes are in LDS when
-// its arrival is counted; `epoch` is the arrival count this barrier waits for (same value in the team's three waves).
-__device__ __forceinline__ void team_barrier(PipeTeamLds& L, unsigned int& epoch)
-{
-    if constexpr (kTeamsPerWG == 1 && !kTeamShare) {   // the team is alone in its workgroup: the hardware barrier (it counts live waves only)
-        __syncthreads();
-        return;
-    }
-    epoch += (unsigned int)kTeam;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane_id() == 0) __hip_atomic_fetch_add(&L.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while ((int)(__hip_atomic_load(&L.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - epoch) < 0) {}
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// team_trip (rm_kernels.h) with the team's own barrier
+// team_trip (rm_kernels.h) with the exchange in the team's LDS block
 template <class Scene, class PartT>
-__device__ __forceinline__ bool team_trip_lds(typename Scene::Eval& ev, bool go, PartT part, int lane, PipeTeamLds& L, int& turn,
-                                              unsigned int& epoch)
+__device__ __forceinline__ bool team_trip_lds(typename Scene::Eval& ev, bool go, PartT part, int lane, PipeTeamLds& L, int& turn)
 {
     double o0 = 0.0, o1 = 0.0;
     if constexpr (std::is_same<PartT, int>::value) {
@@ -310,7 +270,7 @@ __device__ __forceinline__ bool team_trip_lds(typename Scene::Eval& ev, bool go,
     ++turn;
     buf[2 * (int)part][lane] = o0;
     buf[2 * (int)part + 1][lane] = o1;
-    team_barrier(L, epoch);
+    __syncthreads();
     bool done = true;
     if (go) done = Scene::trip_join(ev, buf[0][lane], buf[1][lane], buf[2][lane], buf[3][lane], buf[4][lane], buf[5][lane]);
     return done;
@@ -361,10 +321,8 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     constexpr int TILE_PIX = kTileW * TILE_H;
     using Entry = QEntry<Strat>;
     using PLds = PipeProducerLds<TILE_PIX>;
-    constexpr size_t kTeamBytes = sizeof(PipeTeamLds) * kTeamsPerWG;
-    // a workgroup has one role (producer staging and team block overlap) unless team workgroups also render tiles
-    constexpr size_t kRoleBytes = kTeamShare ? sizeof(PLds) + kTeamBytes : (sizeof(PLds) > kTeamBytes ? sizeof(PLds) : kTeamBytes);
-    constexpr size_t kTeamOffset = kTeamShare ? sizeof(PLds) : 0;
+    // a workgroup has one role: producer staging and team block overlap
+    constexpr size_t kRoleBytes = sizeof(PLds) > sizeof(PipeTeamLds) ? sizeof(PLds) : sizeof(PipeTeamLds);
     __shared__ __attribute__((aligned(16))) unsigned char s_role[kRoleBytes];
     __shared__ unsigned int s_hist[kHistBins];
     __shared__ unsigned int s_leave;          // an early-exit producer workgroup has decided to leave
@@ -385,18 +343,14 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     const bool late_team = TEAMS && (int)blockIdx.x >= a.late_team_first;
     const bool team_wg = TEAMS && ((int)blockIdx.x < a.team_wgs || late_team);      // workgroup-uniform
     if (late_team && threadIdx.x == 0) __hip_atomic_fetch_add(ctl(a, kCLateStarted), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // wave roles in a team workgroup: 0..2 = part of team 0 (3..5: team 1), -1 = leave, -2 = producer
-    constexpr int kRoleAlone[8] = { 0, 1, 2, kTeamsPerWG > 1 ? 3 : -1, -1, kTeamsPerWG > 1 ? 4 : -1, kTeamsPerWG > 1 ? 5 : -1, -1 };
-    constexpr int kRoleShared[8] = { 0, 1, 2, -2, -1, -2, -2, -2 };
-    constexpr int kProducerRank[8] = { 0, 0, 0, 0, 0, 1, 2, 3 };     // among the producer waves of a shared team workgroup
-    const int wave_role = !team_wg ? -2 : (kTeamShare ? kRoleShared[wave & 7] : kRoleAlone[wave & 7]);
+    // wave roles in a team workgroup: 0..2 = part of the team, -1 = leave, -2 = producer
+    constexpr int kRole[8] = { 0, 1, 2, -1, -1, -1, -1, -1 };
+    const int wave_role = !team_wg ? -2 : kRole[wave & 7];
     const bool team_role = team_wg && wave_role >= 0;
     if (team_wg) {
-        PipeTeamLds* const T = reinterpret_cast<PipeTeamLds*>(s_role + kTeamOffset);
-        for (int t = 0; t < kTeamsPerWG; ++t) {
-            for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) T[t].hist[b] = 0u;
-            if (threadIdx.x == 0) { T[t].bar = 0u; T[t].base = T[t].count = T[t].queue = T[t].done = 0u; T[t].ok_lo = T[t].ok_hi = 0u; }
-        }
+        PipeTeamLds& T = *reinterpret_cast<PipeTeamLds*>(s_role);
+        for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) T.hist[b] = 0u;
+        if (threadIdx.x == 0) { T.base = T.count = T.queue = T.done = 0u; T.ok_lo = T.ok_hi = 0u; }
         __syncthreads();                     // the last workgroup-wide barrier of a team workgroup
     }
 
@@ -404,14 +358,15 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     if (team_wg && wave_role == -1) return;     // the wave that would share a SIMD with a team's critical wave
     if (team_role) {
         // =================================== TEAM ====================================================
-        const int team = wave_role / kTeam;
         // a team carries the frame's critical chains: its waves win the issue arbitration on the SIMDs they share
         if (a.team_prio >= 3) __builtin_amdgcn_s_setprio(3);
         else if (a.team_prio == 2) __builtin_amdgcn_s_setprio(2);
         else if (a.team_prio == 1) __builtin_amdgcn_s_setprio(1);
-        PipeTeamLds& L = reinterpret_cast<PipeTeamLds*>(s_role + kTeamOffset)[team];
+        // (team is 0 and part is wave_role; spelt as the division the code generator was tuned with -- the plain forms
+        // allocate a few more VGPRs)
+        const int team = wave_role / kTeam;
+        PipeTeamLds& L = reinterpret_cast<PipeTeamLds*>(s_role)[team];
         const int part = wave_role % kTeam;
-        unsigned int epoch = 0;               // this team's barrier count (identical in its three waves)
         bool active = false;
         uint32_t my_gi = 0;
         uint32_t my_push = 0;                 // when this ray entered the queue (ticks since launch; tuning marks)
@@ -471,10 +426,10 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
                         L.ok_lo = (unsigned int)okm; L.ok_hi = (unsigned int)(okm >> 32);
                     }
                 }
-                team_barrier(L, epoch);
+                __syncthreads();
                 const unsigned int base = L.base, cnt = L.count, q = L.queue, done = L.done;
                 const unsigned long long okm = ((unsigned long long)L.ok_hi << 32) | (unsigned long long)L.ok_lo;
-                team_barrier(L, epoch);       // the mailbox may be rewritten on the next look
+                __syncthreads();              // the mailbox may be rewritten on the next look
                 if (done) break;
                 if (cnt > 0) {
                     if (part != 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // part 0 acquired in q_wait_ready
@@ -513,7 +468,7 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
             ++since_try;
             bool ready = true;
             if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-            team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip_lds<Scene>(ev, go, P, lane, L, turn, epoch); });
+            team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip_lds<Scene>(ev, go, P, lane, L, turn); });
             const int live = a.trace ? __popcll(__ballot(active)) : 0;
             if (active) {
                 ++nev;
@@ -543,7 +498,7 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
         }
         unsigned long long* const spart = stats_part(a.stats);
         if (part == 0) acc.flush(spart);
-        team_barrier(L, epoch);               // part 0's histogram updates are in LDS
+        __syncthreads();                      // part 0's histogram updates are in LDS
         for (int b = part * 64 + lane; b < kHistBins; b += 64 * kTeam) {
             const unsigned int c = L.hist[b];
             if (c) atomicAdd(&spart[kStatsHead + b], (unsigned long long)c);
@@ -560,8 +515,7 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     const int ntiles = a.tiles_per_frame * a.nframes;
     // this wave's index among the launch's producer waves (its first tile)
     const int team_wgs = TEAMS ? a.team_wgs : 0;
-    const int pwave = (kTeamShare && team_wg) ? (int)blockIdx.x * kSharedProducers + kProducerRank[wave & 7]
-                                              : (kTeamShare ? team_wgs * kSharedProducers : 0) + ((int)blockIdx.x - team_wgs) * kPipeWaves + wave;
+    const int pwave = ((int)blockIdx.x - team_wgs) * kPipeWaves + wave;
     const int park0 = a.suspend_after;                                   // fresh rays -> queue 0
     const int park1 = (TEAMS && a.team_wgs > 0) ? a.suspend_after2 : 0;  // resumed rays -> queue 1 (teams)
     const bool queues = park0 > 0;
@@ -951,12 +905,9 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
         add_after_drain(ctl(a, kCProdExited), 1ull);                           // after this wave's last push
         if (a.marks) atomicMax(&a.stats[kWMarkProd], realtime());
     }
-    __syncthreads();      // (in a shared team workgroup this also waits for the team waves to have left)
+    __syncthreads();
     // the producer waves of this workgroup flush its histogram between them
-    const bool shared_wg = kTeamShare && team_wg;
-    const int fl_rank = shared_wg ? kProducerRank[wave & 7] * 64 + lane : (int)threadIdx.x;
-    const int fl_stride = shared_wg ? kSharedProducers * 64 : (int)blockDim.x;
-    for (int b = fl_rank; b < kHistBins; b += fl_stride) {
+    for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) {
         const unsigned int c = s_hist[b];
         if (c) atomicAdd(&part[kStatsHead + b], (unsigned long long)c);
     }
