@@ -314,6 +314,52 @@ int rm_scene_program_create(const RmSceneOp* ops, int32_t nops, double lipschitz
 /* Frees the program and its device copy; its id is never handed out again.  RM_E_BAD_SCENE for an unknown id. */
 int rm_scene_program_destroy(int32_t scene_id);
 
+/* ---- Interval first-hit oracle (gpu/interval_oracle.py, gpu/interval.py) ----------------------------------------------
+ * A sound first hit by interval root isolation: each step evaluates an interval extension of the scene's SDF over the
+ * box of the ray segment [t, t + h]; lo > 0 proves the segment empty (t += h, h = min(h * growth, h_max); a miss once
+ * t > t_max), otherwise h shrinks by half until h <= tol, and the ray hits at t.  A miss after max_steps steps.  Unlike a
+ * sampling marcher it cannot tunnel through thin features.  Rounding is to nearest, as in the reference: the enclosure
+ * is exact in real arithmetic only.
+ * Scenes: the 14 catalogue scenes that are compositions of primitives.py (ids 0-8, 12, 13, 14, 17, 19: the library holds
+ * their programs) and every live scene program.  Sphere, Grazing Plane, Cube and Thin Torus are the reference's
+ * INTERVAL_SCENES bit for bit.  Any other scene (Mandelbulb, Menger, Gyroid, ...) and a destroyed program: RM_E_BAD_SCENE.
+ * The scene and the configuration are checked before the device: RM_E_BAD_SCENE / RM_E_BAD_ARG come without a GPU, every
+ * call that passes them returns RM_E_NO_DEVICE without one.  Host pointers; synchronous. */
+/* Ceiling of RmIntervalConfig.max_steps: every step is one dependent evaluation of the scene's interval program (2-25 us
+ * on the MI355X for the catalogue scenes), so 10x the reference's 20000 bounds one launch to seconds, not hours. */
+#define RM_INTERVAL_MAX_STEPS 200000
+typedef struct RmIntervalConfig {  /* every field 0 = the reference's constant */
+    double t_max;                  /* 100    DEFAULT_T_MAX */
+    double tol;                    /* 1e-5   DEFAULT_TOL: a hit once a non-empty probe has h <= tol */
+    double h0;                     /* 0.25   _H0: first probe length */
+    double growth;                 /* 1.5    _GROWTH: probe growth across empty space (> 1) */
+    double h_max;                  /* 10     _HMAX: probe ceiling */
+    double normal_eps;             /* 1e-4   _normals_fd's eps */
+    double bound_radius;           /* rm_interval_render's prune (_prune_candidates, origin-centred sphere): 0 = the library's
+                                    * bound for the scene (SCENE_BOUND: Sphere 1.05, Cube 1.7421, Thin Torus 1.65; none for the
+                                    * others), > 0 = this radius, < 0 = no prune */
+    int32_t max_steps;             /* 20000  _MAX_ITERS: steps per ray (at most RM_INTERVAL_MAX_STEPS) */
+    int32_t reserved;              /* 0 */
+} RmIntervalConfig;
+/* Negative or non-finite fields, growth <= 1 after defaults, max_steps < 0 or > RM_INTERVAL_MAX_STEPS, reserved != 0:
+ * RM_E_BAD_ARG. */
+
+/* 1 when scene_id has an interval extension (a restated catalogue id or a live program), else 0.  Host only. */
+int rm_interval_supported(int scene_id);
+/* The interval extension over n boxes: lo, hi are n x 3 corners; out_lo / out_hi receive the enclosure per box. */
+int rm_interval_sdf_eval(int scene_id, const double* lo, const double* hi, size_t n, double* out_lo, double* out_hi);
+/* first_hit over n explicit rays (origins, dirs: n x 3; directions are used as given, first_hit does not normalise).
+ * t: first hit, +inf on a miss.  steps (n int32, optional): steps the ray marched.  normals (n x 3, optional): _normals_fd
+ * at o + t * d on a hit, 0 on a miss.  cfg may be NULL (all defaults); its bound_radius is not used here. */
+int rm_interval_march_rays(int scene_id, const RmIntervalConfig* cfg, const double* origins, const double* dirs,
+                           size_t n, double* t, int32_t* steps, double* normals);
+/* interval_capture over rows [row0, row0 + rows) of the frame desc describes (scene_id, width, height, row0, rows, cam:
+ * the library's camera rays, the ones rm_render marches; every other field is ignored).  Per pixel, row-major from row0:
+ * depth (t on a hit, 0 on a miss), hit (0 / 1), normal (3 doubles, optional), steps (optional; 0 for a pruned ray).
+ * timing (optional): warmup + repeats timed launches as rm_render. */
+int rm_interval_render(const RmFrameDesc* desc, const RmIntervalConfig* cfg, double* depth, uint8_t* hit,
+                       double* normal, int32_t* steps, RmTiming* timing);
+
 /* Same contract, evaluated by wavefront TEAMS (scenes whose SDF is a loop of independent
  * transcendental chains -- Mandelbulb: three waves carry the same 64 rays and each evaluates one
  * chain per trip; see rm_kernels.h).  Identical results; RM_E_BAD_SCENE for scenes without a team form. */

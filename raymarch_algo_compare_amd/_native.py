@@ -33,7 +33,10 @@ EXPORTS = [
     "rm_comm_unique_id", "rm_comm_init", "rm_comm_destroy", "rm_shard_rows", "rm_gather_frame", "rm_assemble_frame", "rm_gather_frame_root",
     "rm_runtime_info", "rm_stream_create", "rm_stream_synchronize", "rm_stream_destroy", "rm_debug_poison_queues",
     "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy", "rm_debug_math_eval",
+    "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
 ]
+RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
+RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
 RM_SCENE_PROGRAM_BASE = 1024
 # RmMathFn (include/rm_hip.h): the device math routines rm_debug_math_eval evaluates
 MATH_FNS = {"POW": 0, "POW2": 1, "POW_HALF_DENSE": 2, "POW_HALF_SPARSE": 3, "POW_HALF_GUARD": 4, "SQRT": 5, "SIN": 6,
@@ -144,6 +147,13 @@ class RmSceneOp(ctypes.Structure):
     _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("f", ctypes.c_double * 8)]
 
 
+class RmIntervalConfig(ctypes.Structure):
+    """The interval oracle's constants (include/rm_hip.h); every field 0 = the reference's value."""
+    _fields_ = [("t_max", ctypes.c_double), ("tol", ctypes.c_double), ("h0", ctypes.c_double), ("growth", ctypes.c_double),
+                ("h_max", ctypes.c_double), ("normal_eps", ctypes.c_double), ("bound_radius", ctypes.c_double),
+                ("max_steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class RmDeviceInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 128), ("arch", ctypes.c_char * 64),
                 ("device_id", ctypes.c_int32), ("compute_units", ctypes.c_int32),
@@ -224,6 +234,11 @@ def load() -> ctypes.CDLL:
         L.rm_debug_get_trace.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), vp, vp, ctypes.c_int64,
                                          ctypes.POINTER(ctypes.c_uint32)]
         L.rm_debug_math_eval.argtypes = [ctypes.c_int32, dp, dp, ctypes.c_size_t, ctypes.c_uint64, dp, dp]
+        L.rm_interval_supported.argtypes = [ctypes.c_int]
+        L.rm_interval_sdf_eval.argtypes = [ctypes.c_int, dp, dp, ctypes.c_size_t, dp, dp]
+        L.rm_interval_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmIntervalConfig), dp, dp, ctypes.c_size_t, dp, vp, vp]
+        L.rm_interval_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmIntervalConfig), vp, vp, vp, vp,
+                                         ctypes.POINTER(RmTiming)]
         for name in EXPORTS:
             if name not in ("rm_shutdown", "rm_last_error", "rm_stats_device_bytes", "rm_default_strategy_params"):
                 getattr(L, name).restype = ctypes.c_int
@@ -444,3 +459,69 @@ def debug_math_eval(fn, a, b=None, lane_mask=(1 << 64) - 1):
     check(L.rm_debug_math_eval(MATH_FNS[name] if name in MATH_FNS else int(fn), ptr(a), ptr(b), len(a),
                                int(lane_mask), ptr(out0), ptr(out1)))
     return out0, out1
+
+
+def interval_config(t_max=0.0, tol=0.0, h0=0.0, growth=0.0, h_max=0.0, normal_eps=0.0, bound_radius=0.0,
+                    max_steps=0) -> RmIntervalConfig:
+    """RmIntervalConfig; 0 = the reference's constant (bound_radius 0: the library's bound for the scene, < 0: no prune)."""
+    c = RmIntervalConfig()
+    c.t_max, c.tol, c.h0, c.growth, c.h_max = float(t_max), float(tol), float(h0), float(growth), float(h_max)
+    c.normal_eps, c.bound_radius, c.max_steps = float(normal_eps), float(bound_radius), int(max_steps)
+    return c
+
+
+def interval_supported(scene_id: int) -> bool:
+    """rm_interval_supported (no GPU needed)."""
+    return load().rm_interval_supported(int(scene_id)) == 1
+
+
+def interval_sdf_eval(scene_id: int, lo, hi):
+    """rm_interval_sdf_eval: the enclosure (lo, hi) of the scene's SDF over each box [lo, hi] (n x 3 corners)."""
+    L = init()
+    lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(-1, 3)
+    if lo.shape != hi.shape:
+        raise ValueError("lo and hi differ in shape")
+    out_lo, out_hi = np.empty(len(lo)), np.empty(len(lo))
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_interval_sdf_eval(int(scene_id), lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), len(lo),
+                                 out_lo.ctypes.data_as(dp), out_hi.ctypes.data_as(dp)))
+    return out_lo, out_hi
+
+
+def interval_march_rays(scene_id: int, origins, dirs, cfg: RmIntervalConfig | None = None, want_normals=True):
+    """rm_interval_march_rays: (t (+inf on a miss), steps, normals or None) of n explicit rays."""
+    L = init()
+    origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    if origins.shape != dirs.shape:
+        raise ValueError("origins and dirs differ in shape")
+    n = len(dirs)
+    t, steps = np.empty(n), np.empty(n, np.int32)
+    normals = np.empty((n, 3)) if want_normals else None
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_interval_march_rays(int(scene_id), ctypes.byref(cfg) if cfg is not None else None, origins.ctypes.data_as(dp),
+                                   dirs.ctypes.data_as(dp), n, t.ctypes.data_as(dp), _ptr(steps), _ptr(normals)))
+    return t, steps, normals
+
+
+def interval_render(scene_id: int, cam14, width: int, height: int, cfg: RmIntervalConfig | None = None, row0=0, rows=None,
+                    warmup=0, repeats=0) -> dict:
+    """rm_interval_render: depth (0 on a miss), hit, normal, steps of rows [row0, row0 + rows); `timing` with repeats > 0."""
+    L = init()
+    d = make_desc(scene_id, 0, cam14, width, height, row0, rows)
+    n = int(width) * int(d.rows)
+    depth, hit = np.empty(n), np.empty(n, np.uint8)
+    normal, steps = np.empty((n, 3)), np.empty(n, np.int32)
+    tm = None
+    if repeats > 0:
+        tm = RmTiming()
+        tm.warmup, tm.repeats = int(warmup), int(repeats)
+    check(L.rm_interval_render(ctypes.byref(d), ctypes.byref(cfg) if cfg is not None else None, _ptr(depth), _ptr(hit),
+                               _ptr(normal), _ptr(steps), ctypes.byref(tm) if tm is not None else None))
+    shape = (int(d.rows), int(width))
+    out = {"depth": depth.reshape(shape), "hit": hit.reshape(shape), "normal": normal.reshape(shape + (3,)),
+           "steps": steps.reshape(shape)}
+    if tm is not None:
+        out["timing"] = timing_dict(tm)
+    return out

@@ -22,6 +22,8 @@
 #include "rm_launch_plan.h"
 #include "rm_pipeline.h"
 #include "rm_scene_program.h"
+#include "rm_interval.h"
+#include "rm_interval_catalogue.h"
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
 static_assert(RM_NUM_SCENES == 20 && RM_NUM_STRATEGIES == 11 && RM_NUM_STRATEGY_KERNELS == 13, "registry size");
@@ -43,6 +45,13 @@ const SceneLaunchers* scene_launchers_program();
 // rm_math_check.hip: the device math routines one by one (rm_debug_math_eval)
 hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1,
                              hipStream_t s);
+// rm_interval.hip: the interval first-hit oracle (rm_interval_*)
+hipError_t launch_interval_sdf(const void* prog, const double* lo, const double* hi, size_t n, double* out_lo, double* out_hi,
+                               hipStream_t s);
+hipError_t launch_interval_march(const void* prog, const IntervalParams& P, const double* origins, const double* dirs, size_t n,
+                                 double* t, int32_t* steps, double* normals, hipStream_t s);
+hipError_t launch_interval_render(const void* prog, const IntervalParams& P, const CameraParams& cam, int width, int height,
+                                  int row0, int rows, double* depth, uint8_t* hit, double* normal, int32_t* steps, hipStream_t s);
 static const SceneLaunchers* scene(int id)
 {
     switch (id) {
@@ -111,6 +120,7 @@ struct State {
     hipEvent_t ev[2 * RM_MAX_TIMED];
     bool events = false;
     Buf bstats;   // rm_render_batch: the device frame table
+    Buf ivprog;   // rm_interval_*: the device image of a catalogue scene's program
     Buf ctl;      // single-launch pipeline: its hot counters, one per 128-byte line
     Buf busy;     // rm_march_rays_team: the counter its filler workgroups watch (its own word: a frame in flight owns `ctl`)
     Buf trace, trace_start, trace_detach;   // development trace of single-launch frames (rm_debug_set_trace)
@@ -920,7 +930,7 @@ void rm_shutdown(void)
     g.tracing = false;
     g_seen_streams.clear();
     for (Buf* b : { &g.trace, &g.trace_start, &g.trace_detach, &g.ccost, &g.corder, &g.ctl, &g.busy, &g.bstats, &g.stats, &g.depth, &g.iters, &g.hit, &g.traw, &g.fs, &g.bvar, &g.evals, &g.in0, &g.in1, &g.out0, &g.out1,
-                    &g.out2, &g.out3, &g.tcost, &g.torder, &g.queue[0], &g.queue[1] })
+                    &g.out2, &g.out3, &g.tcost, &g.torder, &g.queue[0], &g.queue[1], &g.ivprog })
         b->release();
     if (g.frame_ev_valid) (void)hipEventDestroy(g.frame_ev);
     g.frame_ev_valid = false;
@@ -1728,6 +1738,176 @@ int rm_bench_store_path(int32_t width, int32_t rows, void* d_depth, void* d_iter
     HIP_TRY(hipStreamSynchronize(g.stream));
     for (int i = 0; i < t->repeats; ++i) HIP_TRY(hipEventElapsedTime(&t->ms_each[i], g.ev[2 * i], g.ev[2 * i + 1]));
     summarise(t);
+    return RM_OK;
+}
+
+// ---- interval first-hit oracle (rm_interval.h, rm_interval.hip) ----------------------------------------------------
+
+namespace {
+
+// The encoded programs of the restated catalogue scenes (program_encode of rm_interval_catalogue.h, made once).
+const rm::ProgramImage* interval_catalogue_image(int id)
+{
+    static std::once_flag once;
+    static std::unique_ptr<rm::ProgramImage> imgs[RM_NUM_SCENES];
+    std::call_once(once, [] {
+        for (int i = 0; i < RM_NUM_SCENES; ++i) {
+            int32_t n = 0;
+            const RmSceneOp* ops = rm::interval_catalogue_ops(i, &n);
+            if (!ops) continue;
+            std::unique_ptr<rm::ProgramImage> img(new rm::ProgramImage);
+            char why[160];
+            if (rm::program_encode(ops, n, img.get(), why, sizeof why)) imgs[i] = std::move(img);
+        }
+    });
+    return id >= 0 && id < RM_NUM_SCENES ? imgs[id].get() : nullptr;
+}
+
+int interval_check_scene(int id)
+{
+    if (is_program_id(id)) {
+        std::lock_guard<std::mutex> lk(g_prog_mu);
+        if (!g_programs.count(id)) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id);
+        return RM_OK;
+    }
+    if (!interval_catalogue_image(id)) return fail(RM_E_BAD_SCENE, "scene %d has no interval extension", id);
+    return RM_OK;
+}
+
+int interval_params(int id, const RmIntervalConfig* cfg, rm::IntervalParams* P)
+{
+    char why[160];
+    if (!rm::interval_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
+        return fail(RM_E_BAD_ARG, "RmIntervalConfig: %s", why);
+    return RM_OK;
+}
+
+// the device image of scene `id` (under g_mu with the device selected): a program's own copy, or the catalogue
+// scene's image copied into the library's buffer on the stream
+int interval_program(int id, const void** prog)
+{
+    if (is_program_id(id)) return scene_data(id, prog);
+    const rm::ProgramImage* img = interval_catalogue_image(id);
+    int rc = g.ivprog.ensure(sizeof(rm::ProgramImage));
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(g.ivprog.p, img, sizeof(rm::ProgramImage), hipMemcpyHostToDevice, g.stream));
+    *prog = g.ivprog.p;
+    return RM_OK;
+}
+
+}  // namespace
+
+int rm_interval_supported(int scene_id)
+{
+    if (is_program_id(scene_id)) {
+        std::lock_guard<std::mutex> lk(g_prog_mu);
+        return g_programs.count(scene_id) ? 1 : 0;
+    }
+    return interval_catalogue_image(scene_id) ? 1 : 0;
+}
+
+int rm_interval_sdf_eval(int scene_id, const double* lo, const double* hi, size_t n, double* out_lo, double* out_hi)
+{
+    int rc = interval_check_scene(scene_id);
+    if (rc) return rc;
+    if ((rc = check_ready())) return rc;
+    if (n == 0) return RM_OK;
+    if (!lo || !hi || !out_lo || !out_hi) return fail(RM_E_BAD_ARG, "NULL buffer");
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g.device));
+    const void* prog = nullptr;
+    if ((rc = interval_program(scene_id, &prog))) return rc;
+    if ((rc = g.in0.ensure(n * 24)) || (rc = g.in1.ensure(n * 24)) || (rc = g.out0.ensure(n * 8)) || (rc = g.out1.ensure(n * 8)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(g.in0.p, lo, n * 24, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipMemcpyAsync(g.in1.p, hi, n * 24, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(rm::launch_interval_sdf(prog, (const double*)g.in0.p, (const double*)g.in1.p, n, (double*)g.out0.p,
+                                    (double*)g.out1.p, g.stream));
+    HIP_TRY(hipMemcpyAsync(out_lo, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(out_hi, g.out1.p, n * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RM_OK;
+}
+
+int rm_interval_march_rays(int scene_id, const RmIntervalConfig* cfg, const double* origins, const double* dirs, size_t n,
+                           double* t, int32_t* steps, double* normals)
+{
+    int rc = interval_check_scene(scene_id);
+    if (rc) return rc;
+    rm::IntervalParams P;
+    if ((rc = interval_params(scene_id, cfg, &P))) return rc;
+    if ((rc = check_ready())) return rc;
+    if (n == 0) return RM_OK;
+    if (!origins || !dirs || !t) return fail(RM_E_BAD_ARG, "NULL buffer");
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g.device));
+    const void* prog = nullptr;
+    if ((rc = interval_program(scene_id, &prog))) return rc;
+    if ((rc = g.in0.ensure(n * 24)) || (rc = g.in1.ensure(n * 24)) || (rc = g.out0.ensure(n * 8)) ||
+        (steps && (rc = g.out1.ensure(n * 4))) || (normals && (rc = g.out2.ensure(n * 24))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(g.in0.p, origins, n * 24, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipMemcpyAsync(g.in1.p, dirs, n * 24, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(rm::launch_interval_march(prog, P, (const double*)g.in0.p, (const double*)g.in1.p, n, (double*)g.out0.p,
+                                      steps ? (int32_t*)g.out1.p : nullptr, normals ? (double*)g.out2.p : nullptr, g.stream));
+    HIP_TRY(hipMemcpyAsync(t, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
+    if (steps) HIP_TRY(hipMemcpyAsync(steps, g.out1.p, n * 4, hipMemcpyDeviceToHost, g.stream));
+    if (normals) HIP_TRY(hipMemcpyAsync(normals, g.out2.p, n * 24, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RM_OK;
+}
+
+int rm_interval_render(const RmFrameDesc* d, const RmIntervalConfig* cfg, double* depth, uint8_t* hit, double* normal,
+                       int32_t* steps, RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    int rc = interval_check_scene(d->scene_id);
+    if (rc) return rc;
+    rm::IntervalParams P;
+    if ((rc = interval_params(d->scene_id, cfg, &P))) return rc;
+    if (d->width <= 0 || d->height <= 0 || d->row0 < 0 || d->rows < 0 || d->row0 + d->rows > d->height)
+        return fail(RM_E_BAD_DIMS, "bad frame slice: %dx%d rows [%d,%d)", d->width, d->height, d->row0, d->row0 + d->rows);
+    if ((long long)d->width * d->height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "frame too large");
+    if (timing && (timing->repeats < 1 || timing->repeats > RM_MAX_TIMED || timing->warmup < 0))
+        return fail(RM_E_BAD_ARG, "timing: repeats must be 1..%d, warmup >= 0", RM_MAX_TIMED);
+    if ((rc = check_ready())) return rc;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    if (n == 0) return RM_OK;
+    if (!depth || !hit) return fail(RM_E_BAD_ARG, "depth and hit are required");
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g.device));
+    const void* prog = nullptr;
+    if ((rc = interval_program(d->scene_id, &prog))) return rc;
+    if ((rc = g.out0.ensure(n * 8)) || (rc = g.out1.ensure(n)) || (normal && (rc = g.out2.ensure(n * 24))) ||
+        (steps && (rc = g.out3.ensure(n * 4))))
+        return rc;
+    rm::CameraParams cam;
+    for (int i = 0; i < 14; ++i) cam.v[i] = d->cam[i];
+    auto go = [&]() -> hipError_t {
+        return rm::launch_interval_render(prog, P, cam, d->width, d->height, d->row0, d->rows, (double*)g.out0.p,
+                                          (uint8_t*)g.out1.p, normal ? (double*)g.out2.p : nullptr,
+                                          steps ? (int32_t*)g.out3.p : nullptr, g.stream);
+    };
+    if (timing) {
+        if ((rc = ensure_events())) return rc;
+        for (int i = 0; i < timing->warmup; ++i) HIP_TRY(go());
+        for (int i = 0; i < timing->repeats; ++i) {
+            HIP_TRY(hipEventRecord(g.ev[2 * i], g.stream));
+            HIP_TRY(go());
+            HIP_TRY(hipEventRecord(g.ev[2 * i + 1], g.stream));
+        }
+    } else {
+        HIP_TRY(go());
+    }
+    HIP_TRY(hipMemcpyAsync(depth, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(hit, g.out1.p, n, hipMemcpyDeviceToHost, g.stream));
+    if (normal) HIP_TRY(hipMemcpyAsync(normal, g.out2.p, n * 24, hipMemcpyDeviceToHost, g.stream));
+    if (steps) HIP_TRY(hipMemcpyAsync(steps, g.out3.p, n * 4, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    if (timing) {
+        for (int i = 0; i < timing->repeats; ++i) HIP_TRY(hipEventElapsedTime(&timing->ms_each[i], g.ev[2 * i], g.ev[2 * i + 1]));
+        summarise(timing);
+    }
     return RM_OK;
 }
 

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import registry
+from . import interval_oracle, registry, scoring
 from .camera import Camera
 from .collector import HipCollector
 from .config import MarchConfig
@@ -67,6 +67,11 @@ ROW_FIELDS = ["scene", "strategy", "params", "viewpoint", "category", "sweep_axi
               "width", "height", "iters_mean", "iters_median", "iters_p95", "iters_max", "evals_mean", "evals_median", "evals_p95", "evals_max",
               "divergence_proxy", "hit_rate",
               "depth_mae_vs_finest", "hit_flips_vs_finest", "ms_per_frame"]
+# with an oracle (run_sweep(oracle="interval")): each frame against the sound first hit of its viewpoint
+# (interval_oracle.interval_capture, scoring.py); empty cells for a scene without an interval extension
+ORACLE_FIELDS = ["oracle_iou", "oracle_false_hit", "oracle_false_miss", "oracle_depth_mae", "oracle_depth_rmse",
+                 "oracle_depth_p95"]
+ORACLES = ("interval",)
 
 
 def build_levels(mode: str, *, budgets: Sequence[int] = DEFAULT_BUDGETS, epsilons: Sequence[float] = DEFAULT_EPSILONS,
@@ -96,9 +101,11 @@ def finest_index(mode: str, levels) -> int:
     return int(np.argmax(vals)) if mode == "budget" else int(np.argmin(vals))
 
 
-def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, width: int, height: int, grid: bool = False) -> List[Dict]:
+def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, width: int, height: int, grid: bool = False,
+               oracle_frames: Optional[Dict[str, Optional[Dict]]] = None) -> List[Dict]:
     """All viewpoints x parameter combos x levels of one (scene, strategy) in one batched launch -> one row per
-    frame.  `grid` brute-forces the strategy's tunable parameters (reference sweep.py:181,222-223)."""
+    frame.  `grid` brute-forces the strategy's tunable parameters (reference sweep.py:181,222-223).  `oracle_frames`
+    (viewpoint name -> oracle capture, None without one) adds the ORACLE_FIELDS columns."""
     from .runner import GPURunner
     vps = viewpoints_for(scene)
     combos = param_combos(strategy.key) if grid else [{}]
@@ -134,16 +141,43 @@ def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, widt
             "hit_flips_vs_finest": int((st.hit_map != ref.hit_map).sum()),
             "ms_per_frame": float(st.kernel_ms),
         })
+        if oracle_frames is not None:
+            rows[-1].update(oracle_columns({"hit": st.hit_map, "depth": st.depth_map}, oracle_frames.get(vp.name)))
     return rows
+
+
+def oracle_columns(frame: Dict, oracle: Optional[Dict]) -> Dict:
+    """ORACLE_FIELDS of one frame against its oracle capture (scoring.py); None (an empty cell) without one."""
+    if oracle is None:
+        return {k: None for k in ORACLE_FIELDS}
+    h = scoring._hit_metrics(frame["hit"], oracle["hit"])
+    d = scoring._depth_metrics(frame, oracle)
+    return {"oracle_iou": h["iou"], "oracle_false_hit": h["false_hit_rate"], "oracle_false_miss": h["false_miss_rate"],
+            "oracle_depth_mae": d["mae"], "oracle_depth_rmse": d["rmse"], "oracle_depth_p95": d["p95"]}
+
+
+def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float) -> Dict[str, Optional[Dict]]:
+    """The oracle capture of every curated viewpoint of `scene` (None for each when it has no interval extension);
+    `oracle` is one of ORACLES (run_sweep has checked it)."""
+    vps = viewpoints_for(scene)
+    if not interval_oracle.has_interval(scene):
+        return {vp.name: None for vp in vps}
+    return {vp.name: interval_oracle.interval_capture(scene, Camera(vp.position, vp.target, vp.up, 60.0, width, height), tol=tol)
+            for vp in vps}
 
 
 def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optional[Sequence[str]] = None, mode: str = "budget",
               width: int = 384, height: int = 384, budgets: Sequence[int] = DEFAULT_BUDGETS,
               epsilons: Sequence[float] = DEFAULT_EPSILONS, cap: int = 512, hit_threshold: float = 1e-4,
-              out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False) -> List[Dict]:
+              out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False,
+              oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
-    for a .json path) when `out_path` is given."""
+    for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
+    interval oracle's first hit of its viewpoint (ORACLE_FIELDS; one oracle frame per scene and viewpoint, tolerance
+    `oracle_tol`)."""
+    if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
+        raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
     scenes = registry.get_all_scenes() if not scene_names else [_need(registry.get_scene_by_name(n), "scene", n) for n in scene_names]
     strats = ([registry.get_strategy_by_name(k) for k in registry.list_strategies()] if not strategy_names
               else [_need(registry.get_shader_strategy(n) or registry.get_strategy_by_name(n), "strategy", n) for n in strategy_names])
@@ -151,10 +185,11 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     collector = HipCollector(MarchConfig(), device_id=device_id)
     rows: List[Dict] = []
     for scene in scenes:
+        ofr = oracle_frames_for(scene, width, height, oracle, oracle_tol) if oracle is not None else None
         for strat in strats:
             if strat.has_lipschitz:
                 strat.lipschitz = scene.known_lipschitz_bound() or 1.0      # run_once wiring (reference main.py:58-61)
-            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid)
+            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid, ofr)
             rows.extend(cell)
             if verbose:
                 print(f"{scene.name:24s} {strat.short_name:24s} {len(cell):3d} frames  "
@@ -169,8 +204,9 @@ def write_rows(rows: List[Dict], path: str) -> None:
         with open(path, "w", encoding="utf-8") as f:
             json.dump(rows, f, indent=1, ensure_ascii=False)
         return
+    fields = ROW_FIELDS + ORACLE_FIELDS if rows and "oracle_iou" in rows[0] else ROW_FIELDS
     with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=ROW_FIELDS)
+        w = csv.DictWriter(f, fieldnames=fields)
         w.writeheader()
         w.writerows(rows)
 
@@ -194,10 +230,13 @@ def main(argv=None) -> int:
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--out", default="sweep.csv")
     ap.add_argument("--grid", action="store_true", help="also sweep each strategy's tunable parameters (STRATEGY_PARAM_GRID)")
+    ap.add_argument("--oracle", default=None, choices=list(ORACLES),
+                    help="score every frame against a sound first-hit oracle (adds the oracle_* columns)")
+    ap.add_argument("--oracle-tol", type=float, default=interval_oracle.DEFAULT_TOL, help="the oracle's hit tolerance")
     a = ap.parse_args(argv)
     rows = run_sweep([s for s in a.scenes.split(",") if s], [s for s in a.strategies.split(",") if s], a.mode, a.width, a.height,
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
-                     a.out, verbose=True, grid=a.grid)
+                     a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 

@@ -1,0 +1,442 @@
+"""The interval first-hit oracle without a GPU: csrc/rm_interval.h compiled for the host by g++
+(tests/native/interval_check.cpp) against the reference's own results (tests/golden/interval_*.npz, written by
+tools/gen_interval_golden.py), the catalogue table against scene_program.compile_ops, inclusion and degenerate boxes
+against the pointwise interpreter, the host-only behaviour of the C ABI, scoring.py, and the code object of the
+kernels (interval.o)."""
+import ctypes
+import hashlib
+import importlib.util
+import json
+import math
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT, build_native
+
+from raymarch_algo_compare_amd import _native, scoring
+from raymarch_algo_compare_amd import interval_oracle as io
+from raymarch_algo_compare_amd import scene_program as sp
+
+CATALOGUE_IDS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 12, 13, 14, 17, 19]
+dp = ctypes.POINTER(ctypes.c_double)
+
+
+def load_host_lib():
+    """tests/native/interval_check.cpp built by g++, prototypes declared"""
+    L = ctypes.CDLL(build_native("interval_check"))
+    L.rmi_catalogue.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+    L.rmi_eval.argtypes = [ctypes.c_void_p, ctypes.c_int32, dp, dp, ctypes.c_size_t, dp, dp, ctypes.c_char_p, ctypes.c_int]
+    L.rmi_march.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, dp, dp, ctypes.c_size_t, dp, ctypes.c_void_p,
+                            ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
+    L.rmi_render.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double, dp, ctypes.c_int, ctypes.c_int,
+                             ctypes.c_int, ctypes.c_int, dp, ctypes.c_void_p, dp, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
+    L.rmi_scene_bound.restype = ctypes.c_double
+    L.rmi_sizeof_config.restype = ctypes.c_size_t
+    L.rmi_offsetof_config.restype = ctypes.c_size_t
+    return L
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_host_lib()
+
+
+@pytest.fixture(scope="module")
+def prog_lib():
+    L = ctypes.CDLL(build_native("program_check"))
+    L.rmp_eval.argtypes = [ctypes.c_void_p, ctypes.c_int32, dp, ctypes.c_size_t, dp, ctypes.c_char_p, ctypes.c_int]
+    return L
+
+
+def _ops(expr):
+    return sp.to_ctypes(expr)
+
+
+def _cfg(a):
+    """RmIntervalConfig from a fixture's cfg array (t_max, tol, h0, growth, h_max, normal_eps, bound_radius, max_steps)"""
+    c = _native.RmIntervalConfig()
+    c.t_max, c.tol, c.h0, c.growth, c.h_max, c.normal_eps, c.bound_radius = (float(x) for x in a[:7])
+    c.max_steps = int(a[7])
+    return c
+
+
+def host_march(lib, ops, nops, cfg, o, d):
+    o = np.ascontiguousarray(o, np.float64)
+    d = np.ascontiguousarray(d, np.float64)
+    n = len(o)
+    t, steps, nrm = np.empty(n), np.empty(n, np.int32), np.empty((n, 3))
+    why = ctypes.create_string_buffer(256)
+    rc = lib.rmi_march(ops, nops, ctypes.byref(cfg), o.ctypes.data_as(dp), d.ctypes.data_as(dp), n, t.ctypes.data_as(dp),
+                       steps.ctypes.data, nrm.ctypes.data, why, 256)
+    assert rc == 0, why.value
+    return t, steps, nrm
+
+
+def host_render(lib, ops, nops, cfg, scene_bound, cam14, W, H):
+    cam = np.ascontiguousarray(cam14, np.float64)
+    depth, hit, nrm, steps = np.empty(W * H), np.empty(W * H, np.uint8), np.empty((W * H, 3)), np.empty(W * H, np.int32)
+    why = ctypes.create_string_buffer(256)
+    rc = lib.rmi_render(ops, nops, ctypes.byref(cfg), scene_bound, cam.ctypes.data_as(dp), W, H, 0, H, depth.ctypes.data_as(dp),
+                        hit.ctypes.data, nrm.ctypes.data_as(dp), steps.ctypes.data, why, 256)
+    assert rc == 0, why.value
+    return depth, hit, nrm, steps
+
+
+def host_eval(lib, ops, nops, lo, hi):
+    lo = np.ascontiguousarray(lo, np.float64)
+    hi = np.ascontiguousarray(hi, np.float64)
+    n = len(lo)
+    olo, ohi = np.empty(n), np.empty(n)
+    why = ctypes.create_string_buffer(256)
+    rc = lib.rmi_eval(ops, nops, lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), n, olo.ctypes.data_as(dp),
+                      ohi.ctypes.data_as(dp), why, 256)
+    assert rc == 0, why.value
+    return olo, ohi
+
+
+def pointwise(prog_lib, ops, nops, pts):
+    pts = np.ascontiguousarray(pts, np.float64)
+    out = np.empty(len(pts))
+    why = ctypes.create_string_buffer(256)
+    assert prog_lib.rmp_eval(ops, nops, pts.ctypes.data_as(dp), len(pts), out.ctypes.data_as(dp), why, 256) == 0, why.value
+    return out
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+# ---- 1. the reference's fixtures, bit for bit ---------------------------------------------------------------------------
+
+def frame_cases():
+    z = np.load(os.path.join(GOLDEN, "interval_frames.npz"))
+    W, H = (int(x) for x in z["shape"])
+    for key in sorted(k for k in z.files if k.endswith("_cam")):
+        p = key[: -len("cam")]
+        sid = int(p[1:p.index("_")])
+        yield p, sid, W, H, z[p + "cam"], z[p + "cfg"], np.unpackbits(z[p + "hit"])[: W * H].astype(bool), z[p + "t"], \
+            z[p + "n_sha"].tobytes(), z[p + "n_bits"]
+
+
+def check_frame(depth, hit, nrm, want_hit, want_t, n_sha, n_bits, what):
+    assert np.array_equal(hit.astype(bool), want_hit), (what, int((hit.astype(bool) != want_hit).sum()))
+    assert np.array_equal(bits(depth[want_hit]), want_t), what
+    assert np.all(depth[~want_hit] == 0.0), what
+    nh = np.ascontiguousarray(nrm[want_hit])
+    assert np.array_equal(bits(nh[:256]).reshape(-1), n_bits), what
+    assert hashlib.sha256(bits(nh).tobytes()).digest() == n_sha, what
+
+
+@pytest.mark.parametrize("case", [c[0] for c in frame_cases()])
+def test_frames_match_reference(lib, case):
+    for p, sid, W, H, cam, cfg, want_hit, want_t, n_sha, n_bits in frame_cases():
+        if p != case:
+            continue
+        ops, nops = _ops(sp.catalogue_expressions()[sid])
+        depth, hit, nrm, steps = host_render(lib, ops, nops, _cfg(cfg), lib.rmi_scene_bound(sid), cam, W, H)
+        check_frame(depth, hit, nrm, want_hit, want_t, n_sha, n_bits, case)
+        assert steps.max() <= int(cfg[7])
+
+
+def ray_cases():
+    z = np.load(os.path.join(GOLDEN, "interval_rays.npz"))
+    for key in sorted(k for k in z.files if k.endswith("_o")):
+        p = key[:-1]
+        sid = int(p.split("_s")[1].rstrip("_"))
+        yield p, sid, z[p + "o"], z[p + "d"], z[p + "cfg"], z[p + "t"], z[p + "n"]
+
+
+@pytest.mark.parametrize("case", [c[0] for c in ray_cases()])
+def test_rays_match_reference(lib, case):
+    for p, sid, o, d, cfg, want_t, want_n in ray_cases():
+        if p != case:
+            continue
+        ops, nops = _ops(sp.catalogue_expressions()[sid])
+        t, steps, nrm = host_march(lib, ops, nops, _cfg(cfg), o, d)
+        assert np.array_equal(bits(t), want_t), (case, np.nonzero(bits(t) != want_t)[0][:8])
+        assert np.array_equal(bits(nrm), want_n), case
+
+
+def test_reference_unit_rays(lib):
+    """tests/test_interval.py's two rays: the sphere straight on at t = 4, and the thin torus's tube from above"""
+    cfg = _native.RmIntervalConfig()
+    cfg.t_max, cfg.tol = 10.0, 1e-6
+    ops, nops = _ops(sp.catalogue_expressions()[0])
+    t, _, _ = host_march(lib, ops, nops, cfg, [[0.0, 0.0, 5.0]], [[0.0, 0.0, -1.0]])
+    assert abs(t[0] - 4.0) < 1e-5
+    ops, nops = _ops(sp.catalogue_expressions()[3])
+    t, _, _ = host_march(lib, ops, nops, cfg, [[1.5, 3.0, 0.0]], [[0.0, -1.0, 0.0]])
+    assert abs(t[0] - 2.95) < 1e-5
+
+
+# ---- 2. the C catalogue table -----------------------------------------------------------------------------------------
+
+def test_catalogue_table_equals_compile_ops(lib):
+    ex = sp.catalogue_expressions()
+    assert sorted(ex) == CATALOGUE_IDS
+    for sid in range(20):
+        buf = (_native.RmSceneOp * 256)()
+        n = lib.rmi_catalogue(sid, buf, 256)
+        if sid not in ex:
+            assert n == 0, sid
+            continue
+        want = sp.compile_ops(ex[sid])
+        assert n == len(want), sid
+        for i, (op, f) in enumerate(want):
+            assert buf[i].op == op and buf[i].arg == 0, (sid, i)
+            got = [buf[i].f[j] for j in range(8)]
+            full = list(f) + [0.0] * (8 - len(f))
+            assert bits(got).tolist() == bits(full).tolist(), (sid, i, got, full)
+
+
+# ---- 3. / 4. inclusion and degenerate boxes ------------------------------------------------------------------------------
+
+def _programs():
+    ex = sp.catalogue_expressions()
+    out = [(f"catalogue {sid}", ex[sid]) for sid in CATALOGUE_IDS]
+    with open(os.path.join(GOLDEN, "programs_trees.json"), encoding="utf-8") as f:
+        trees = json.load(f)["trees"]
+    out += [(f"tree {i}", sp.expr_from_json(t)) for i, t in enumerate(trees)]
+    return out
+
+
+PROGRAMS = _programs()
+
+
+@pytest.mark.parametrize("idx", range(len(PROGRAMS)), ids=[p[0] for p in PROGRAMS])
+def test_inclusion(lib, prog_lib, idx):
+    """random boxes with edges 1e-6 .. 1 and random points inside: lo - e <= f(p) <= hi + e, e = 1e-12 (1 + |f|)"""
+    name, expr = PROGRAMS[idx]
+    ops, nops = _ops(expr)
+    rng = np.random.default_rng(1000 + idx)
+    nb, ns = 300, 24
+    c = rng.uniform(-3.0, 3.0, size=(nb, 3))
+    edge = 10.0 ** rng.uniform(-6.0, 0.0, size=(nb, 3))
+    lo, hi = c - 0.5 * edge, c + 0.5 * edge
+    blo, bhi = host_eval(lib, ops, nops, lo, hi)
+    assert np.all(blo <= bhi), name
+    u = rng.uniform(0.0, 1.0, size=(nb, ns, 3))
+    pts = np.clip(lo[:, None, :] + u * (hi - lo)[:, None, :], lo[:, None, :], hi[:, None, :])
+    corners = np.stack([np.where(np.array([(k >> a) & 1 for a in range(3)], bool), hi, lo) for k in range(8)], axis=1)
+    pts = np.concatenate([pts, corners], axis=1)
+    f = pointwise(prog_lib, ops, nops, pts.reshape(-1, 3)).reshape(nb, -1)
+    e = 1e-12 * (1.0 + np.abs(f))
+    bad_lo = f < blo[:, None] - e
+    bad_hi = f > bhi[:, None] + e
+    assert not bad_lo.any(), (name, "lower bound violated", np.argwhere(bad_lo)[:4])
+    assert not bad_hi.any(), (name, "upper bound violated", np.argwhere(bad_hi)[:4])
+
+
+# ops whose degenerate value may differ from program_eval ("Interval oracle"): the reference's
+# interval primitives take np.sqrt where the pointwise primitives take `** 0.5`
+DIFFERING_OPS = {"sd_sphere", "sd_box", "sd_torus"}
+
+
+def _uses(expr, names):
+    return expr.op in names or any(_uses(c, names) for c in expr.children)
+
+
+@pytest.mark.parametrize("idx", range(len(PROGRAMS)), ids=[p[0] for p in PROGRAMS])
+def test_degenerate_boxes(lib, prog_lib, idx):
+    name, expr = PROGRAMS[idx]
+    ops, nops = _ops(expr)
+    rng = np.random.default_rng(2000 + idx)
+    p = rng.uniform(-3.0, 3.0, size=(2000, 3))
+    lo, hi = host_eval(lib, ops, nops, p, p)
+    f = pointwise(prog_lib, ops, nops, p)
+    assert np.array_equal(lo, hi, equal_nan=True), name
+    assert np.all(np.abs(lo - f) <= 1e-12 * (1.0 + np.abs(f))), name
+    if not _uses(expr, DIFFERING_OPS):
+        assert np.array_equal(lo, f), (name, np.nonzero(lo != f)[0][:8])
+
+
+# ---- 5. the C ABI without a device ---------------------------------------------------------------------------------------
+
+def test_supported():
+    L = _native.load()
+    for sid in range(20):
+        assert L.rm_interval_supported(sid) == (1 if sid in CATALOGUE_IDS else 0), sid
+    for sid in (-1, 20, 1023, 999999):
+        assert L.rm_interval_supported(sid) == 0
+    ops, nops = sp.to_ctypes(sp.op_union(sp.sd_sphere(0.5), sp.sd_box((0.2, 0.3, 0.4))))
+    pid = _native.scene_program_create(ops, nops)
+    assert L.rm_interval_supported(pid) == 1
+    _native.scene_program_destroy(pid)
+    assert L.rm_interval_supported(pid) == 0
+    assert [io.has_interval(s) for s in ("Sphere", "Thin Torus", "Mandelbulb", "Menger Sponge", 17, 9)] == \
+        [True, True, False, False, True, False]
+
+
+def test_config_layout(lib):
+    names = ["t_max", "tol", "h0", "growth", "h_max", "normal_eps", "bound_radius", "max_steps", "reserved"]
+    assert ctypes.sizeof(_native.RmIntervalConfig) == lib.rmi_sizeof_config() == 64
+    for i, n in enumerate(names):
+        assert getattr(_native.RmIntervalConfig, n).offset == lib.rmi_offsetof_config(i), n
+
+
+def test_abi_layout_gcc():
+    """RmIntervalConfig as gcc lays it out from include/rm_hip.h (as test_abi.py does for the other records)"""
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "rm_hip.h"\nint main(void){printf("%zu %zu %zu %zu\\n", '
+           'sizeof(RmIntervalConfig), offsetof(RmIntervalConfig, bound_radius), offsetof(RmIntervalConfig, max_steps), '
+           'offsetof(RmIntervalConfig, reserved));return 0;}\n')
+    with tempfile.TemporaryDirectory() as td:
+        c = os.path.join(td, "a.c")
+        with open(c, "w") as f:
+            f.write(src)
+        exe = os.path.join(td, "a")
+        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, c], check=True)
+        got = [int(x) for x in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    C = _native.RmIntervalConfig
+    assert got == [ctypes.sizeof(C), C.bound_radius.offset, C.max_steps.offset, C.reserved.offset]
+
+
+BAD_CONFIGS = [("t_max", -1.0), ("tol", -1e-5), ("h0", float("nan")), ("growth", 1.0), ("growth", 0.5), ("h_max", float("inf")),
+               ("normal_eps", -1e-4), ("bound_radius", float("nan")), ("max_steps", -1), ("max_steps", _native.RM_INTERVAL_MAX_STEPS + 1),
+               ("reserved", 1)]
+
+
+@pytest.mark.parametrize("field,value", BAD_CONFIGS)
+def test_bad_config(field, value):
+    L = _native.load()
+    cfg = _native.RmIntervalConfig()
+    setattr(cfg, field, value)
+    o = np.zeros(3)
+    t = np.empty(1)
+    rc = L.rm_interval_march_rays(0, ctypes.byref(cfg), o.ctypes.data_as(dp), o.ctypes.data_as(dp), 1, t.ctypes.data_as(dp),
+                                  None, None)
+    assert rc == _native.RM_E_BAD_ARG, rc
+    desc = _native.make_desc(0, 0, np.zeros(14), 4, 4)
+    assert L.rm_interval_render(ctypes.byref(desc), ctypes.byref(cfg), None, None, None, None, None) == _native.RM_E_BAD_ARG
+
+
+def test_bad_scene_and_no_device():
+    L = _native.load()
+    o = np.zeros(3)
+    t = np.empty(1)
+    for sid in (9, 10, 11, 15, 16, 18, 20, -1, 5000):
+        rc = L.rm_interval_march_rays(sid, None, o.ctypes.data_as(dp), o.ctypes.data_as(dp), 1, t.ctypes.data_as(dp), None, None)
+        assert rc == _native.RM_E_BAD_SCENE, (sid, rc)
+        desc = _native.make_desc(sid, 0, np.zeros(14), 4, 4)
+        assert L.rm_interval_render(ctypes.byref(desc), None, None, None, None, None, None) == _native.RM_E_BAD_SCENE, sid
+    # every call that passes the host checks needs a device: a fresh process that never called rm_init
+    code = (
+        "import ctypes, numpy as np\n"
+        "from raymarch_algo_compare_amd import _native\n"
+        "L = _native.load(); dp = ctypes.POINTER(ctypes.c_double)\n"
+        "o = np.zeros(3); t = np.empty(1); d = np.empty(16); h = np.empty(16, np.uint8)\n"
+        "desc = _native.make_desc(3, 0, np.zeros(14), 4, 4)\n"
+        "print(L.rm_interval_march_rays(0, None, o.ctypes.data_as(dp), o.ctypes.data_as(dp), 1, t.ctypes.data_as(dp), None, None),"
+        " L.rm_interval_sdf_eval(0, o.ctypes.data_as(dp), o.ctypes.data_as(dp), 1, t.ctypes.data_as(dp), t.ctypes.data_as(dp)),"
+        " L.rm_interval_render(ctypes.byref(desc), None, d.ctypes.data_as(dp), h.ctypes.data, None, None, None))\n")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, check=True, capture_output=True, text=True).stdout
+    assert [int(x) for x in out.split()] == [_native.RM_E_NO_DEVICE] * 3, out
+
+
+# ---- 6. scoring.py ---------------------------------------------------------------------------------------------------------
+
+def _cap(hit, depth, normal=None):
+    hit = np.asarray(hit, bool)
+    if normal is None:
+        normal = np.zeros(hit.shape + (3,))
+        normal[..., 2] = 1.0
+    return {"hit": hit, "depth": np.asarray(depth, np.float64), "normal": np.asarray(normal, np.float64)}
+
+
+def test_scoring_hit_metrics():
+    m = _cap([[1, 1, 0, 0]], [[1.0, 2.0, 0, 0]])
+    r = _cap([[1, 0, 1, 0]], [[1.5, 0, 3.0, 0]])
+    s = scoring.score_capture(m, r, compute_ssim=False)
+    assert s["primary"] == s["hit"]
+    assert s["hit"]["iou"] == pytest.approx(1 / 3)
+    assert s["hit"]["false_hit_rate"] == pytest.approx(0.25)
+    assert s["hit"]["false_miss_rate"] == pytest.approx(0.25)
+    assert s["hit"]["agreement"] == pytest.approx(0.5)
+    assert s["depth"]["n_pixels"] == 1 and s["depth"]["mae"] == pytest.approx(0.5) and s["depth"]["rmse"] == pytest.approx(0.5)
+    assert s["secondary"] == {"depth": s["depth"], "normal": s["normal"]}
+    assert s["tertiary"] == s["ssim"] == {"depth_ssim": None, "normal_ssim": None, "color_ssim": None, "color_rmse": None}
+    empty = scoring._hit_metrics(np.zeros((2, 2), bool), np.zeros((2, 2), bool))
+    assert empty["iou"] == 1.0 and empty["agreement"] == 1.0
+
+
+def test_scoring_depth_and_angle():
+    rng = np.random.default_rng(3)
+    d_ref = rng.uniform(1, 5, size=(8, 8))
+    err = rng.uniform(-0.1, 0.1, size=(8, 8))
+    hit = np.ones((8, 8), bool)
+    dm = scoring._depth_metrics(_cap(hit, d_ref + err), _cap(hit, d_ref))
+    e = np.abs((d_ref + err) - d_ref).ravel()
+    assert dm["rmse"] == pytest.approx(math.sqrt(float(np.mean(e ** 2))))
+    assert dm["mae"] == pytest.approx(float(np.mean(e)))
+    assert dm["p95"] == pytest.approx(float(np.percentile(e, 95)))
+    assert dm["n_pixels"] == 64
+    a = np.zeros((1, 2, 3))
+    a[..., 2] = 1.0
+    b = np.zeros((1, 2, 3))
+    b[0, 0] = (0.0, 0.0, 1.0)
+    b[0, 1] = (1.0, 0.0, 0.0)
+    na = scoring._normal_angle_error(_cap([[1, 1]], [[1, 1]], a), _cap([[1, 1]], [[1, 1]], b))
+    assert na["mean_deg"] == pytest.approx(45.0)
+    assert na["p95_deg"] == pytest.approx(float(np.percentile([0.0, 90.0], 95)))
+
+
+def test_scoring_no_cohit_and_shape_mismatch():
+    m = _cap([[1, 0]], [[1.0, 0]])
+    r = _cap([[0, 1]], [[0, 2.0]])
+    s = scoring.score_capture(m, r, compute_ssim=False)
+    assert s["depth"]["n_pixels"] == 0 and all(math.isnan(s["depth"][k]) for k in ("rmse", "mae", "p95"))
+    assert math.isnan(s["normal"]["mean_deg"]) and math.isnan(s["normal"]["p95_deg"])
+    assert s["hit"]["iou"] == 0.0
+    with pytest.raises(ValueError):
+        scoring.score_capture(_cap([[1, 0, 1]], [[1, 0, 1]]), r, compute_ssim=False)
+    with pytest.raises(NotImplementedError):
+        scoring.score_capture(m, r, compute_ssim=True)
+
+
+def test_sweep_rejects_unknown_oracle_before_the_device():
+    from raymarch_algo_compare_amd import sweep
+    with pytest.raises(ValueError):
+        sweep.run_sweep(["Sphere"], ["Standard"], oracle="dense")
+
+
+# ---- 7. the code object ------------------------------------------------------------------------------------------------------
+
+OBJ = os.path.join(ROOT, "raymarch_algo_compare_amd", "_build", "interval.o")
+
+
+def _tool():
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_code_object_no_scratch_no_spills():
+    assert os.path.exists(OBJ), "interval.o is missing: build the library (make -C raymarch_algo_compare_amd/csrc)"
+    tool = _tool()
+    kernels = [k for k in tool.collect([OBJ]) if "interval_" in k["demangled"]]
+    assert sorted(re.search(r"interval_\w+_kernel", k["demangled"]).group(0) for k in kernels) == \
+        ["interval_march_kernel", "interval_render_kernel", "interval_sdf_kernel"]
+    found = {}
+    with tempfile.TemporaryDirectory() as td:
+        for co in tool.code_objects(OBJ, td):
+            dis = subprocess.run([os.path.join(tool.LLVM, "llvm-objdump"), "-d", co], check=True, capture_output=True,
+                                 text=True).stdout
+            cur = None
+            for line in dis.splitlines():
+                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+                if m:
+                    cur = m.group(1)
+                    found.setdefault(cur, [])
+                elif cur and re.search(r"\b(scratch|buffer)_", line):
+                    found[cur].append(line.strip())
+    for k in kernels:
+        assert found.get(k["name"]) == [], (k["demangled"], found.get(k["name"], "not disassembled")[:4])
+        assert k["vgpr_spill_count"] == 0, k["demangled"]
+        assert k["private_segment_fixed_size"] == 0, k["demangled"]
