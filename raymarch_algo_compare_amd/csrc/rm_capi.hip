@@ -87,9 +87,15 @@ int fail(int code, const char* fmt, ...)
             return fail(RM_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// A grow-only device buffer.  Every Buf links itself into its owner's list when it is constructed, so "free all the
+// device memory this owner holds" is a walk of that list (release_all): a new buffer needs no second edit anywhere.
 struct Buf {
     void* p = nullptr;
     size_t cap = 0;
+    Buf* const next;
+    explicit Buf(Buf*& owner) : next(owner) { owner = this; }
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
     int ensure(size_t bytes)
     {
         if (bytes <= cap) return RM_OK;
@@ -107,28 +113,33 @@ struct Buf {
     }
 };
 
-struct State {
+void release_all(Buf* owner)
+{
+    for (Buf* b = owner; b; b = b->next) b->release();
+}
+Buf* g_workspace_bufs = nullptr;   // freed by rm_shutdown
+Buf* g_comm_bufs = nullptr;        // freed by rm_comm_destroy
+struct WsBuf : Buf { WsBuf() : Buf(g_workspace_bufs) {} };
+struct CommBuf : Buf { CommBuf() : Buf(g_comm_bufs) {} };
+
+// Everything one rm_init .. rm_shutdown life of the library knows, the device buffers aside: rm_shutdown destroys the
+// stream and the events and then assigns a fresh Session, so nothing that described freed memory survives it and a
+// new field needs no line there.
+struct Session {
     bool ready = false;
     int device = -1;
     hipStream_t stream = nullptr;
     hipDeviceProp_t prop;
     bool stats_ready = false;   // the library's statistics buffer was left clean by a fused-reduce frame (launch_frame)
-    Buf stats, depth, iters, hit, traw, fs, bvar, evals, in0, in1, out0, out1, out2, out3, tcost, torder, queue[rm::kQueues];
     // shape of the frame whose per-tile costs sit in `tcost` (tile_order_mode 1 needs a match)
     long long cost_key[10] = { -1 };
     bool cost_valid = false;
     hipEvent_t ev[2 * RM_MAX_TIMED];
     bool events = false;
-    Buf bstats;   // rm_render_batch: the device frame table
-    Buf ivprog;   // rm_interval_*: the device image of a catalogue scene's program
-    Buf ctl;      // single-launch pipeline: its hot counters, one per 128-byte line
-    Buf busy;     // rm_march_rays_team: the counter its filler workgroups watch (its own word: a frame in flight owns `ctl`)
-    Buf trace, trace_start, trace_detach;   // development trace of single-launch frames (rm_debug_set_trace)
-    bool tracing = false;
+    bool tracing = false;                   // development trace of single-launch frames (rm_debug_set_trace)
     size_t trace_pix = 0;
     unsigned long long trace_t0 = 0;        // low bits irrelevant: the start mark of the traced frame is read back from the stats block
-    Buf ccost, corder;   // single-launch pipeline: the centre-out tile order of the frame shape `corder_key`
-    long long corder_key[12] = { -1 };
+    long long corder_key[12] = { -1 };      // the frame shape whose centre-out tile order sits in `corder`
     bool corder_valid = false;
     // optional per-pass timing of the last frame (rm_set_pass_timing): events around the passes
     bool pass_timing = false;
@@ -149,6 +160,19 @@ struct State {
     hipEvent_t frame_ev = nullptr;                   // end of the latest frame, on `frame_stream` (frames share one workspace)
     hipStream_t frame_stream = nullptr;
     bool frame_ev_valid = false;
+};
+
+// The library's state: the session and the grow-only device workspace.  Only buffers are declared here (anything else
+// belongs to Session, where rm_shutdown resets it).
+struct State : Session {
+    WsBuf stats, depth, iters, hit, traw, fs, bvar, evals, tcost, torder, queue[rm::kQueues];
+    WsBuf in[2], out[4];   // staging of the per-point / per-ray calls (Staged)
+    WsBuf bstats;   // rm_render_batch: the device frame table
+    WsBuf ivprog;   // rm_interval_*: the device image of a catalogue scene's program
+    WsBuf ctl;      // single-launch pipeline: its hot counters, one per 128-byte line
+    WsBuf busy;     // rm_march_rays_team: the counter its filler workgroups watch (its own word: a frame in flight owns `ctl`)
+    WsBuf trace, trace_start, trace_detach;   // development trace of single-launch frames (rm_debug_set_trace)
+    WsBuf ccost, corder;   // single-launch pipeline: the centre-out tile order of the frame shape `corder_key`
 } g;
 
 std::mutex g_mu;
@@ -179,11 +203,18 @@ const rm::SceneLaunchers* program_launchers()
 // The kernels of scene `id` (a catalogue scene or a program; check_scene has accepted the id)
 const rm::SceneLaunchers* launchers(int id) { return is_program_id(id) ? program_launchers() : rm::scene(id); }
 
+bool program_exists(int id)
+{
+    std::lock_guard<std::mutex> lk(g_prog_mu);
+    return g_programs.count(id) != 0;
+}
+
+int no_such_program(int id) { return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id); }
+
 int check_scene(int id)
 {
     if (is_program_id(id)) {
-        std::lock_guard<std::mutex> lk(g_prog_mu);
-        if (!g_programs.count(id)) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id);
+        if (!program_exists(id)) return no_such_program(id);
         if (!program_launchers()) return fail(RM_E_BAD_SCENE, "the scene-program kernels are not built into this (development) library");
         return RM_OK;
     }
@@ -200,7 +231,7 @@ int scene_data(int id, const void** data)
     if (!is_program_id(id)) return RM_OK;
     std::lock_guard<std::mutex> lk(g_prog_mu);
     auto it = g_programs.find(id);
-    if (it == g_programs.end()) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id);
+    if (it == g_programs.end()) return no_such_program(id);
     Program& p = it->second;
     if (!p.dev) {
         void* dev = nullptr;
@@ -277,16 +308,105 @@ int check_stream(void* stream)
     return RM_OK;
 }
 
+int select_device()
+{
+    HIP_TRY(hipSetDevice(g.device));
+    return RM_OK;
+}
+
+// An entry point's way to the workspace and the device.  Constructing one takes g_mu, refuses a library without a device
+// (RM_E_NO_DEVICE) and selects the device, in that order; while rc() is RM_OK the lock is held until the Entry goes out
+// of scope.  Whatever enqueues on the workspace (Staged, timed, read_stats, shard_open, interval_program) asks for an
+// Entry, so it cannot be reached without the lock held and the device selected.
+class Entry {
+public:
+    Entry() : lk_(g_mu), rc_(check_ready())
+    {
+        if (!rc_) rc_ = select_device();
+        if (rc_) lk_.unlock();
+    }
+    int rc() const { return rc_; }
+    // The stream a call enqueues on: the caller's (checked: check_stream) or, for NULL, the library's own.
+    int stream(void* users, hipStream_t* s) const
+    {
+        if (int rc = check_stream(users)) return rc;
+        *s = users ? (hipStream_t)users : g.stream;
+        return RM_OK;
+    }
+
+private:
+    std::unique_lock<std::mutex> lk_;
+    int rc_;
+};
+
+// The staging of a call that takes host arrays and returns host arrays: inputs and outputs are declared with the
+// workspace buffer that carries them (every `ensure` happens here, before anything is enqueued), begin() reports an
+// allocation failure or enqueues the uploads, download() enqueues the copies back in declaration order and finish()
+// waits for them.  A NULL host output is an optional one the caller did not ask for: nothing is allocated or copied
+// and its device pointer is NULL.  Everything runs on the library's stream.
+class Staged {
+public:
+    explicit Staged(const Entry&) {}
+    template <class T>
+    const T* in(Buf& b, const T* host, size_t bytes)
+    {
+        return (const T*)add(b, const_cast<T*>(host), bytes, 0, true);
+    }
+    template <class T>
+    T* out(Buf& b, T* host, size_t bytes, size_t slack = 0)
+    {
+        return host ? (T*)add(b, host, bytes, slack, false) : nullptr;
+    }
+    int begin()
+    {
+        if (rc_) return rc_;
+        for (int i = 0; i < n_; ++i)
+            if (v_[i].upload) HIP_TRY(hipMemcpyAsync(v_[i].dev, v_[i].host, v_[i].bytes, hipMemcpyHostToDevice, g.stream));
+        return RM_OK;
+    }
+    int download()
+    {
+        for (int i = 0; i < n_; ++i)
+            if (!v_[i].upload && v_[i].bytes) HIP_TRY(hipMemcpyAsync(v_[i].host, v_[i].dev, v_[i].bytes, hipMemcpyDeviceToHost, g.stream));
+        return RM_OK;
+    }
+    int finish()
+    {
+        if (int rc = download()) return rc;
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        return RM_OK;
+    }
+
+private:
+    void* add(Buf& b, void* host, size_t bytes, size_t slack, bool upload)
+    {
+        if (rc_) return nullptr;
+        if (n_ == kMax) { rc_ = fail(RM_E_BAD_ARG, "more than %d staged arrays", kMax); return nullptr; }
+        if ((rc_ = b.ensure(bytes + slack))) return nullptr;
+        v_[n_++] = { host, b.p, bytes, upload };
+        return b.p;
+    }
+    static constexpr int kMax = 8;
+    struct Array { void* host; void* dev; size_t bytes; bool upload; } v_[kMax];
+    int n_ = 0, rc_ = RM_OK;
+};
+
+// The rows [row0, row0 + rows) of a width x height frame; a band-cyclic slice (check_desc) has its own test of the last row.
+int check_slice(const RmFrameDesc* d, bool band_cyclic)
+{
+    if (d->width <= 0 || d->height <= 0 || d->row0 < 0 || d->rows < 0 || (!band_cyclic && d->row0 + d->rows > d->height))
+        return fail(RM_E_BAD_DIMS, "bad frame slice: %dx%d rows [%d,%d)", d->width, d->height, d->row0, d->row0 + d->rows);
+    if ((long long)d->width * d->height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "frame too large");
+    return RM_OK;
+}
+
 int check_desc(const RmFrameDesc* d)
 {
     if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
     if (int rc = check_scene(d->scene_id)) return rc;
     if (d->strategy_id < 0 || d->strategy_id >= RM_NUM_STRATEGY_KERNELS)
         return fail(RM_E_BAD_STRATEGY, "strategy_id %d out of range", d->strategy_id);
-    if (d->width <= 0 || d->height <= 0 || d->row0 < 0 || d->rows < 0 ||
-        (!(d->band_rows > 0 && d->band_stride > 1) && d->row0 + d->rows > d->height))
-        return fail(RM_E_BAD_DIMS, "bad frame slice: %dx%d rows [%d,%d)", d->width, d->height, d->row0, d->row0 + d->rows);
-    if ((long long)d->width * d->height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "frame too large");
+    if (int rc = check_slice(d, d->band_rows > 0 && d->band_stride > 1)) return rc;
     if (d->tile_rows != 0 && d->tile_rows != 4 && d->tile_rows != 1) return fail(RM_E_BAD_ARG, "tile_rows must be 0, 4 or 1");
     if (d->tile_order_mode < 0 || d->tile_order_mode > 4) return fail(RM_E_BAD_ARG, "tile_order_mode must be 0 .. 4");
     if (d->eval_mode < 0 || d->eval_mode > 2) return fail(RM_E_BAD_ARG, "eval_mode must be 0, 1 or 2");
@@ -707,24 +827,47 @@ int ensure_events()
     return RM_OK;
 }
 
-// Launch warmup + repeats times; each timed launch bracketed by events on the launch stream.
-int timed_launches(const RmFrameDesc* d, const rm::LaunchPlan& p, const rm::KernelArgs& a, RmTiming* t)
+int check_timing(const RmTiming* t)
 {
     if (t->repeats < 1 || t->repeats > RM_MAX_TIMED || t->warmup < 0)
         return fail(RM_E_BAD_ARG, "timing: repeats must be 1..%d, warmup >= 0", RM_MAX_TIMED);
-    int rc = ensure_events();
-    if (rc) return rc;
+    return RM_OK;
+}
+
+// Runs `once` (one enqueue on `s`, returning an RM_ code) warmup + repeats times, each timed run bracketed by events
+// on `s`; waits for the stream and fills ms_each and the summary of `t`.
+template <class Once>
+int timed(const Entry&, RmTiming* t, hipStream_t s, Once once)
+{
+    int rc = check_timing(t);
+    if (rc || (rc = ensure_events())) return rc;
     for (int i = 0; i < t->warmup; ++i)
-        if ((rc = launch(d, p, a, g.stream))) return rc;
+        if ((rc = once())) return rc;
     for (int i = 0; i < t->repeats; ++i) {
-        // events bracket one whole frame: stats reset, optional tile ordering, render kernel
-        HIP_TRY(hipEventRecord(g.ev[2 * i], g.stream));
-        if ((rc = launch(d, p, a, g.stream))) return rc;
-        HIP_TRY(hipEventRecord(g.ev[2 * i + 1], g.stream));
+        HIP_TRY(hipEventRecord(g.ev[2 * i], s));
+        if ((rc = once())) return rc;
+        HIP_TRY(hipEventRecord(g.ev[2 * i + 1], s));
     }
-    HIP_TRY(hipStreamSynchronize(g.stream));
+    HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < t->repeats; ++i) HIP_TRY(hipEventElapsedTime(&t->ms_each[i], g.ev[2 * i], g.ev[2 * i + 1]));
     summarise(t);
+    return RM_OK;
+}
+
+// The events of timed() bracket one whole frame: stats reset, optional tile ordering, render kernel.
+int timed_launches(const Entry& e, const RmFrameDesc* d, const rm::LaunchPlan& p, const rm::KernelArgs& a, RmTiming* t)
+{
+    return timed(e, t, g.stream, [&] { return launch(d, p, a, g.stream); });
+}
+
+// The canonical statistics block at `dev`, read once `s` has run dry: the pipeline's error word, then the counters.
+int read_stats(const Entry&, const void* dev, hipStream_t s, RmStats* out)
+{
+    unsigned long long w[rm::kStatsWords];
+    HIP_TRY(hipMemcpyAsync(w, dev, kStatsBlockBytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = check_pipeline_error(w)) return rc;
+    if (out) decode_stats(w, out);
     return RM_OK;
 }
 
@@ -742,7 +885,7 @@ struct Rccl {
     decltype(&ncclGetErrorString) GetErrorString = nullptr;
     ncclComm_t comm = nullptr;
     int world = 0, rank = -1;
-    Buf gather[3], pad[3];      // all-gather landing buffers (rank-major) and padded send buffers of a short last shard
+    CommBuf gather[3], pad[3];  // all-gather landing buffers (rank-major) and padded send buffers of a short last shard
 } R;
 
 int rccl_load()
@@ -875,7 +1018,7 @@ int rm_scene_program_destroy(int32_t scene_id)
     {
         std::lock_guard<std::mutex> lp(g_prog_mu);
         auto it = g_programs.find(scene_id);
-        if (it == g_programs.end()) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", scene_id);
+        if (it == g_programs.end()) return no_such_program(scene_id);
         dev = it->second.dev;
         g_programs.erase(it);
     }
@@ -923,22 +1066,11 @@ void rm_shutdown(void)
     if (!g.ready) return;
     (void)hipSetDevice(g.device);
     (void)hipStreamSynchronize(g.stream);
-    g.corder_valid = false;
-    g.cost_valid = false;
-    g.stats_ready = false;
-    for (auto& k : g.qkey) k = State::QueueKey();
-    g.tracing = false;
     g_seen_streams.clear();
-    for (Buf* b : { &g.trace, &g.trace_start, &g.trace_detach, &g.ccost, &g.corder, &g.ctl, &g.busy, &g.bstats, &g.stats, &g.depth, &g.iters, &g.hit, &g.traw, &g.fs, &g.bvar, &g.evals, &g.in0, &g.in1, &g.out0, &g.out1,
-                    &g.out2, &g.out3, &g.tcost, &g.torder, &g.queue[0], &g.queue[1], &g.ivprog })
-        b->release();
+    release_all(g_workspace_bufs);
     if (g.frame_ev_valid) (void)hipEventDestroy(g.frame_ev);
-    g.frame_ev_valid = false;
     if (g.events) for (auto& e : g.ev) (void)hipEventDestroy(e);
-    g.events = false;
     if (g.pev_ready) for (auto& e : g.pev) (void)hipEventDestroy(e);
-    g.pev_ready = false;
-    g.pass_timing = false;
     {
         // programs stay registered; their device copies are made again by the next frame after rm_init
         std::lock_guard<std::mutex> lp(g_prog_mu);
@@ -948,11 +1080,8 @@ void rm_shutdown(void)
                 kv.second.dev = nullptr;
             }
     }
-
     (void)hipStreamDestroy(g.stream);
-    g.stream = nullptr;
-    g.ready = false;
-    g.device = -1;
+    static_cast<Session&>(g) = Session();       // not ready, no device, and nothing remembered about what was just freed
 }
 
 int rm_device_info(RmDeviceInfo* out)
@@ -973,44 +1102,43 @@ int rm_device_info(RmDeviceInfo* out)
 
 int rm_sdf_eval(int scene_id, const double* xyz, size_t n, double* out)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_scene(scene_id))) return rc;
+    Entry e;
+    int rc = e.rc();
+    if (rc || (rc = check_scene(scene_id))) return rc;
     if (n == 0) return RM_OK;
     if (!xyz || !out) return fail(RM_E_BAD_ARG, "NULL buffer");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const void* data = nullptr;
     if ((rc = scene_data(scene_id, &data))) return rc;
-    if ((rc = g.in0.ensure(n * 24)) || (rc = g.out0.ensure(n * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(g.in0.p, xyz, n * 24, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(launchers(scene_id)->sdf_eval((const double*)g.in0.p, n, (double*)g.out0.p, data, g.stream));
-    HIP_TRY(hipMemcpyAsync(out, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
+    Staged st(e);
+    const double* d_xyz = st.in(g.in[0], xyz, n * 24);
+    double* d_out = st.out(g.out[0], out, n * 8);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(launchers(scene_id)->sdf_eval(d_xyz, n, d_out, data, g.stream));
+    return st.finish();
 }
 
 static int march_rays_impl(bool team, int scene_id, int strategy_id, const RmMarchConfig* cfg, const double* origins,
                            const double* dirs, size_t n, uint8_t* hit, double* t, int32_t* iters, double* final_sdf)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_scene(scene_id))) return rc;
+    Entry e;
+    int rc = e.rc();
+    if (rc || (rc = check_scene(scene_id))) return rc;
     if (strategy_id < 0 || strategy_id >= RM_NUM_STRATEGY_KERNELS)
         return fail(RM_E_BAD_STRATEGY, "strategy_id %d out of range", strategy_id);
     if (!cfg) return fail(RM_E_BAD_ARG, "cfg is NULL");
     if (team && !launchers(scene_id)->march_rays_team) return fail(RM_E_BAD_SCENE, "scene %d has no wavefront-team form", scene_id);
     if (n == 0) return RM_OK;
     if (!origins || !dirs || !hit || !t || !iters || !final_sdf) return fail(RM_E_BAD_ARG, "NULL buffer");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const void* data = nullptr;
     if ((rc = scene_data(scene_id, &data))) return rc;
-    if ((rc = g.in0.ensure(n * 24)) || (rc = g.in1.ensure(n * 24)) || (rc = g.out0.ensure(n)) ||
-        (rc = g.out1.ensure(n * 8)) || (rc = g.out2.ensure(n * 4)) || (rc = g.out3.ensure(n * 8)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(g.in0.p, origins, n * 24, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(hipMemcpyAsync(g.in1.p, dirs, n * 24, hipMemcpyHostToDevice, g.stream));
+    Staged st(e);
+    const double* d_origins = st.in(g.in[0], origins, n * 24);
+    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
+    uint8_t* d_hit = st.out(g.out[0], hit, n);
+    double* d_t = st.out(g.out[1], t, n * 8);
+    int32_t* d_iters = st.out(g.out[2], iters, n * 4);
+    double* d_fs = st.out(g.out[3], final_sdf, n * 8);
+    if ((rc = st.begin())) return rc;
     rm::MarchCfg c = to_cfg(*cfg);
     c.full = 1;   // per-ray API always returns final_sdf, like MarchResult
     if (team) {
@@ -1020,19 +1148,12 @@ static int march_rays_impl(bool team, int scene_id, int strategy_id, const RmMar
         HIP_TRY(hipMemsetAsync(g.busy.p, 0, sizeof(unsigned long long), g.stream));
         const long long nteams = (long long)((n + 63) / 64);
         const int fillers = (int)std::max<long long>(0, 2ll * g.prop.multiProcessorCount - nteams);
-        HIP_TRY(launchers(scene_id)->march_rays_team(strategy_id, c, (const double*)g.in0.p, (const double*)g.in1.p, n, (uint8_t*)g.out0.p,
-                                                     (double*)g.out1.p, (int32_t*)g.out2.p, (double*)g.out3.p,
+        HIP_TRY(launchers(scene_id)->march_rays_team(strategy_id, c, d_origins, d_dirs, n, d_hit, d_t, d_iters, d_fs,
                                                      (unsigned long long*)g.busy.p, fillers, g.stream));
     } else {
-        HIP_TRY(launchers(scene_id)->march_rays(strategy_id, c, (const double*)g.in0.p, (const double*)g.in1.p, n, (uint8_t*)g.out0.p,
-                                                (double*)g.out1.p, (int32_t*)g.out2.p, (double*)g.out3.p, data, g.stream));
+        HIP_TRY(launchers(scene_id)->march_rays(strategy_id, c, d_origins, d_dirs, n, d_hit, d_t, d_iters, d_fs, data, g.stream));
     }
-    HIP_TRY(hipMemcpyAsync(hit, g.out0.p, n, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(t, g.out1.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(iters, g.out2.p, n * 4, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(final_sdf, g.out3.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
+    return st.finish();
 }
 
 int rm_march_rays(int scene_id, int strategy_id, const RmMarchConfig* cfg, const double* origins, const double* dirs,
@@ -1049,48 +1170,30 @@ int rm_march_rays_team(int scene_id, int strategy_id, const RmMarchConfig* cfg, 
 
 int rm_render_outputs(const RmFrameDesc* d, const RmOutputs* o, RmStats* stats, RmTiming* timing)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_desc(d))) return rc;
+    Entry e;
+    int rc = e.rc();
+    if (rc || (rc = check_desc(d))) return rc;
     if (!o || !o->depth || !o->iters || !o->hit) return fail(RM_E_BAD_ARG, "depth, iters and hit are required");
     if (o->final_sdf && !d->march.full) return fail(RM_E_BAD_ARG, "final_sdf requires march.full = 1");
     if (o->block_var && (d->row0 % 4) != 0) return fail(RM_E_BAD_ARG, "block_var requires row0 %% 4 == 0");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const size_t n = (size_t)d->rows * (size_t)d->width;
     const size_t nblk = (size_t)(d->rows / 4) * (size_t)(d->width / 8);
-    if ((rc = g.depth.ensure(n * 4 + 16)) || (rc = g.iters.ensure(n * 4 + 16)) || (rc = g.hit.ensure(n + 16))) return rc;
-    if (o->t_raw && (rc = g.traw.ensure(n * 8 + 16))) return rc;
-    if (o->final_sdf && (rc = g.fs.ensure(n * 8 + 16))) return rc;
-    if (o->block_var && (rc = g.bvar.ensure(nblk * 8 + 16))) return rc;
-    if (o->evals && (rc = g.evals.ensure(n * 4 + 16))) return rc;
+    Staged st(e);
+    float* d_depth = st.out(g.depth, o->depth, n * 4, 16);
+    int32_t* d_iters = st.out(g.iters, o->iters, n * 4, 16);
+    uint8_t* d_hit = st.out(g.hit, o->hit, n, 16);
+    double* d_traw = st.out(g.traw, o->t_raw, n * 8, 16);
+    double* d_fs = st.out(g.fs, o->final_sdf, n * 8, 16);
+    long long* d_bvar = (long long*)st.out(g.bvar, o->block_var, nblk * 8, 16);
+    int32_t* d_evals = st.out(g.evals, o->evals, n * 4, 16);
+    if ((rc = st.begin())) return rc;
     const rm::LaunchPlan p = plan_for(d);
     rm::KernelArgs a;
-    if ((rc = make_args(d, p, (float*)g.depth.p, (int32_t*)g.iters.p, (uint8_t*)g.hit.p, o->t_raw ? (double*)g.traw.p : nullptr,
-                        o->final_sdf ? (double*)g.fs.p : nullptr, o->block_var ? (long long*)g.bvar.p : nullptr,
-                        (unsigned long long*)g.stats.p, &a)))
-        return rc;
-    a.evals = o->evals ? (int32_t*)g.evals.p : nullptr;
-    if (timing) {
-        if ((rc = timed_launches(d, p, a, timing))) return rc;
-    } else {
-        if ((rc = launch(d, p, a, g.stream))) return rc;
-    }
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(o->depth, g.depth.p, n * 4, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(o->iters, g.iters.p, n * 4, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(o->hit, g.hit.p, n, hipMemcpyDeviceToHost, g.stream));
-        if (o->t_raw) HIP_TRY(hipMemcpyAsync(o->t_raw, g.traw.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-        if (o->final_sdf) HIP_TRY(hipMemcpyAsync(o->final_sdf, g.fs.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-        if (o->block_var && nblk) HIP_TRY(hipMemcpyAsync(o->block_var, g.bvar.p, nblk * 8, hipMemcpyDeviceToHost, g.stream));
-        if (o->evals) HIP_TRY(hipMemcpyAsync(o->evals, g.evals.p, n * 4, hipMemcpyDeviceToHost, g.stream));
-    }
-    unsigned long long w[rm::kStatsWords];
-    HIP_TRY(hipMemcpyAsync(w, g.stats.p, kStatsBlockBytes, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    if ((rc = check_pipeline_error(w))) return rc;
-    if (stats) decode_stats(w, stats);
-    return RM_OK;
+    if ((rc = make_args(d, p, d_depth, d_iters, d_hit, d_traw, d_fs, d_bvar, (unsigned long long*)g.stats.p, &a))) return rc;
+    a.evals = d_evals;
+    if ((rc = timing ? timed_launches(e, d, p, a, timing) : launch(d, p, a, g.stream))) return rc;
+    if ((rc = st.download())) return rc;
+    return read_stats(e, g.stats.p, g.stream, stats);
 }
 
 int rm_render(const RmFrameDesc* d, float* depth, int32_t* iters, uint8_t* hit, double* t_raw, double* final_sdf,
@@ -1104,59 +1207,44 @@ int rm_render(const RmFrameDesc* d, float* depth, int32_t* iters, uint8_t* hit, 
 
 int rm_render_device(const RmFrameDesc* d, void* d_depth, void* d_iters, void* d_hit, void* d_stats, void* stream)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_desc(d))) return rc;
+    Entry e;                                  // the enqueue touches the shared workspace (queues, tile order, pass events)
+    int rc = e.rc();
+    if (rc || (rc = check_desc(d))) return rc;
     if (!d_depth || !d_iters || !d_hit) return fail(RM_E_BAD_ARG, "device output pointers are required");
-    std::lock_guard<std::mutex> lk(g_mu);     // the enqueue touches the shared workspace (queues, tile order, pass events)
-    HIP_TRY(hipSetDevice(g.device));
-    if ((rc = check_stream(stream))) return rc;
+    hipStream_t s;
+    if ((rc = e.stream(stream, &s))) return rc;
     const rm::LaunchPlan p = plan_for(d);
     rm::KernelArgs a;
     if ((rc = make_args(d, p, (float*)d_depth, (int32_t*)d_iters, (uint8_t*)d_hit, nullptr, nullptr, nullptr,
                         (unsigned long long*)(d_stats ? d_stats : g.stats.p), &a)))
         return rc;
-    return launch(d, p, a, stream ? (hipStream_t)stream : g.stream);
+    return launch(d, p, a, s);
 }
 
 int rm_read_stats(const void* d_stats, void* stream, RmStats* out)
 {
-    int rc = check_ready();
+    Entry e;
+    int rc = e.rc();
     if (rc) return rc;
     if (!out) return fail(RM_E_BAD_ARG, "out is NULL");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
-    if ((rc = check_stream(stream))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : g.stream;
-    unsigned long long w[rm::kStatsWords];
-    HIP_TRY(hipMemcpyAsync(w, d_stats ? d_stats : g.stats.p, kStatsBlockBytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = check_pipeline_error(w))) return rc;
-    decode_stats(w, out);
-    return RM_OK;
+    hipStream_t s;
+    if ((rc = e.stream(stream, &s))) return rc;
+    return read_stats(e, d_stats ? d_stats : g.stats.p, s, out);
 }
 
 int rm_bench_device(const RmFrameDesc* d, void* d_depth, void* d_iters, void* d_hit, RmStats* stats, RmTiming* timing)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_desc(d))) return rc;
+    Entry e;
+    int rc = e.rc();
+    if (rc || (rc = check_desc(d))) return rc;
     if (!d_depth || !d_iters || !d_hit || !timing) return fail(RM_E_BAD_ARG, "device outputs and timing are required");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const rm::LaunchPlan p = plan_for(d);
     rm::KernelArgs a;
     if ((rc = make_args(d, p, (float*)d_depth, (int32_t*)d_iters, (uint8_t*)d_hit, nullptr, nullptr, nullptr,
                         (unsigned long long*)g.stats.p, &a)))
         return rc;
-    if ((rc = timed_launches(d, p, a, timing))) return rc;
-    if (stats) {
-        unsigned long long w[rm::kStatsWords];
-        HIP_TRY(hipMemcpy(w, g.stats.p, kStatsBlockBytes, hipMemcpyDeviceToHost));
-        if ((rc = check_pipeline_error(w))) return rc;
-        decode_stats(w, stats);
-    }
-    return RM_OK;
+    if ((rc = timed_launches(e, d, p, a, timing))) return rc;
+    return stats ? read_stats(e, g.stats.p, g.stream, stats) : RM_OK;
 }
 
 int rm_render_batch_outputs(const RmFrameDesc* shape, int32_t nframes, const double* cams, const RmMarchConfig* configs,
@@ -1168,9 +1256,9 @@ int rm_render_batch_outputs(const RmFrameDesc* shape, int32_t nframes, const dou
     int32_t* const iters = o->iters;
     uint8_t* const hit = o->hit;
     int32_t* const evals = o->evals;
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_desc(shape))) return rc;
+    Entry e;
+    int rc = e.rc();
+    if (rc || (rc = check_desc(shape))) return rc;
     if (nframes < 0 || (nframes > 0 && (!cams || !depth || !iters || !hit))) return fail(RM_E_BAD_ARG, "bad batch arguments");
     if (shape->tile_order_mode != 0) return fail(RM_E_BAD_ARG, "tile_order_mode is not supported for batches");
     if (nframes == 0) return RM_OK;
@@ -1180,38 +1268,33 @@ int rm_render_batch_outputs(const RmFrameDesc* shape, int32_t nframes, const dou
     const size_t n = (size_t)shape->rows * (size_t)shape->width;          // elements per frame
     const size_t total = n * (size_t)nframes;
     if (total > (size_t)1 << 31) return fail(RM_E_BAD_DIMS, "batch too large");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     if ((rc = ensure_events())) return rc;
-    if ((rc = g.depth.ensure(total * 4 + 16)) || (rc = g.iters.ensure(total * 4 + 16)) || (rc = g.hit.ensure(total + 16)) ||
-        (rc = g.bstats.ensure(sizeof(rm::FrameParams) * (size_t)nframes)))
-        return rc;
-    if (evals && (rc = g.evals.ensure(total * 4 + 16))) return rc;
     // the frame table: one camera + march configuration per frame
     std::vector<rm::FrameParams> fp((size_t)nframes);
     for (int f = 0; f < nframes; ++f) {
         for (int i = 0; i < 14; ++i) fp[f].cam.v[i] = cams[(size_t)f * 14 + i];
         fp[f].cfg = to_cfg(configs ? configs[f] : shape->march);
     }
-    HIP_TRY(hipMemcpyAsync(g.bstats.p, fp.data(), sizeof(rm::FrameParams) * (size_t)nframes, hipMemcpyHostToDevice, g.stream));
+    Staged st(e);
+    float* d_depth = st.out(g.depth, depth, total * 4, 16);
+    int32_t* d_iters = st.out(g.iters, iters, total * 4, 16);
+    uint8_t* d_hit = st.out(g.hit, hit, total, 16);
+    int32_t* d_evals = st.out(g.evals, evals, total * 4, 16);
+    const rm::FrameParams* d_frames = st.in(g.bstats, fp.data(), sizeof(rm::FrameParams) * (size_t)nframes);
+    if ((rc = st.begin())) return rc;
     const rm::LaunchPlan p = plan_for(shape, nframes, configs);
     RmFrameDesc d = *shape;
     if (p.march_frame >= 0) d.march = configs[p.march_frame];      // (KernelArgs.single: the configuration the plan looked at)
     rm::KernelArgs a;
-    if ((rc = make_args(&d, p, (float*)g.depth.p, (int32_t*)g.iters.p, (uint8_t*)g.hit.p, nullptr, nullptr, nullptr,
-                        (unsigned long long*)g.stats.p, &a)))
-        return rc;
-    a.frames = (const rm::FrameParams*)g.bstats.p;
+    if ((rc = make_args(&d, p, d_depth, d_iters, d_hit, nullptr, nullptr, nullptr, (unsigned long long*)g.stats.p, &a))) return rc;
+    a.frames = d_frames;
     a.nframes = nframes;
     a.full = full;
-    a.evals = evals ? (int32_t*)g.evals.p : nullptr;
+    a.evals = d_evals;
     HIP_TRY(hipEventRecord(g.ev[0], g.stream));
     if ((rc = launch(&d, p, a, g.stream))) return rc;
     HIP_TRY(hipEventRecord(g.ev[1], g.stream));
-    HIP_TRY(hipMemcpyAsync(depth, g.depth.p, total * 4, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(iters, g.iters.p, total * 4, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(hit, g.hit.p, total, hipMemcpyDeviceToHost, g.stream));
-    if (evals) HIP_TRY(hipMemcpyAsync(evals, g.evals.p, total * 4, hipMemcpyDeviceToHost, g.stream));
+    if ((rc = st.download())) return rc;
     unsigned long long whead[rm::kStatsHead];
     HIP_TRY(hipMemcpyAsync(whead, g.stats.p, sizeof whead, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
@@ -1262,13 +1345,12 @@ int rm_comm_unique_id(uint8_t id[RM_COMM_ID_BYTES])
 
 int rm_comm_init(const uint8_t id[RM_COMM_ID_BYTES], int32_t world_size, int32_t rank)
 {
-    int rc = check_ready();
+    Entry e;
+    int rc = e.rc();
     if (rc) return rc;
     if (!id || world_size < 1 || rank < 0 || rank >= world_size) return fail(RM_E_BAD_ARG, "bad communicator arguments");
-    std::lock_guard<std::mutex> lk(g_mu);
     if ((rc = rccl_load())) return rc;
     if (R.comm) return fail(RM_E_BAD_ARG, "a communicator exists already; call rm_comm_destroy() first");
-    HIP_TRY(hipSetDevice(g.device));
     ncclUniqueId u;
     memcpy(&u, id, sizeof u);
     RCCL_TRY(R.CommInitRank(&R.comm, world_size, u, rank));
@@ -1288,8 +1370,7 @@ int rm_comm_destroy(void)
     const ncclResult_t r = R.CommDestroy(R.comm);
     R.comm = nullptr;
     R.world = 0; R.rank = -1;
-    for (Buf& b : R.gather) b.release();
-    for (Buf& b : R.pad) b.release();
+    release_all(g_comm_bufs);
     if (r != ncclSuccess) return fail(RM_E_RCCL, "ncclCommDestroy failed: %s", R.GetErrorString(r));
     return RM_OK;
 }
@@ -1297,7 +1378,8 @@ int rm_comm_destroy(void)
 int rm_assemble_frame(int32_t world_size, int32_t height, int32_t width, int32_t rows_per_rank, int32_t cyclic, int32_t elem_bytes,
                       const void* d_gathered, void* d_full, void* stream)
 {
-    int rc = check_ready();
+    Entry e;
+    int rc = e.rc();
     if (rc) return rc;
     if (world_size < 1 || height < 0 || width <= 0 || rows_per_rank < 0 || (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) ||
         !d_gathered || !d_full)
@@ -1305,71 +1387,82 @@ int rm_assemble_frame(int32_t world_size, int32_t height, int32_t width, int32_t
     if (cyclic && (height % (4 * world_size) != 0 || rows_per_rank != height / world_size))
         return fail(RM_E_BAD_DIMS, "band-cyclic plan needs height %% (4 * world_size) == 0 and rows_per_rank == height / world_size");
     if (!cyclic && (long long)rows_per_rank * world_size < height) return fail(RM_E_BAD_DIMS, "the shards do not cover the frame");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
-    if ((rc = check_stream(stream))) return rc;
-    return assemble(world_size, height, width, rows_per_rank, cyclic ? 1 : 0, elem_bytes, d_gathered, d_full,
-                    stream ? (hipStream_t)stream : g.stream);
+    hipStream_t s;
+    if ((rc = e.stream(stream, &s))) return rc;
+    return assemble(world_size, height, width, rows_per_rank, cyclic ? 1 : 0, elem_bytes, d_gathered, d_full, s);
 }
 
-// The plan a shard descriptor must follow on this communicator: rows every rank contributes (`per`), cyclic or not.
-static int shard_plan(const RmFrameDesc* d, int* per_out, bool* cyclic_out)
+// What rm_gather_frame and rm_gather_frame_root share: this rank's three maps, where they go, and the plan the shard
+// descriptor must follow on this communicator -- rows every rank contributes to the collective (`per`), cyclic or not.
+static const int kMapBytes[3] = { 4, 4, 1 };   // bytes per pixel of depth, iters, hit
+struct Shard {
+    hipStream_t s;
+    int N, H, W, per;
+    bool cyclic, is_root;
+    const void* src[3];
+    void* dst[3];
+    size_t bytes(int k, long long rows) const { return (size_t)rows * W * kMapBytes[k]; }
+};
+
+static int shard_plan(const RmFrameDesc* d, Shard* sh)
 {
     const int N = R.world, H = d->height;
-    const bool cyclic = d->band_rows > 0 && d->band_stride > 1;
-    int per;
-    if (cyclic) {
+    sh->cyclic = d->band_rows > 0 && d->band_stride > 1;
+    if (sh->cyclic) {
         if (d->band_rows != 4 || d->band_stride != N || d->band_offset != R.rank || d->row0 != 0 || H % (4 * N) != 0 || d->rows != H / N)
             return fail(RM_E_BAD_DIMS, "band-cyclic shard does not match the communicator (4-row bands, stride = world size %d, "
                                        "offset = rank %d, rows = height / world size)", N, R.rank);
-        per = d->rows;
+        sh->per = d->rows;
     } else {
-        per = rm_shard_rows(H, N);
-        if (N == 1) per = H;
-        const int r0 = std::min(R.rank * per, H), r1 = std::min((R.rank + 1) * per, H);
+        sh->per = N == 1 ? H : rm_shard_rows(H, N);
+        const int r0 = std::min(R.rank * sh->per, H), r1 = std::min((R.rank + 1) * sh->per, H);
         if (d->row0 != r0 || d->rows != r1 - r0)
             return fail(RM_E_BAD_DIMS, "contiguous shard of rank %d must be rows [%d, %d)", R.rank, r0, r1);
     }
-    *per_out = per;
-    *cyclic_out = cyclic;
     return RM_OK;
+}
+
+// After the descriptor and the shard pointers have been checked: the communicator, the root (`root` only counts with
+// to_root; without it every rank receives the frame), the stream, the plan.
+static int shard_open(const Entry& e, const RmFrameDesc* d, const void* d_depth, const void* d_iters, const void* d_hit, void* d_full_depth,
+                      void* d_full_iters, void* d_full_hit, bool to_root, int root, void* stream, Shard* sh)
+{
+    if (!R.comm) return fail(RM_E_RCCL, "no communicator: call rm_comm_init() first");
+    *sh = Shard{ nullptr, R.world, d->height, d->width, 0, false, true, { d_depth, d_iters, d_hit }, { d_full_depth, d_full_iters, d_full_hit } };
+    if (to_root) {
+        if (root < 0 || root >= R.world) return fail(RM_E_BAD_ARG, "root %d outside the communicator of %d", root, R.world);
+        sh->is_root = R.rank == root;
+        if (sh->is_root && (!d_full_depth || !d_full_iters || !d_full_hit)) return fail(RM_E_BAD_ARG, "the root needs the three full-frame buffers");
+    }
+    if (int rc = e.stream(stream, &sh->s)) return rc;
+    return shard_plan(d, sh);
 }
 
 int rm_gather_frame(const RmFrameDesc* d, const void* d_depth, const void* d_iters, const void* d_hit, void* d_full_depth,
                     void* d_full_iters, void* d_full_hit, void* stream)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_desc(d))) return rc;
+    Entry e;
+    int rc = e.rc();
+    if (rc || (rc = check_desc(d))) return rc;
     if (!d_depth || !d_iters || !d_hit || !d_full_depth || !d_full_iters || !d_full_hit) return fail(RM_E_BAD_ARG, "NULL buffer");
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!R.comm) return fail(RM_E_RCCL, "no communicator: call rm_comm_init() first");
-    HIP_TRY(hipSetDevice(g.device));
-    if ((rc = check_stream(stream))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : g.stream;
-    const int N = R.world, H = d->height, W = d->width;
-    int per = 0;                                   // rows every rank contributes to the collective
-    bool cyclic = false;
-    if ((rc = shard_plan(d, &per, &cyclic))) return rc;
-    const void* src[3] = { d_depth, d_iters, d_hit };
-    void* dst[3] = { d_full_depth, d_full_iters, d_full_hit };
-    const int eb[3] = { 4, 4, 1 };
+    Shard sh;
+    if ((rc = shard_open(e, d, d_depth, d_iters, d_hit, d_full_depth, d_full_iters, d_full_hit, false, 0, stream, &sh))) return rc;
     const void* send[3];
     for (int k = 0; k < 3; ++k) {
-        const size_t shard_bytes = (size_t)per * W * eb[k];
-        if ((rc = R.gather[k].ensure(shard_bytes * (size_t)N + 16))) return rc;
-        send[k] = src[k];
-        if (d->rows < per) {                        // short last shard of a contiguous plan: pad the send buffer
+        const size_t shard_bytes = sh.bytes(k, sh.per);
+        if ((rc = R.gather[k].ensure(shard_bytes * (size_t)sh.N + 16))) return rc;
+        send[k] = sh.src[k];
+        if (d->rows < sh.per) {                     // short last shard of a contiguous plan: pad the send buffer
             if ((rc = R.pad[k].ensure(shard_bytes + 16))) return rc;
-            HIP_TRY(hipMemsetAsync(R.pad[k].p, 0, shard_bytes, s));
-            if (d->rows > 0) HIP_TRY(hipMemcpyAsync(R.pad[k].p, src[k], (size_t)d->rows * W * eb[k], hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemsetAsync(R.pad[k].p, 0, shard_bytes, sh.s));
+            if (d->rows > 0) HIP_TRY(hipMemcpyAsync(R.pad[k].p, sh.src[k], sh.bytes(k, d->rows), hipMemcpyDeviceToDevice, sh.s));
             send[k] = R.pad[k].p;
         }
     }
     // the frame's only exchange: three all-gathers in one group (direct xGMI links between the GPUs of a node)
     RCCL_TRY(R.GroupStart());
     for (int k = 0; k < 3; ++k) {
-        const ncclResult_t r = R.AllGather(send[k], R.gather[k].p, (size_t)per * W * eb[k], ncclUint8, R.comm, s);
+        const ncclResult_t r = R.AllGather(send[k], R.gather[k].p, sh.bytes(k, sh.per), ncclUint8, R.comm, sh.s);
         if (r != ncclSuccess) {
             (void)R.GroupEnd();
             return fail(RM_E_RCCL, "ncclAllGather failed: %s", R.GetErrorString(r));
@@ -1377,51 +1470,39 @@ int rm_gather_frame(const RmFrameDesc* d, const void* d_depth, const void* d_ite
     }
     RCCL_TRY(R.GroupEnd());
     for (int k = 0; k < 3; ++k)
-        if ((rc = assemble(N, H, W, per, cyclic ? 1 : 0, eb[k], R.gather[k].p, dst[k], s))) return rc;
+        if ((rc = assemble(sh.N, sh.H, sh.W, sh.per, sh.cyclic ? 1 : 0, kMapBytes[k], R.gather[k].p, sh.dst[k], sh.s))) return rc;
     return RM_OK;
 }
 
 int rm_gather_frame_root(const RmFrameDesc* d, const void* d_depth, const void* d_iters, const void* d_hit, void* d_full_depth,
                          void* d_full_iters, void* d_full_hit, int32_t root, void* stream)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    if ((rc = check_desc(d))) return rc;
+    Entry e;
+    int rc = e.rc();
+    if (rc || (rc = check_desc(d))) return rc;
     if (!d_depth || !d_iters || !d_hit) return fail(RM_E_BAD_ARG, "NULL shard buffer");
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!R.comm) return fail(RM_E_RCCL, "no communicator: call rm_comm_init() first");
-    if (root < 0 || root >= R.world) return fail(RM_E_BAD_ARG, "root %d outside the communicator of %d", root, R.world);
-    const bool is_root = R.rank == root;
-    if (is_root && (!d_full_depth || !d_full_iters || !d_full_hit)) return fail(RM_E_BAD_ARG, "the root needs the three full-frame buffers");
-    HIP_TRY(hipSetDevice(g.device));
-    if ((rc = check_stream(stream))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : g.stream;
-    const int N = R.world, H = d->height, W = d->width;
-    int per = 0;
-    bool cyclic = false;
-    if ((rc = shard_plan(d, &per, &cyclic))) return rc;
-    const void* src[3] = { d_depth, d_iters, d_hit };
-    void* dst[3] = { d_full_depth, d_full_iters, d_full_hit };
-    const int eb[3] = { 4, 4, 1 };
-    auto rows_of = [&](int r) { return cyclic ? per : std::max(0, std::min((r + 1) * per, H) - std::min(r * per, H)); };
+    Shard sh;
+    if ((rc = shard_open(e, d, d_depth, d_iters, d_hit, d_full_depth, d_full_iters, d_full_hit, true, root, stream, &sh))) return rc;
+    const int N = sh.N, H = sh.H, per = sh.per;
+    auto rows_of = [&](int r) { return sh.cyclic ? per : std::max(0, std::min((r + 1) * per, H) - std::min(r * per, H)); };
     // Where rank r's rows land on the root: contiguous plan -> straight into the image (its rows are one block there: no
     // second pass over the frame); band-cyclic plan -> slot r of a rank-major landing buffer, placed by ONE pass of
     // assemble_rows_kernel afterwards (receiving every 4-row band into place would be H / (4 N) x 3 x (N - 1)
     // point-to-point operations per frame: 2835 at 7680x4320 on 8 ranks).
-    if (is_root && cyclic)
+    if (sh.is_root && sh.cyclic)
         for (int k = 0; k < 3; ++k)
-            if ((rc = R.gather[k].ensure((size_t)per * W * eb[k] * (size_t)N + 16))) return rc;
+            if ((rc = R.gather[k].ensure(sh.bytes(k, per) * (size_t)N + 16))) return rc;
     auto slot = [&](int k, int r) -> char* {
-        return cyclic ? (char*)R.gather[k].p + (size_t)r * per * W * eb[k] : (char*)dst[k] + (size_t)std::min(r * per, H) * W * eb[k];
+        return sh.cyclic ? (char*)R.gather[k].p + sh.bytes(k, (long long)r * per) : (char*)sh.dst[k] + sh.bytes(k, std::min(r * per, H));
     };
     RCCL_TRY(R.GroupStart());
     ncclResult_t err = ncclSuccess;
     for (int k = 0; k < 3 && err == ncclSuccess; ++k) {
-        if (!is_root) {
-            if (d->rows > 0) err = R.Send(src[k], (size_t)d->rows * W * eb[k], ncclUint8, root, R.comm, s);
+        if (!sh.is_root) {
+            if (d->rows > 0) err = R.Send(sh.src[k], sh.bytes(k, d->rows), ncclUint8, root, R.comm, sh.s);
         } else {
             for (int r = 0; r < N && err == ncclSuccess; ++r)
-                if (r != root && rows_of(r) > 0) err = R.Recv(slot(k, r), (size_t)rows_of(r) * W * eb[k], ncclUint8, r, R.comm, s);
+                if (r != root && rows_of(r) > 0) err = R.Recv(slot(k, r), sh.bytes(k, rows_of(r)), ncclUint8, r, R.comm, sh.s);
         }
     }
     if (err != ncclSuccess) {
@@ -1429,13 +1510,13 @@ int rm_gather_frame_root(const RmFrameDesc* d, const void* d_depth, const void* 
         return fail(RM_E_RCCL, "ncclSend / ncclRecv failed: %s", R.GetErrorString(err));
     }
     RCCL_TRY(R.GroupEnd());
-    if (is_root) {
+    if (sh.is_root) {
         for (int k = 0; k < 3; ++k)
-            if (d->rows > 0 && slot(k, root) != (const char*)src[k])
-                HIP_TRY(hipMemcpyAsync(slot(k, root), src[k], (size_t)d->rows * W * eb[k], hipMemcpyDeviceToDevice, s));
-        if (cyclic)
+            if (d->rows > 0 && slot(k, root) != (const char*)sh.src[k])
+                HIP_TRY(hipMemcpyAsync(slot(k, root), sh.src[k], sh.bytes(k, d->rows), hipMemcpyDeviceToDevice, sh.s));
+        if (sh.cyclic)
             for (int k = 0; k < 3; ++k)
-                if ((rc = assemble(N, H, W, per, 1, eb[k], R.gather[k].p, dst[k], s))) return rc;
+                if ((rc = assemble(N, H, sh.W, per, 1, kMapBytes[k], R.gather[k].p, sh.dst[k], sh.s))) return rc;
     }
     return RM_OK;
 }
@@ -1450,10 +1531,8 @@ int rm_set_queue_capacity(int64_t entries)
 
 int rm_set_pass_timing(int enable)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
+    Entry e;
+    if (e.rc()) return e.rc();
     if (enable && !g.pev_ready) {
         for (auto& e : g.pev) HIP_TRY(hipEventCreate(&e));
         g.pev_ready = true;
@@ -1465,14 +1544,13 @@ int rm_set_pass_timing(int enable)
 
 int rm_get_pass_ms(void* stream, int32_t* npasses, float* ms)
 {
-    int rc = check_ready();
+    Entry e;
+    int rc = e.rc();
     if (rc) return rc;
     if (!npasses || !ms) return fail(RM_E_BAD_ARG, "NULL output");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     if (!g.pass_timing || !g.pev_ready) return fail(RM_E_BAD_ARG, "pass timing is off (rm_set_pass_timing)");
-    if ((rc = check_stream(stream))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : g.stream;
+    hipStream_t s;
+    if ((rc = e.stream(stream, &s))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     *npasses = g.pass_count;
     for (int i = 0; i < g.pass_count; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], g.pev[i], g.pev[i + 1]));
@@ -1530,11 +1608,9 @@ int rm_render_batch(const RmFrameDesc* shape, int32_t nframes, const double* cam
 
 int rm_alloc_frame(int32_t width, int32_t rows, void** d_depth, void** d_iters, void** d_hit)
 {
-    int rc = check_ready();
-    if (rc) return rc;
+    Entry e;
+    if (e.rc()) return e.rc();
     if (width <= 0 || rows <= 0 || !d_depth || !d_iters || !d_hit) return fail(RM_E_BAD_ARG, "bad arguments");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const size_t n = (size_t)width * rows;
     HIP_TRY(hipMalloc(d_depth, n * 4));
     HIP_TRY(hipMalloc(d_iters, n * 4));
@@ -1544,10 +1620,8 @@ int rm_alloc_frame(int32_t width, int32_t rows, void** d_depth, void** d_iters, 
 
 int rm_free_frame(void* d_depth, void* d_iters, void* d_hit)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
+    Entry e;
+    if (e.rc()) return e.rc();
     if (d_depth) HIP_TRY(hipFree(d_depth));
     if (d_iters) HIP_TRY(hipFree(d_iters));
     if (d_hit) HIP_TRY(hipFree(d_hit));
@@ -1557,10 +1631,8 @@ int rm_free_frame(void* d_depth, void* d_iters, void* d_hit)
 int rm_copy_frame_to_host(int32_t width, int32_t rows, const void* d_depth, const void* d_iters, const void* d_hit,
                           float* depth, int32_t* iters, uint8_t* hit)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
+    Entry e;
+    if (e.rc()) return e.rc();
     const size_t n = (size_t)width * rows;
     HIP_TRY(hipStreamSynchronize(g.stream));
     if (depth) HIP_TRY(hipMemcpy(depth, d_depth, n * 4, hipMemcpyDeviceToHost));
@@ -1571,10 +1643,8 @@ int rm_copy_frame_to_host(int32_t width, int32_t rows, const void* d_depth, cons
 
 int rm_debug_poison_queues(uint32_t word_offset, uint32_t* next_generation)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
+    Entry e;
+    if (e.rc()) return e.rc();
     HIP_TRY(hipStreamSynchronize(g.stream));
     uint32_t next = g.generation + 1u;
     if (next == 0) next = 1;
@@ -1592,7 +1662,8 @@ int rm_debug_poison_queues(uint32_t word_offset, uint32_t* next_generation)
 
 int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1)
 {
-    int rc = check_ready();
+    Entry e;
+    int rc = e.rc();
     if (rc) return rc;
     if (fn < 0 || fn >= RM_MATH_COUNT) return fail(RM_E_BAD_ARG, "fn %d out of range [0, %d)", (int)fn, (int)RM_MATH_COUNT);
     if (lane_mask == 0) return fail(RM_E_BAD_ARG, "lane_mask is 0: no live lane");
@@ -1600,26 +1671,20 @@ int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, u
     const bool two_out = fn == RM_MATH_POW2 || fn == RM_MATH_POW_HALF_GUARD || fn == RM_MATH_SINCOS || fn == RM_MATH_SINCOS_U;
     if (n == 0) return RM_OK;
     if (!a || !out0 || (two_in && !b) || (two_out && !out1)) return fail(RM_E_BAD_ARG, "NULL buffer");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
-    if ((rc = g.in0.ensure(n * 8)) || (two_in && (rc = g.in1.ensure(n * 8))) || (rc = g.out0.ensure(n * 8)) ||
-        (two_out && (rc = g.out1.ensure(n * 8))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(g.in0.p, a, n * 8, hipMemcpyHostToDevice, g.stream));
-    if (two_in) HIP_TRY(hipMemcpyAsync(g.in1.p, b, n * 8, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(rm::launch_math_check(fn, (const double*)g.in0.p, two_in ? (const double*)g.in1.p : nullptr, n, lane_mask,
-                                  (double*)g.out0.p, two_out ? (double*)g.out1.p : nullptr, g.stream));
-    HIP_TRY(hipMemcpyAsync(out0, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    if (two_out) HIP_TRY(hipMemcpyAsync(out1, g.out1.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
+    Staged st(e);
+    const double* d_a = st.in(g.in[0], a, n * 8);
+    const double* d_b = two_in ? st.in(g.in[1], b, n * 8) : nullptr;
+    double* d_out0 = st.out(g.out[0], out0, n * 8);
+    double* d_out1 = st.out(g.out[1], two_out ? out1 : nullptr, n * 8);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_math_check(fn, d_a, d_b, n, lane_mask, d_out0, d_out1, g.stream));
+    return st.finish();
 }
 
 int rm_debug_set_trace(int enable)
 {
-    int rc = check_ready();
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
+    Entry e;
+    if (e.rc()) return e.rc();
     g.tracing = enable != 0;
     return RM_OK;
 }
@@ -1627,11 +1692,9 @@ int rm_debug_set_trace(int enable)
 int rm_debug_get_trace(uint32_t* records, int64_t max_records, int64_t* nrecords, uint32_t* start_ticks, uint32_t* detach_ticks,
                        int64_t npix, uint32_t* launch_tick)
 {
-    int rc = check_ready();
-    if (rc) return rc;
+    Entry e;
+    if (e.rc()) return e.rc();
     if (!nrecords) return fail(RM_E_BAD_ARG, "nrecords is NULL");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     HIP_TRY(hipDeviceSynchronize());
     if (!g.trace.p || !g.last_stats) return fail(RM_E_BAD_ARG, "no traced single-launch frame (rm_debug_set_trace, then render)");
     uint32_t head[8];
@@ -1672,11 +1735,9 @@ int rm_runtime_info(RmRuntimeInfo* out)
 
 int rm_stream_create(void** stream)
 {
-    int rc = check_ready();
-    if (rc) return rc;
+    Entry e;
+    if (e.rc()) return e.rc();
     if (!stream) return fail(RM_E_BAD_ARG, "stream is NULL");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     g_own_streams.push_back((void*)s);
@@ -1686,14 +1747,11 @@ int rm_stream_create(void** stream)
 
 int rm_stream_synchronize(void* stream)
 {
-    int rc = check_ready();
-    if (rc) return rc;
     hipStream_t s;
     {
-        std::lock_guard<std::mutex> lk(g_mu);
-        HIP_TRY(hipSetDevice(g.device));
-        if ((rc = check_stream(stream))) return rc;
-        s = stream ? (hipStream_t)stream : g.stream;
+        Entry e;
+        int rc = e.rc();
+        if (rc || (rc = e.stream(stream, &s))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(s));      // outside the lock: other threads may enqueue while this one waits
     return RM_OK;
@@ -1701,11 +1759,10 @@ int rm_stream_synchronize(void* stream)
 
 int rm_stream_destroy(void* stream)
 {
-    int rc = check_ready();
+    Entry e;
+    int rc = e.rc();
     if (rc) return rc;
     if (!stream) return RM_OK;
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     if ((rc = check_stream(stream))) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     if (g.frame_ev_valid && g.frame_stream == (hipStream_t)stream) g.frame_stream = nullptr;   // its last frame has completed
@@ -1717,28 +1774,18 @@ int rm_stream_destroy(void* stream)
 
 int rm_bench_store_path(int32_t width, int32_t rows, void* d_depth, void* d_iters, void* d_hit, RmTiming* t)
 {
-    int rc = check_ready();
-    if (rc) return rc;
+    Entry e;
+    if (e.rc()) return e.rc();
     if (width <= 0 || rows <= 0 || !d_depth || !d_iters || !d_hit || !t) return fail(RM_E_BAD_ARG, "bad arguments");
-    if (t->repeats < 1 || t->repeats > RM_MAX_TIMED || t->warmup < 0) return fail(RM_E_BAD_ARG, "bad timing request");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
-    if ((rc = ensure_events())) return rc;
     const int tiles_x = (width + 63) / 64, tiles_y = (rows + 3) / 4;
     const int ntiles = tiles_x * tiles_y;
     const int grid = std::min(ntiles, g.prop.multiProcessorCount * 32);
-    for (int i = 0; i < t->warmup + t->repeats; ++i) {
-        const int k = i - t->warmup;
-        if (k >= 0) HIP_TRY(hipEventRecord(g.ev[2 * k], g.stream));
+    return timed(e, t, g.stream, [&] {
         hipLaunchKernelGGL(store_path_kernel, dim3(grid), dim3(64), 0, g.stream, (float*)d_depth, (int32_t*)d_iters,
                            (uint8_t*)d_hit, width, rows, tiles_x, ntiles);
         HIP_TRY(hipGetLastError());
-        if (k >= 0) HIP_TRY(hipEventRecord(g.ev[2 * k + 1], g.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    for (int i = 0; i < t->repeats; ++i) HIP_TRY(hipEventElapsedTime(&t->ms_each[i], g.ev[2 * i], g.ev[2 * i + 1]));
-    summarise(t);
-    return RM_OK;
+        return (int)RM_OK;
+    });
 }
 
 // ---- interval first-hit oracle (rm_interval.h, rm_interval.hip) ----------------------------------------------------
@@ -1765,11 +1812,7 @@ const rm::ProgramImage* interval_catalogue_image(int id)
 
 int interval_check_scene(int id)
 {
-    if (is_program_id(id)) {
-        std::lock_guard<std::mutex> lk(g_prog_mu);
-        if (!g_programs.count(id)) return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id);
-        return RM_OK;
-    }
+    if (is_program_id(id)) return program_exists(id) ? RM_OK : no_such_program(id);
     if (!interval_catalogue_image(id)) return fail(RM_E_BAD_SCENE, "scene %d has no interval extension", id);
     return RM_OK;
 }
@@ -1784,7 +1827,7 @@ int interval_params(int id, const RmIntervalConfig* cfg, rm::IntervalParams* P)
 
 // the device image of scene `id` (under g_mu with the device selected): a program's own copy, or the catalogue
 // scene's image copied into the library's buffer on the stream
-int interval_program(int id, const void** prog)
+int interval_program(const Entry&, int id, const void** prog)
 {
     if (is_program_id(id)) return scene_data(id, prog);
     const rm::ProgramImage* img = interval_catalogue_image(id);
@@ -1799,10 +1842,7 @@ int interval_program(int id, const void** prog)
 
 int rm_interval_supported(int scene_id)
 {
-    if (is_program_id(scene_id)) {
-        std::lock_guard<std::mutex> lk(g_prog_mu);
-        return g_programs.count(scene_id) ? 1 : 0;
-    }
+    if (is_program_id(scene_id)) return program_exists(scene_id) ? 1 : 0;
     return interval_catalogue_image(scene_id) ? 1 : 0;
 }
 
@@ -1810,23 +1850,20 @@ int rm_interval_sdf_eval(int scene_id, const double* lo, const double* hi, size_
 {
     int rc = interval_check_scene(scene_id);
     if (rc) return rc;
-    if ((rc = check_ready())) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
     if (n == 0) return RM_OK;
     if (!lo || !hi || !out_lo || !out_hi) return fail(RM_E_BAD_ARG, "NULL buffer");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const void* prog = nullptr;
-    if ((rc = interval_program(scene_id, &prog))) return rc;
-    if ((rc = g.in0.ensure(n * 24)) || (rc = g.in1.ensure(n * 24)) || (rc = g.out0.ensure(n * 8)) || (rc = g.out1.ensure(n * 8)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(g.in0.p, lo, n * 24, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(hipMemcpyAsync(g.in1.p, hi, n * 24, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(rm::launch_interval_sdf(prog, (const double*)g.in0.p, (const double*)g.in1.p, n, (double*)g.out0.p,
-                                    (double*)g.out1.p, g.stream));
-    HIP_TRY(hipMemcpyAsync(out_lo, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(out_hi, g.out1.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
+    if ((rc = interval_program(e, scene_id, &prog))) return rc;
+    Staged st(e);
+    const double* d_lo = st.in(g.in[0], lo, n * 24);
+    const double* d_hi = st.in(g.in[1], hi, n * 24);
+    double* d_out_lo = st.out(g.out[0], out_lo, n * 8);
+    double* d_out_hi = st.out(g.out[1], out_hi, n * 8);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_interval_sdf(prog, d_lo, d_hi, n, d_out_lo, d_out_hi, g.stream));
+    return st.finish();
 }
 
 int rm_interval_march_rays(int scene_id, const RmIntervalConfig* cfg, const double* origins, const double* dirs, size_t n,
@@ -1836,25 +1873,21 @@ int rm_interval_march_rays(int scene_id, const RmIntervalConfig* cfg, const doub
     if (rc) return rc;
     rm::IntervalParams P;
     if ((rc = interval_params(scene_id, cfg, &P))) return rc;
-    if ((rc = check_ready())) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
     if (n == 0) return RM_OK;
     if (!origins || !dirs || !t) return fail(RM_E_BAD_ARG, "NULL buffer");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const void* prog = nullptr;
-    if ((rc = interval_program(scene_id, &prog))) return rc;
-    if ((rc = g.in0.ensure(n * 24)) || (rc = g.in1.ensure(n * 24)) || (rc = g.out0.ensure(n * 8)) ||
-        (steps && (rc = g.out1.ensure(n * 4))) || (normals && (rc = g.out2.ensure(n * 24))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(g.in0.p, origins, n * 24, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(hipMemcpyAsync(g.in1.p, dirs, n * 24, hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(rm::launch_interval_march(prog, P, (const double*)g.in0.p, (const double*)g.in1.p, n, (double*)g.out0.p,
-                                      steps ? (int32_t*)g.out1.p : nullptr, normals ? (double*)g.out2.p : nullptr, g.stream));
-    HIP_TRY(hipMemcpyAsync(t, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    if (steps) HIP_TRY(hipMemcpyAsync(steps, g.out1.p, n * 4, hipMemcpyDeviceToHost, g.stream));
-    if (normals) HIP_TRY(hipMemcpyAsync(normals, g.out2.p, n * 24, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
+    if ((rc = interval_program(e, scene_id, &prog))) return rc;
+    Staged st(e);
+    const double* d_origins = st.in(g.in[0], origins, n * 24);
+    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
+    double* d_t = st.out(g.out[0], t, n * 8);
+    int32_t* d_steps = st.out(g.out[1], steps, n * 4);
+    double* d_normals = st.out(g.out[2], normals, n * 24);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_interval_march(prog, P, d_origins, d_dirs, n, d_t, d_steps, d_normals, g.stream));
+    return st.finish();
 }
 
 int rm_interval_render(const RmFrameDesc* d, const RmIntervalConfig* cfg, double* depth, uint8_t* hit, double* normal,
@@ -1865,50 +1898,30 @@ int rm_interval_render(const RmFrameDesc* d, const RmIntervalConfig* cfg, double
     if (rc) return rc;
     rm::IntervalParams P;
     if ((rc = interval_params(d->scene_id, cfg, &P))) return rc;
-    if (d->width <= 0 || d->height <= 0 || d->row0 < 0 || d->rows < 0 || d->row0 + d->rows > d->height)
-        return fail(RM_E_BAD_DIMS, "bad frame slice: %dx%d rows [%d,%d)", d->width, d->height, d->row0, d->row0 + d->rows);
-    if ((long long)d->width * d->height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "frame too large");
-    if (timing && (timing->repeats < 1 || timing->repeats > RM_MAX_TIMED || timing->warmup < 0))
-        return fail(RM_E_BAD_ARG, "timing: repeats must be 1..%d, warmup >= 0", RM_MAX_TIMED);
-    if ((rc = check_ready())) return rc;
+    if ((rc = check_slice(d, false))) return rc;       // not check_desc: most of its fields mean nothing here
+    if (timing && (rc = check_timing(timing))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
     const size_t n = (size_t)d->width * (size_t)d->rows;
     if (n == 0) return RM_OK;
     if (!depth || !hit) return fail(RM_E_BAD_ARG, "depth and hit are required");
-    std::lock_guard<std::mutex> lk(g_mu);
-    HIP_TRY(hipSetDevice(g.device));
     const void* prog = nullptr;
-    if ((rc = interval_program(d->scene_id, &prog))) return rc;
-    if ((rc = g.out0.ensure(n * 8)) || (rc = g.out1.ensure(n)) || (normal && (rc = g.out2.ensure(n * 24))) ||
-        (steps && (rc = g.out3.ensure(n * 4))))
-        return rc;
+    if ((rc = interval_program(e, d->scene_id, &prog))) return rc;
+    Staged st(e);
+    double* d_depth = st.out(g.out[0], depth, n * 8);
+    uint8_t* d_hit = st.out(g.out[1], hit, n);
+    double* d_normal = st.out(g.out[2], normal, n * 24);
+    int32_t* d_steps = st.out(g.out[3], steps, n * 4);
+    if ((rc = st.begin())) return rc;
     rm::CameraParams cam;
     for (int i = 0; i < 14; ++i) cam.v[i] = d->cam[i];
-    auto go = [&]() -> hipError_t {
-        return rm::launch_interval_render(prog, P, cam, d->width, d->height, d->row0, d->rows, (double*)g.out0.p,
-                                          (uint8_t*)g.out1.p, normal ? (double*)g.out2.p : nullptr,
-                                          steps ? (int32_t*)g.out3.p : nullptr, g.stream);
+    auto go = [&] {
+        HIP_TRY(rm::launch_interval_render(prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_normal, d_steps, g.stream));
+        return (int)RM_OK;
     };
-    if (timing) {
-        if ((rc = ensure_events())) return rc;
-        for (int i = 0; i < timing->warmup; ++i) HIP_TRY(go());
-        for (int i = 0; i < timing->repeats; ++i) {
-            HIP_TRY(hipEventRecord(g.ev[2 * i], g.stream));
-            HIP_TRY(go());
-            HIP_TRY(hipEventRecord(g.ev[2 * i + 1], g.stream));
-        }
-    } else {
-        HIP_TRY(go());
-    }
-    HIP_TRY(hipMemcpyAsync(depth, g.out0.p, n * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(hit, g.out1.p, n, hipMemcpyDeviceToHost, g.stream));
-    if (normal) HIP_TRY(hipMemcpyAsync(normal, g.out2.p, n * 24, hipMemcpyDeviceToHost, g.stream));
-    if (steps) HIP_TRY(hipMemcpyAsync(steps, g.out3.p, n * 4, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    if (timing) {
-        for (int i = 0; i < timing->repeats; ++i) HIP_TRY(hipEventElapsedTime(&timing->ms_each[i], g.ev[2 * i], g.ev[2 * i + 1]));
-        summarise(timing);
-    }
-    return RM_OK;
+    // (a timed call waits twice: timed() before it reads its events, finish() for the maps)
+    if ((rc = timing ? timed(e, timing, g.stream, go) : go())) return rc;
+    return st.finish();
 }
 
 }  // extern "C"
