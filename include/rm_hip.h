@@ -170,7 +170,7 @@ typedef struct RmFrameDesc {
      *   team_retry       evaluations between two looks of a team that still carries rays
      *   age_priority     accepted and ignored by this build (an experiment: waves raising their issue priority with the
      *                    trip count of their oldest ray measured no gain on any scene and cost the cheap scenes 6-8 %;
-     *                    rm::kAgePriority in csrc/rm_kernels.h builds it) */
+     *                    the note above KernelArgs in csrc/rm_kernels.h records it) */
     int32_t pipeline;
     int32_t team_grid;
     int32_t queue_first;

@@ -460,10 +460,10 @@ rm::LaunchPlan plan_for(const RmFrameDesc* d, int batch_frames = 0, const RmMarc
     f.has_teams = sc->has_teams;
     f.has_resume_team = sc->resume_team != nullptr;
     f.entry_bytes = sc->entry_bytes(strategy);
-    f.per_cu = [sc, strategy](rm::OccKernel k, int tile_h, int interleave, int batch) {
+    f.per_cu = [sc, strategy](rm::OccKernel k, int /*tile_h: both queries answer for 64x4 tiles*/, int interleave, int batch) {
         int n = 0;
         const hipError_t e = k == rm::OccKernel::pipeline ? sc->occupancy_pipeline(strategy, interleave, batch, &n)
-                                                          : sc->occupancy(strategy, tile_h, interleave, batch, &n);
+                                                          : sc->occupancy(strategy, interleave, batch, &n);
         return e == hipSuccess ? n : 0;
     };
     return rm::plan_launch(*d, f, batch_frames, configs);
@@ -747,7 +747,7 @@ int launch_frame(const RmFrameDesc* d, const rm::LaunchPlan& p, rm::KernelArgs a
         g.last_was_pipeline = true;
         g.last_stats = a.stats;
     } else {
-        HIP_TRY(sc->render(d->strategy_id, p.tile_h, a, p.render_grid, s));
+        HIP_TRY(sc->render(d->strategy_id, a, p.render_grid, s));
         if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
     }
     if (p.park[0] > 0 && !p.single) {

@@ -101,11 +101,11 @@ __device__ __forceinline__ void pin_cfg(MarchCfg& c)
     pin_lane(p.step_scale); pin_lane(p.dense_min_step);
 }
 
-// Issue priority by ray age (RmFrameDesc.age_priority): built only when this is true.  Measured on the MI355X: no gain on
-// any scene (Sphere 0.47 ms, Cube 0.23, Mandelbulb 10.0-10.6 ms with or without), and its per-turn bookkeeping cost the
-// cheap scenes' render kernel 15 % more scalar instructions and the scalar registers that kept its output pointers
-// resident (Cube +6 %, Pillar Forest +8 % kernel time) -- so the field is accepted and ignored.
-constexpr bool kAgePriority = false;
+// Issue priority by ray age (RmFrameDesc.age_priority, KernelArgs.age_prio: a producer wave raised its s_setprio level with
+// the trip count of its oldest ray) is no longer built.  Measured on the MI355X: no gain on any scene (Sphere 0.47 ms,
+// Cube 0.23, Mandelbulb 10.0-10.6 ms with or without), and its per-turn bookkeeping cost the cheap scenes' render kernel
+// 15 % more scalar instructions and the scalar registers that kept its output pointers resident (Cube +6 %, Pillar
+// Forest +8 % kernel time) -- so the field is accepted and ignored.
 
 struct KernelArgs {
     FrameParams single;          // the frame of a one-frame launch (travels in the kernel arguments)
@@ -153,7 +153,7 @@ struct KernelArgs {
     int32_t team_steal;         // teams take queue 0 entries while queue 1 is empty
     int32_t max_spins;          // polls after which a producer wave with nothing to do stops waiting for the others
     int32_t team_prio;          // s_setprio level of the team waves (0..3)
-    int32_t age_prio;           // > 0: a producer wave's issue priority = (trips of its oldest ray) / age_prio, capped at 2
+    int32_t age_prio;           // accepted and ignored (issue priority by ray age: see the note above KernelArgs)
     int32_t marks;              // single launch: waves leave device-clock marks in stats block 0 (rm_set_pass_timing); off in production
     int32_t early_handover;     // single launch: > 0 = a struck ray at this trip or later whose evaluation ran >= early_trips iterations
     int32_t early_trips;        // (Scene::eval_trips) goes to the teams at once
@@ -410,6 +410,24 @@ struct WaveAcc {
     }
 };
 
+// Band-cyclic row map: the image row of row y of the frame slice (band_rows == 0: identity)
+__device__ __forceinline__ int band_row(const KernelArgs& a, int y)
+{
+    return a.band_rows > 0 ? a.row0 + ((y / a.band_rows) * a.band_stride + a.band_offset) * a.band_rows + (y % a.band_rows)
+                           : a.row0 + y;
+}
+
+// Image coordinates of an output element (for the camera ray of a resumed ray).
+__device__ __forceinline__ void element_pixel(const KernelArgs& a, uint32_t gi, uint32_t& frame, int& x, int& gy)
+{
+    const uint32_t frame_elems = (uint32_t)a.rows * (uint32_t)a.width;
+    frame = gi / frame_elems;
+    const uint32_t pix = gi - frame * frame_elems;
+    const int y = (int)(pix / (uint32_t)a.width);
+    x = (int)(pix - (uint32_t)y * (uint32_t)a.width);
+    gy = band_row(a, y);
+}
+
 // Tile geometry (wave-uniform): frame, origin inside the frame slice, valid extent, image row of its
 // first row, element offset of the frame in the frame-major output arrays.
 struct TileGeom {
@@ -428,9 +446,7 @@ __device__ __forceinline__ TileGeom tile_geom(const KernelArgs& a, int tile)
     g.y0 = ty * TILE_H;                                   // relative to row0
     g.tw = min(kTileW, a.width - g.x0);                   // pixels of this tile that exist in the slice
     g.th = min(TILE_H, a.rows - g.y0);
-    g.gy0 = a.band_rows > 0                               // tiles never straddle a band
-        ? a.row0 + ((g.y0 / a.band_rows) * a.band_stride + a.band_offset) * a.band_rows + (g.y0 % a.band_rows)
-        : a.row0 + g.y0;
+    g.gy0 = band_row(a, g.y0);                            // tiles never straddle a band
     return g;
 }
 
@@ -505,8 +521,6 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void render_kernel(const Kerne
     // wave-uniform: the scheduler (flush + refill) has something to look at -- a ray finished, a
     // refill handed out pixels or opened a tile.  Otherwise a turn goes straight to the SDF.
     bool dirty = true;
-    int prio_level = 0;                           // current s_setprio level of this wave (age_prio)
-    int since_sched = 0;                          // turns since the scheduler last ran
 
     for (;;) {
         if (dirty) {
@@ -649,21 +663,6 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void render_kernel(const Kerne
                 dirty = true;
             }
         }
-        // issue priority by age: a frame ends with its longest ray, and that ray's wave shares its SIMD with waves full
-        // of short rays for most of the frame.  A wave raises its priority with the trip count of its oldest ray
-        // (throughput-neutral: the other waves get the slots a dependent chain leaves free anyway).
-        if (kAgePriority && a.age_prio > 0) {
-            int age = active ? s.i : 0;
-            for (int off = 32; off > 0; off >>= 1) age = max(age, __shfl_xor(age, off));
-            const int lvl = age / a.age_prio;
-            if (lvl != prio_level) {
-                prio_level = lvl;
-                if (lvl <= 0) __builtin_amdgcn_s_setprio(0);
-                else if (lvl == 1) __builtin_amdgcn_s_setprio(1);
-                else if (lvl == 2) __builtin_amdgcn_s_setprio(2);
-                else __builtin_amdgcn_s_setprio(3);
-            }
-        }
         }   // dirty
 
         // ---- 3. exit / idle turn ---------------------------------------------------------------------
@@ -716,8 +715,6 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void render_kernel(const Kerne
             dirty = dirty || nidle_now >= a.refill_min;
         }
         }
-        // with age priority on, the scheduler also runs every 16 turns so an ageing ray is noticed without a finish
-        if (kAgePriority && a.age_prio > 0 && ++since_sched >= 16) { since_sched = 0; dirty = true; }
         if constexpr (INTERLEAVE) {
             if (active && !ready) ready = Scene::trip(ev);
         }
@@ -802,9 +799,7 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void resume_kernel(const Kerne
                     const uint32_t pix = my_gi - frame * frame_elems;
                     const int y = (int)(pix / (uint32_t)a.width);
                     const int x = (int)(pix - (uint32_t)y * (uint32_t)a.width);
-                    const int gy = a.band_rows > 0
-                        ? a.row0 + ((y / a.band_rows) * a.band_stride + a.band_offset) * a.band_rows + (y % a.band_rows)
-                        : a.row0 + y;
+                    const int gy = band_row(a, y);
                     // the camera ray is recomputed: same bits as in the first pass
                     if constexpr (BATCH) {
                         const FrameParams& fp = a.frames[frame];
@@ -848,6 +843,8 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void resume_kernel(const Kerne
                         const uint32_t frame = my_gi / frame_elems;
                         const uint32_t pix = my_gi - frame * frame_elems;
                         const uint32_t y = pix / (uint32_t)a.width, x = pix - y * (uint32_t)a.width;
+                        // 4 = a.tile_h here: this kernel runs in the launch-per-pass frames only, and the launch plan sets one-row
+                        // tiles for the single launch alone (plan_launch: p.single; tile_rows = 1 is refused elsewhere)
                         atomicMax(&a.tile_cost[frame * (uint32_t)a.tiles_per_frame + (y / 4u) * (uint32_t)a.tiles_x + (x >> 6)], it);
                     }
                 } else if (a.suspend_after > 0 && s.i >= a.suspend_after) {
@@ -954,8 +951,8 @@ struct ScenePartLoops : std::false_type {};
 template <class Scene>
 struct ScenePartLoops<Scene, decltype((void)Scene::kPartLoops)> : std::integral_constant<bool, Scene::kPartLoops> {};
 
-// The trips of one evaluation of every live ray (ready: the lane's value is ready).  `trip(part, go)` is team_trip or
-// team_trip_lds (rm_pipeline.h) bound to the team's exchange and barrier.  With per-part loops the part is dispatched
+// The trips of one evaluation of every live ray (ready: the lane's value is ready).  `trip(part, go)` is team_trip
+// bound to the team's exchange and barrier.  With per-part loops the part is dispatched
 // once, outside the trip loop, on a wave-uniform scalar: each wave's loop holds only its own part's chain, with no
 // branch on the part per trip.
 template <int P, class Trip>
@@ -1092,9 +1089,7 @@ __global__ __launch_bounds__(64 * kTeam) void resume_team_kernel(const KernelArg
                     const uint32_t pix = my_gi - frame * frame_elems;
                     const int y = (int)(pix / (uint32_t)a.width);
                     const int x = (int)(pix - (uint32_t)y * (uint32_t)a.width);
-                    const int gy = a.band_rows > 0
-                        ? a.row0 + ((y / a.band_rows) * a.band_stride + a.band_offset) * a.band_rows + (y % a.band_rows)
-                        : a.row0 + y;
+                    const int gy = band_row(a, y);
                     if constexpr (BATCH) {
                         const FrameParams& fp = a.frames[frame];
                         camera_ray(fp.cam, a.width, a.height, x, gy, origin, dir);
@@ -1136,6 +1131,7 @@ __global__ __launch_bounds__(64 * kTeam) void resume_team_kernel(const KernelArg
                     const uint32_t frame = my_gi / frame_elems;
                     const uint32_t pix = my_gi - frame * frame_elems;
                     const uint32_t y = pix / (uint32_t)a.width, x = pix - y * (uint32_t)a.width;
+                    // 4 = a.tile_h here, as in resume_kernel: launch-per-pass frames always have 64x4 tiles
                     atomicMax(&a.tile_cost[frame * (uint32_t)a.tiles_per_frame + (y / 4u) * (uint32_t)a.tiles_x + (x >> 6)], it);
                 }
             }
@@ -1176,14 +1172,14 @@ __global__ __launch_bounds__(64 * kTeam) void resume_team_kernel(const KernelArg
 
 // Per-scene launch table, filled by rm_scene_tu.hip (one translation unit per scene).
 struct SceneLaunchers {
-    hipError_t (*render)(int strategy, int tile_h, const KernelArgs& a, int grid, hipStream_t s);
+    hipError_t (*render)(int strategy, const KernelArgs& a, int grid, hipStream_t s);                    // 64x4 tiles
     hipError_t (*resume)(int strategy, int level, const KernelArgs& a, int grid, hipStream_t s);
     hipError_t (*resume_team)(int strategy, int level, const KernelArgs& a, int grid, hipStream_t s);   // nullptr: no team form
     hipError_t (*pipeline)(int strategy, const KernelArgs& a, int grid, hipStream_t s);                  // rm_pipeline.h (a.tile_h: 4, or 1 where has_teams)
     hipError_t (*occupancy_pipeline)(int strategy, int interleave, int batch, int* blocks_per_cu);
     bool has_teams;
     int (*entry_bytes)(int strategy);   // sizeof(QEntry<Strat>)
-    hipError_t (*occupancy)(int strategy, int tile_h, int interleave, int batch, int* blocks_per_cu);
+    hipError_t (*occupancy)(int strategy, int interleave, int batch, int* blocks_per_cu);      // of render
     // scene_data: KernelArgs.scene_data (nullptr for the catalogue scenes)
     hipError_t (*sdf_eval)(const double* xyz, size_t n, double* out, const void* scene_data, hipStream_t s);
     hipError_t (*march_rays)(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,

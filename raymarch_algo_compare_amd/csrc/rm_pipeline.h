@@ -227,18 +227,6 @@ __device__ __forceinline__ bool q_push(const KernelArgs& a, int q, bool want, ui
     return ok;
 }
 
-// Image coordinates of an output element (for the camera ray of a resumed ray).
-__device__ __forceinline__ void element_pixel(const KernelArgs& a, uint32_t gi, uint32_t& frame, int& x, int& gy)
-{
-    const uint32_t frame_elems = (uint32_t)a.rows * (uint32_t)a.width;
-    frame = gi / frame_elems;
-    const uint32_t pix = gi - frame * frame_elems;
-    const int y = (int)(pix / (uint32_t)a.width);
-    x = (int)(pix - (uint32_t)y * (uint32_t)a.width);
-    gy = a.band_rows > 0 ? a.row0 + ((y / a.band_rows) * a.band_stride + a.band_offset) * a.band_rows + (y % a.band_rows)
-                         : a.row0 + y;
-}
-
 // Workgroup shape of the pipeline kernel: kPipeWaves (rm_shape.h, with the rejected shapes and their figures).
 
 // Role-specific LDS of the pipeline kernel (one allocation: a workgroup has exactly one role).
@@ -255,26 +243,6 @@ struct PipeTeamLds {
     unsigned int base, count, queue, done;
     unsigned int ok_lo, ok_hi;            // lanes whose popped entry was published in time (part 0 polls for the team)
 };
-
-// team_trip (rm_kernels.h) with the exchange in the team's LDS block
-template <class Scene, class PartT>
-__device__ __forceinline__ bool team_trip_lds(typename Scene::Eval& ev, bool go, PartT part, int lane, PipeTeamLds& L, int& turn)
-{
-    double o0 = 0.0, o1 = 0.0;
-    if constexpr (std::is_same<PartT, int>::value) {
-        if (go) Scene::trip_part(ev, part, o0, o1);
-    } else {
-        if (go) Scene::template trip_part<PartT::value>(ev, o0, o1);
-    }
-    double (*buf)[64] = L.xch.v[turn & 1];
-    ++turn;
-    buf[2 * (int)part][lane] = o0;
-    buf[2 * (int)part + 1][lane] = o1;
-    __syncthreads();
-    bool done = true;
-    if (go) done = Scene::trip_join(ev, buf[0][lane], buf[1][lane], buf[2][lane], buf[3][lane], buf[4][lane], buf[5][lane]);
-    return done;
-}
 
 // A finished ray whose result goes straight to the maps (a ray that was parked at least once).
 __device__ __forceinline__ void store_direct(const KernelArgs& a, uint32_t gi, const Result& r, int nev, WaveAcc& acc,
@@ -468,7 +436,7 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
             ++since_try;
             bool ready = true;
             if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-            team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip_lds<Scene>(ev, go, P, lane, L, turn); });
+            team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, L.xch, turn); });
             const int live = a.trace ? __popcll(__ballot(active)) : 0;
             if (active) {
                 ++nev;
@@ -555,7 +523,6 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     bool fresh_reported = false;                  // wave-uniform: this wave has reported the end of its fresh work
     int spins = 0;                                // polls of an empty queue 0 with nothing else to do
     int since_look = 0;                           // turns since the scheduler last ran
-    int prio_level = 0;                           // current s_setprio level of this wave (age_prio)
 
     for (;;) {
         if (dirty) {
@@ -767,20 +734,6 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
                 for (int k = 0; k < kSlots; ++k) slot_out[k] += (k == cur) ? nstarted : 0;
                 pool_next += nidle;
                 dirty = true;
-            }
-        }
-
-        // ---- 2a. issue priority by age: a wave that carries an old ray (a candidate for the frame's longest chain)
-        // wins the arbitration against the wave it shares its SIMD with; throughput-neutral among producers
-        if (kAgePriority && a.age_prio > 0) {
-            int age = active ? s.i : 0;
-            for (int off = 32; off > 0; off >>= 1) age = max(age, __shfl_xor(age, off));
-            const int lvl = age / a.age_prio;
-            if (lvl != prio_level) {
-                prio_level = lvl;
-                if (lvl <= 0) __builtin_amdgcn_s_setprio(0);
-                else if (lvl == 1) __builtin_amdgcn_s_setprio(1);
-                else __builtin_amdgcn_s_setprio(2);
             }
         }
 

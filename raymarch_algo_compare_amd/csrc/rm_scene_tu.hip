@@ -28,232 +28,175 @@ using SceneT = SceneById<RM_SCENE_ID>::type;
 
 constexpr bool kIter = SceneIterative<SceneT>::value;
 
-template <class Strat, int TH>
-static hipError_t launch_render(const KernelArgs& a, int grid, hipStream_t s)
-{
-    const bool il = kIter && a.interleave;
-    if (a.frames) {
-        if (il) hipLaunchKernelGGL((render_kernel<SceneT, Strat, TH, kIter, true>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a);
-        else hipLaunchKernelGGL((render_kernel<SceneT, Strat, TH, false, true>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a);
-    } else {
-        if (il) hipLaunchKernelGGL((render_kernel<SceneT, Strat, TH, kIter, false>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a);
-        else hipLaunchKernelGGL((render_kernel<SceneT, Strat, TH, false, false>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a);
-    }
-    return hipGetLastError();
-}
+// ---- choosing an instantiation: written once per kernel family, as the kernel's address.  A launch and the occupancy
+// query that sizes its grid go through the same function, so they cannot name different instantiations.
+template <class S> struct Tag { using type = S; };
 
-template <class Strat>
-static hipError_t launch_resume(int level, const KernelArgs& a, int grid, hipStream_t s)
-{
-    const bool il = kIter && a.interleave;
-    if (a.frames) {
-        if (il) hipLaunchKernelGGL((resume_kernel<SceneT, Strat, kIter, true>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a, level);
-        else hipLaunchKernelGGL((resume_kernel<SceneT, Strat, false, true>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a, level);
-    } else {
-        if (il) hipLaunchKernelGGL((resume_kernel<SceneT, Strat, kIter, false>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a, level);
-        else hipLaunchKernelGGL((resume_kernel<SceneT, Strat, false, false>), dim3(grid), dim3(64 * kWavesPerWG), 0, s, a, level);
-    }
-    return hipGetLastError();
-}
-
-template <class Strat, int TH>
-static hipError_t occ_render(int interleave, int batch, int* blocks)
-{
-    const bool il = kIter && interleave;
-    if (batch) {
-        if (il) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, render_kernel<SceneT, Strat, TH, kIter, true>, 64 * kWavesPerWG, 0);
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, render_kernel<SceneT, Strat, TH, false, true>, 64 * kWavesPerWG, 0);
-    }
-    if (il) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, render_kernel<SceneT, Strat, TH, kIter, false>, 64 * kWavesPerWG, 0);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, render_kernel<SceneT, Strat, TH, false, false>, 64 * kWavesPerWG, 0);
-}
-
-#if !defined(RM_SCENE_PROGRAM)
-// One-row tiles (TILE_H = 1) are built for the scenes with a team form only: there a frame ends with its longest
-// ray, and with 64x4 tiles that ray may sit in its tile's pixel pool for milliseconds behind lanes that older rays hold.
-template <class Strat, int TH>
-static hipError_t launch_pipeline_th(const KernelArgs& a, int grid, hipStream_t s)
-{
-    const bool il = kIter && a.interleave;
-    const dim3 g(grid), b(64 * kPipeWaves);
-    if (a.frames) {
-        if (il) hipLaunchKernelGGL((pipeline_kernel<SceneT, Strat, TH, kIter, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((pipeline_kernel<SceneT, Strat, TH, false, true>), g, b, 0, s, a);
-    } else {
-        if (il) hipLaunchKernelGGL((pipeline_kernel<SceneT, Strat, TH, kIter, false>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((pipeline_kernel<SceneT, Strat, TH, false, false>), g, b, 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-template <class Strat>
-static hipError_t launch_pipeline(const KernelArgs& a, int grid, hipStream_t s)
-{
-    if constexpr (kIter) {
-        if (a.tile_h == 1) return launch_pipeline_th<Strat, 1>(a, grid, s);
-    }
-    if (a.tile_h != 4) return hipErrorInvalidValue;
-    return launch_pipeline_th<Strat, 4>(a, grid, s);
-}
-
-template <class Strat>
-static hipError_t occ_pipeline(int interleave, int batch, int* blocks)
-{
-    const bool il = kIter && interleave;
-    if (batch) {
-        if (il) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, pipeline_kernel<SceneT, Strat, 4, kIter, true>, 64 * kPipeWaves, 0);
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, pipeline_kernel<SceneT, Strat, 4, false, true>, 64 * kPipeWaves, 0);
-    }
-    if (il) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, pipeline_kernel<SceneT, Strat, 4, kIter, false>, 64 * kPipeWaves, 0);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, pipeline_kernel<SceneT, Strat, 4, false, false>, 64 * kPipeWaves, 0);
-}
-
-static hipError_t pipeline(int strategy, const KernelArgs& a, int grid, hipStream_t s)
+// f(Tag<Strat>()) for the strategy with this id; `none` for an id this build has no kernels for
+template <class R, class F>
+static R with_strategy(int strategy, R none, F f)
 {
     switch (strategy) {
 #define RM_X(id, S) \
-    case id: return launch_pipeline<S>(a, grid, s);
+    case id: return f(Tag<S>());
         RM_STRATEGY_LIST(RM_X)
 #undef RM_X
     }
-    return hipErrorInvalidValue;
+    return none;
 }
 
-static hipError_t occupancy_pipeline(int strategy, int interleave, int batch, int* blocks)
+// f(INTERLEAVE, BATCH) as compile-time constants; a scene without a resumable SDF has no INTERLEAVE form
+template <class F>
+static auto with_mode(int interleave, int batch, F f)
 {
-    switch (strategy) {
-#define RM_X(id, S) \
-    case id: return occ_pipeline<S>(interleave, batch, blocks);
-        RM_STRATEGY_LIST(RM_X)
-#undef RM_X
-    }
-    return hipErrorInvalidValue;
+    using I = std::integral_constant<bool, kIter>;
+    using N = std::false_type;
+    if (batch) return kIter && interleave ? f(I(), std::true_type()) : f(N(), std::true_type());
+    return kIter && interleave ? f(I(), N()) : f(N(), N());
 }
 
-#endif  // !RM_SCENE_PROGRAM
+using FrameKernel = void (*)(KernelArgs);        // render_kernel, pipeline_kernel
+using PassKernel = void (*)(KernelArgs, int);    // resume_kernel, resume_team_kernel
 
-static hipError_t render(int strategy, int tile_h, const KernelArgs& a, int grid, hipStream_t s)
+static FrameKernel render_fn(int strategy, int interleave, int batch)      // 64x4 tiles always
 {
-    switch (strategy) {
-#define RM_X(id, S) \
-    case id: return launch_render<S, 4>(a, grid, s);
-        RM_STRATEGY_LIST(RM_X)
-#undef RM_X
-    }
-    return hipErrorInvalidValue;
+    return with_strategy(strategy, FrameKernel(), [&](auto t) {
+        using S = typename decltype(t)::type;
+        return with_mode(interleave, batch, [](auto il, auto b) -> FrameKernel { return render_kernel<SceneT, S, 4, il(), b()>; });
+    });
+}
+
+static PassKernel resume_fn(int strategy, int interleave, int batch)
+{
+    return with_strategy(strategy, PassKernel(), [&](auto t) {
+        using S = typename decltype(t)::type;
+        return with_mode(interleave, batch, [](auto il, auto b) -> PassKernel { return resume_kernel<SceneT, S, il(), b()>; });
+    });
+}
+
+static PassKernel resume_team_fn(int strategy, int batch)      // nullptr: the scene has no team form
+{
+    return with_strategy(strategy, PassKernel(), [&](auto t) -> PassKernel {
+        using S = typename decltype(t)::type;
+        if constexpr (kIter) return batch ? resume_team_kernel<SceneT, S, true> : resume_team_kernel<SceneT, S, false>;
+        return nullptr;
+    });
+}
+
+template <class K, class... A>
+static hipError_t launch(K kernel, int grid, int block, hipStream_t s, const A&... args)
+{
+    if (!kernel) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, args...);
+    return hipGetLastError();
+}
+
+template <class K>
+static hipError_t blocks_per_cu(K kernel, int block, int* blocks)
+{
+    if (!kernel) return hipErrorInvalidValue;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kernel, block, 0);
+}
+
+static hipError_t render(int strategy, const KernelArgs& a, int grid, hipStream_t s)
+{
+    return launch(render_fn(strategy, a.interleave, a.frames != nullptr), grid, 64 * kWavesPerWG, s, a);
+}
+
+static hipError_t occupancy(int strategy, int interleave, int batch, int* blocks)
+{
+    return blocks_per_cu(render_fn(strategy, interleave, batch), 64 * kWavesPerWG, blocks);
 }
 
 static hipError_t resume(int strategy, int level, const KernelArgs& a, int grid, hipStream_t s)
 {
-    switch (strategy) {
-#define RM_X(id, S) \
-    case id: return launch_resume<S>(level, a, grid, s);
-        RM_STRATEGY_LIST(RM_X)
-#undef RM_X
-    }
-    return hipErrorInvalidValue;
+    return launch(resume_fn(strategy, a.interleave, a.frames != nullptr), grid, 64 * kWavesPerWG, s, a, level);
 }
 
-template <bool ITER>
-static hipError_t resume_team_impl(int strategy, int level, const KernelArgs& a, int grid, hipStream_t s)
+static hipError_t resume_team(int strategy, int level, const KernelArgs& a, int grid, hipStream_t s)
 {
-    if constexpr (ITER) {
-        switch (strategy) {
-#define RM_X(id, S)                                                                                              \
-    case id:                                                                                                     \
-        if (a.frames) hipLaunchKernelGGL((resume_team_kernel<SceneT, S, true>), dim3(grid), dim3(64 * kTeam), 0, s, a, level);   \
-        else hipLaunchKernelGGL((resume_team_kernel<SceneT, S, false>), dim3(grid), dim3(64 * kTeam), 0, s, a, level);           \
-        return hipGetLastError();
-            RM_STRATEGY_LIST(RM_X)
-#undef RM_X
-        }
-    }
-    return hipErrorInvalidValue;
+    return launch(resume_team_fn(strategy, a.frames != nullptr), grid, 64 * kTeam, s, a, level);
 }
+
+#if defined(RM_SCENE_PROGRAM)
+#define RM_PIPELINE_FNS nullptr, nullptr
+#else
+#define RM_PIPELINE_FNS pipeline, occupancy_pipeline
+// One-row tiles (TILE_H = 1) are built for the scenes with a team form only: there a frame ends with its longest
+// ray, and with 64x4 tiles that ray may sit in its tile's pixel pool for milliseconds behind lanes that older rays hold.
+static FrameKernel pipeline_fn(int strategy, int tile_h, int interleave, int batch)
+{
+    return with_strategy(strategy, FrameKernel(), [&](auto t) -> FrameKernel {
+        using S = typename decltype(t)::type;
+        if constexpr (kIter) {
+            if (tile_h == 1)
+                return with_mode(interleave, batch, [](auto il, auto b) -> FrameKernel { return pipeline_kernel<SceneT, S, 1, il(), b()>; });
+        }
+        if (tile_h != 4) return nullptr;
+        return with_mode(interleave, batch, [](auto il, auto b) -> FrameKernel { return pipeline_kernel<SceneT, S, 4, il(), b()>; });
+    });
+}
+
+static hipError_t pipeline(int strategy, const KernelArgs& a, int grid, hipStream_t s)
+{
+    return launch(pipeline_fn(strategy, a.tile_h, a.interleave, a.frames != nullptr), grid, 64 * kPipeWaves, s, a);
+}
+
+static hipError_t occupancy_pipeline(int strategy, int interleave, int batch, int* blocks)
+{
+    // the TILE_H = 4 instantiation is asked about for one-row launches too: the grids the launch plan computes rest on it
+    return blocks_per_cu(pipeline_fn(strategy, 4, interleave, batch), 64 * kPipeWaves, blocks);
+}
+#endif
 
 static int entry_bytes(int strategy)
 {
-    switch (strategy) {
-#define RM_X(id, S) \
-    case id: return (int)sizeof(QEntry<S>);
-        RM_STRATEGY_LIST(RM_X)
-#undef RM_X
-    }
-    return 0;
-}
-
-static hipError_t occupancy(int strategy, int tile_h, int interleave, int batch, int* blocks)
-{
-    switch (strategy) {
-#define RM_X(id, S) \
-    case id: return occ_render<S, 4>(interleave, batch, blocks);
-        RM_STRATEGY_LIST(RM_X)
-#undef RM_X
-    }
-    return hipErrorInvalidValue;
+    return with_strategy(strategy, 0, [](auto t) { return (int)sizeof(QEntry<typename decltype(t)::type>); });
 }
 
 static hipError_t sdf_eval(const double* xyz, size_t n, double* out, const void* scene_data, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL((sdf_eval_kernel<SceneT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xyz, n, out, scene_data);
-    return hipGetLastError();
+    return launch(sdf_eval_kernel<SceneT>, (int)((n + 255) / 256), 256, s, xyz, n, out, scene_data);
 }
 
 static hipError_t march_rays(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,
                              uint8_t* hit, double* t, int32_t* iters, double* fs, const void* scene_data, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
-    dim3 grid((unsigned)((n + 63) / 64)), block(64);
-    switch (strategy) {
-#define RM_X(id, S)                                                                                        \
-    case id:                                                                                               \
-        hipLaunchKernelGGL((march_rays_kernel<SceneT, S>), grid, block, 0, s, cfg, o, d, n, hit, t, iters, fs, scene_data); \
-        return hipGetLastError();
-        RM_STRATEGY_LIST(RM_X)
-#undef RM_X
-    }
-    return hipErrorInvalidValue;
+    return with_strategy(strategy, hipErrorInvalidValue, [&](auto tag) {
+        return launch(march_rays_kernel<SceneT, typename decltype(tag)::type>, (int)((n + 63) / 64), 64, s, cfg, o, d, n, hit, t, iters, fs, scene_data);
+    });
 }
 
-template <bool ITER>
-static hipError_t march_rays_team_impl(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,
-                                       uint8_t* hit, double* t, int32_t* iters, double* fs, unsigned long long* busy, int fillers,
-                                       hipStream_t s)
+static hipError_t march_rays_team(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,
+                                  uint8_t* hit, double* t, int32_t* iters, double* fs, unsigned long long* busy, int fillers,
+                                  hipStream_t s)
 {
-    if constexpr (ITER) {
-        if (n == 0) return hipSuccess;
-        dim3 grid((unsigned)((n + 63) / 64) + (unsigned)(busy ? fillers : 0)), block(64 * kTeam);
-        switch (strategy) {
-#define RM_X(id, S)                                                                                             \
-    case id:                                                                                                    \
-        hipLaunchKernelGGL((march_rays_team_kernel<SceneT, S>), grid, block, 0, s, cfg, o, d, n, hit, t, iters, fs, busy); \
-        return hipGetLastError();
-            RM_STRATEGY_LIST(RM_X)
-#undef RM_X
+    if (kIter && n == 0) return hipSuccess;
+    return with_strategy(strategy, hipErrorInvalidValue, [&](auto tag) {
+        if constexpr (kIter) {
+            const int grid = (int)((unsigned)((n + 63) / 64) + (unsigned)(busy ? fillers : 0));
+            return launch(march_rays_team_kernel<SceneT, typename decltype(tag)::type>, grid, 64 * kTeam, s, cfg, o, d, n, hit, t, iters, fs, busy);
         }
-    }
-    return hipErrorInvalidValue;
+        return hipErrorInvalidValue;
+    });
 }
 
 #if defined(RM_SCENE_PROGRAM)
 static_assert(!kIter, "a scene program has no resumable evaluation");
-const SceneLaunchers* scene_launchers_program()
-{
-    static const SceneLaunchers l = { render, resume, nullptr, nullptr, nullptr, false,
-                                      entry_bytes, occupancy, sdf_eval, march_rays, nullptr };
-    return &l;
-}
+#define RM_LAUNCHERS_FN scene_launchers_program
 #else
 #define RM_CAT2(a, b) a##b
 #define RM_CAT(a, b) RM_CAT2(a, b)
+#define RM_LAUNCHERS_FN RM_CAT(scene_launchers_, RM_SCENE_ID)
+#endif
 // a host function (not a const global: hipcc would try to emit that for the device too)
-const SceneLaunchers* RM_CAT(scene_launchers_, RM_SCENE_ID)()
+const SceneLaunchers* RM_LAUNCHERS_FN()
 {
-    static const SceneLaunchers l = { render, resume, kIter ? resume_team_impl<kIter> : nullptr, pipeline, occupancy_pipeline, kIter,
-                                      entry_bytes, occupancy, sdf_eval, march_rays, kIter ? march_rays_team_impl<kIter> : nullptr };
+    static const SceneLaunchers l = { render, resume, kIter ? resume_team : nullptr, RM_PIPELINE_FNS, kIter,
+                                      entry_bytes, occupancy, sdf_eval, march_rays, kIter ? march_rays_team : nullptr };
     return &l;
 }
-#endif
 
 }  // namespace rm
