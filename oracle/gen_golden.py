@@ -19,7 +19,10 @@ Layout of each frames_*.npz (keys prefixed "s{scene_id}_k{strategy_id}_"):
   cam     float64 (14,)       position, forward, right, up, half_width, half_height
   meta    float64 (8,)        W, H, row0, rows, max_iterations, hit_threshold, max_distance, lipschitz
 
-Usage:  python oracle/gen_golden.py [--only frames64|frames160|rows1080|sdf|stats|leak|leakseq|params|schema|viewpoints|evals|analytic]
+frames_config_<family>.npz and rays_config.npz (--only config, --only rays) are laid out differently: see the
+comment above CONFIG_SEED.
+
+Usage:  python oracle/gen_golden.py [--only frames64|frames160|rows1080|sdf|stats|leak|leakseq|params|schema|viewpoints|evals|analytic|config|rays]
 """
 from __future__ import annotations
 
@@ -373,9 +376,437 @@ def gen_viewpoints():
     print("viewpoints.json:", sum(len(v) for v in out.values()), "viewpoints of", len(out), "scenes")
 
 
+# ---- off-default march configurations, cameras, shapes and explicit rays --------------------------------------
+# frames_config_<family>.npz hold the fields of frames_params_48x36.npz (ids, prm, meta, cam, iters, hitbits, sha_t,
+# sha_fs) for some two thousand small frames.  They are stored BY COLUMN -- one array per field, one row per case --
+# because a key per case and field costs about 200 bytes of zip directory and .npy header, twice the payload of such
+# a frame.  Per file, N cases:
+#   ids (N,2) int32 scene, strategy     prm (N,16) RmStrategyParams order     meta (N,8) as in pack()
+#   cam (N,14) the reference camera's basis     view (N,10) its arguments: position, target, up, fov_degrees
+#   iters int16, all frames concatenated row-major; off (N+1,) int64 ray offsets     hitbits uint8 packbits of all hits
+#   sha_t, sha_fs (N,32)   sha_depth32 (N,32): sha256 of float32(t if hit else 0.0), the depth map of core/types.py:93
+#   t_bits (N,64) uint64: the bits of t of the first 64 rays (0-padded), to locate a mismatch the hashes only detect
+#   refstats (N,6) int64: total_rays, hit_count, miss_count, sample_count, iteration_min, iteration_max of the
+#                         reference's RayMarchStats for whole frames of family D, -1 elsewhere
+#   tag (N,) the generator's label of the case (family, sub-family, level), for the coverage test and for messages
+# Everything is seeded by CONFIG_SEED; archives are written with fixed timestamps, so a rerun is byte-identical.
+CONFIG_SEED = 20261016
+HEAVY_SCENES = (9, 10, 15, 16)          # Menger, Mandelbulb, Bumpy Sphere, Gyroid: slow in pure Python
+FRACTAL_SCENES = (9, 10)
+BUDGET_EDGES = (0, 1, 2, 3, 15, 16, 17, 18)
+FAMILIES = ("A", "B", "C", "D", "E")
+# which RmStrategyParams a constructor argument is (PARAM_CASES spells the same pairs out by hand)
+CTOR_TO_PRM = {1: dict(omega="omega"),
+               2: dict(omega_min="ar_omega_min", omega_max="ar_omega_max", smoothing="ar_smoothing",
+                       growth_rate="ar_growth_rate", decay_rate="ar_decay_rate"),
+               3: dict(beta="beta"),
+               6: dict(min_step_factor="overstep_min_step", bisection_steps="overstep_bisection_steps"),
+               9: dict(stuck_threshold="hybrid_stuck_threshold", stuck_step_ratio="hybrid_stuck_step_ratio",
+                       min_step_factor="hybrid_min_step")}
+# the march() literal with_literal can swap per strategy: (its value in the reference, the RmStrategyParams field)
+LITERAL_OF = {7: (0.05, "margin"), 2: (1.2, "ar_omega_init"), 10: (8, "segment_bisection_steps"), 8: (8, "revaa_bisection_steps")}
+
+
+def save_npz(path, store):
+    """np.savez_compressed with fixed member timestamps (numpy stamps the wall clock), so reruns are byte-identical."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, v in store.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            zf.writestr(zi, buf.getvalue())
+
+
+def default_view(scene):
+    """(position, target, up, fov) as run_once finds them: the scene's suggestion or RenderConfig's defaults."""
+    rc = scene.suggested_camera() or RenderConfig()
+    return (tuple(rc.camera_position), tuple(rc.camera_target), tuple(rc.camera_up), float(rc.fov_degrees))
+
+
+def spec(tag, sid, kid, view, W, H, row0=0, rows=None, mi=512, thr=1e-4, far=100.0, lip=None, ctor=None, lit=None, stats=False):
+    """One case.  lip None: main.py's wiring (the scene's bound if it has one); lit: new value of LITERAL_OF[kid]."""
+    pos, tgt, up, fov = view
+    return dict(tag=tag, sid=sid, kid=kid, view=[*map(float, pos), *map(float, tgt), *map(float, up), float(fov)], W=W, H=H,
+                row0=row0, rows=H - row0 if rows is None else rows, mi=int(mi), thr=float(thr), far=float(far), lip=lip,
+                ctor=dict(ctor or {}), lit=lit, stats=stats)
+
+
+def build_strategy(scene, kid, ctor, lit, lip):
+    cls = STRATEGIES[STRAT_KEYS[kid]]
+    overrides = {CTOR_TO_PRM[kid][k]: v for k, v in ctor.items()}
+    if lit is not None:
+        old, field_name = LITERAL_OF[kid]
+        if lit != old:
+            cls = with_literal(cls, old, lit)
+        overrides[field_name] = lit
+    strategy = cls(**ctor)
+    lipschitz = 1.0
+    if hasattr(strategy, "lipschitz"):                                     # main.py:58-61
+        if lip is None:
+            bound = scene.known_lipschitz_bound()
+            if bound is not None:
+                strategy.lipschitz = bound
+        else:
+            strategy.lipschitz = lip
+        lipschitz = float(strategy.lipschitz)
+    return strategy, lipschitz, overrides
+
+
+def run_spec(sp):
+    """Worker: march one case with the reference.  Returns the case's columns, or its description and the exception."""
+    try:
+        scene = SCENES[sp["sid"]]
+        strategy, lip, overrides = build_strategy(scene, sp["kid"], sp["ctor"], sp["lit"], sp["lip"])
+        v = sp["view"]
+        cam = Camera(position=Vec3(*v[0:3]), target=Vec3(*v[3:6]), up=Vec3(*v[6:9]), fov_degrees=v[9], width=sp["W"], height=sp["H"])
+        mc = MarchConfig(max_iterations=sp["mi"], hit_threshold=sp["thr"], max_distance=sp["far"])
+        res = march_rows(scene, strategy, cam, mc, sp["row0"], sp["rows"])
+        one = {}
+        pack("", res, cam, mc, lip, sp["row0"], sp["rows"], one)
+        hit = np.array([bool(r.hit) for r in res], dtype=bool)
+        t = np.array([float(r.t) for r in res], dtype="<f8")
+        one.pop("t_hit")
+        one["hit"] = hit
+        one["sha_depth32"] = np.frombuffer(hashlib.sha256(np.where(hit, t, 0.0).astype("<f4").tobytes()).digest(), dtype=np.uint8)
+        tb = np.zeros(64, dtype=np.uint64)
+        tb[:min(64, len(t))] = t[:64].view(np.uint64)
+        one["t_bits"] = tb
+        prm = dict(PARAM_DEFAULTS, **overrides)
+        one["prm"] = np.array([float(prm[k]) for k in PARAM_ORDER], dtype=np.float64)
+        one["refstats"] = np.full(6, -1, dtype=np.int64)
+        if sp["stats"] and sp["row0"] == 0 and sp["rows"] == sp["H"]:
+            s = stats_dict(scene, strategy, res, sp["W"], sp["H"])
+            one["refstats"] = np.array([s["total_rays"], s["hit_count"], s["miss_count"], s["sample_count"],
+                                        s["iteration_min"], s["iteration_max"]], dtype=np.int64)
+        return sp, one, None
+    except Exception as e:                                                  # noqa: BLE001 -- the reference refused the case
+        return sp, None, f"{type(e).__name__}: {e}"
+
+
+def _vp_views(sid):
+    from raymarching_benchmark.viewpoints import viewpoints_for
+    return [(v.name, (tuple(v.position), tuple(v.target), tuple(v.up), 60.0)) for v in viewpoints_for(SCENES[sid])]
+
+
+def sweep_levels():
+    """DEFAULT_BUDGETS, DEFAULT_EPSILONS and RESIDUAL_CAP of the reference's sweep.py (:48-55), read from its text: the module
+    imports moderngl (gpu/runner.py:3) and cannot be imported here."""
+    import ast
+    with open(os.path.join(REF, "raymarching_benchmark", "sweep.py"), encoding="utf-8") as f:
+        tree = ast.parse(f.read())
+    found = {n.targets[0].id: ast.literal_eval(n.value) for n in tree.body
+             if isinstance(n, ast.Assign) and isinstance(n.targets[0], ast.Name)
+             and n.targets[0].id in ("DEFAULT_BUDGETS", "DEFAULT_EPSILONS", "RESIDUAL_CAP")}
+    return found["DEFAULT_BUDGETS"], found["DEFAULT_EPSILONS"], found["RESIDUAL_CAP"]
+
+
+def family_a(W=16, H=12):
+    """The sweep's grid (sweep.py:48-55, :222-240): every level of both axes, from the curated viewpoints, fov 60.  A group
+    is one (scene, viewpoint, strategy) with all levels of one axis -- what the sweep renders in one go."""
+    DEFAULT_BUDGETS, DEFAULT_EPSILONS, RESIDUAL_CAP = sweep_levels()
+    axes = {"budget": [(b, 1e-4) for b in DEFAULT_BUDGETS], "eps512": [(512, e) for e in DEFAULT_EPSILONS],
+            "eps2048": [(RESIDUAL_CAP, e) for e in DEFAULT_EPSILONS]}
+    entries = [(sid, name, view) for sid in range(len(SCENES)) if sid != 10 for name, view in _vp_views(sid)]
+    used = {(e[0], e[1]): 0 for e in entries}
+    mandel = _vp_views(10)
+    out, g, m = [], 0, 0
+    for kid in range(len(STRAT_KEYS)):
+        for axis, levels in axes.items():
+            chosen = []
+            if axis != "eps2048":                                              # Mandelbulb: every strategy, both axes at 512
+                name, view = mandel[m % len(mandel)]
+                m += 1
+                chosen.append((10, name, view))
+            while len(chosen) < 3:
+                # least-used eligible viewpoint of a scene this (strategy, axis) does not have yet; the 2048 cap stays off the
+                # fractals (as the issue asks) and off the other slow scenes, which the two other axes therefore take first
+                ok = [e for e in entries if e[0] not in [c[0] for c in chosen]
+                      and not (axis == "eps2048" and e[0] in HEAVY_SCENES)]
+                ok.sort(key=lambda e: (used[(e[0], e[1])], 0 if (axis != "eps2048" and e[0] in HEAVY_SCENES) else 1))
+                chosen.append(ok[0])
+                used[(ok[0][0], ok[0][1])] += 1
+            for sid, name, view in chosen:
+                for mi, thr in levels:
+                    out.append(spec(f"A/{axis}/g{g}/{name}", sid, kid, view, W, H, mi=mi, thr=thr))
+                g += 1
+    assert all(n > 0 for n in used.values()), [k for k, n in used.items() if not n]
+    return out
+
+
+def family_b(W=12, H=8):
+    """Budget edges: the empty loop, Overstep-Bisect's reserve (overstep_bisect.py:40-41), the bisection loops of Segment and
+    RevAA, and bisection counts of 0, 1, the budget and one more.  Plus the two frames test_edge_cases used to assert on."""
+    out = []
+    for sid in (0, 9, 10, 12):
+        view = default_view(SCENES[sid])
+        for kid in range(len(STRAT_KEYS)):
+            for b in BUDGET_EDGES:
+                out.append(spec(f"B/budget/{b}", sid, kid, view, W, H, mi=b))
+    for sid in (0, 9, 10):
+        view = default_view(SCENES[sid])
+        for kid in (6, 10, 8):
+            for b in BUDGET_EDGES:
+                for n in sorted({0, 1, b, b + 1}):
+                    kw = dict(ctor=dict(bisection_steps=n)) if kid == 6 else dict(lit=n)
+                    out.append(spec(f"B/steps/{b}/{n}", sid, kid, view, W, H, mi=b, **kw))
+    edge_view = ((0.0, 0.0, 5.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 60.0)
+    out.append(spec("B/edge/0", 0, 0, edge_view, 8, 4, mi=0))
+    out.append(spec("B/edge/10", 0, 6, edge_view, 8, 4, mi=10))
+    return out
+
+
+# constructor arguments and literals at both ends of their meaningful range: (strategy, ctor kwargs, literal)
+PARAM_ENDS = (
+    [(1, dict(omega=w), None) for w in (1.0, 2.5)] +
+    [(2, dict(omega_min=a, omega_max=b, smoothing=c, growth_rate=d, decay_rate=e), None)
+     for a, b, c, d, e in ((1.0, 1.0, 0.0, 1.0, 1.0), (1.0, 2.5, 1.0, 1.5, 0.1), (2.5, 2.5, 0.0, 1.05, 0.7), (1.0, 2.5, 0.0, 2.0, 0.0))] +
+    [(2, {}, w) for w in (1.0, 2.0)] +
+    [(3, dict(beta=b), None) for b in (0.0, 1.0)] +
+    [(6, dict(min_step_factor=m, bisection_steps=n), None) for m, n in ((0.0, 16), (1.0, 16), (0.0, 64), (1.0, 1))] +
+    [(9, dict(stuck_threshold=k, stuck_step_ratio=r, min_step_factor=m), None)
+     for k, r, m in ((0, 0.001, 0.005), (1, 0.001, 0.005), (5, 0.0, 0.0), (5, 1.0, 1.0), (1, 1.0, 0.0), (20, 0.01, 1.0))] +
+    [(7, {}, m) for m in (0.0, 1.0)] +
+    [(10, {}, n) for n in (1, 64)] +
+    [(8, {}, n) for n in (1, 64)]
+)
+
+
+def _center_t(sid, view):
+    """t of the frame's central ray under the default configuration: places a far plane relative to the object."""
+    scene = SCENES[sid]
+    cam = Camera(position=Vec3(*view[0]), target=Vec3(*view[1]), up=Vec3(*view[2]), fov_degrees=view[3], width=1, height=1)
+    r = STRATEGIES["Standard"]().march(cam.get_ray(0, 0), scene.sdf, MarchConfig())
+    assert r.hit, (sid, view)
+    return float(r.t)
+
+
+def family_c(W=16, H=12):
+    out = []
+    for sid in (0, 3, 13):
+        view = default_view(SCENES[sid])
+        for kid in range(len(STRAT_KEYS)):
+            for thr in (0.0, 1e-9, 0.5):                                      # nothing converges below 1e-9: the budget runs out
+                out.append(spec(f"C/thr/{thr:g}", sid, kid, view, W, H, mi=200 if thr == 0.5 else 700, thr=thr))
+    for mi in (542, 543, 544, 2048):                                         # around the last bin of a 544-bin iteration histogram
+        for kid in (0, 4, 6, 10):
+            out.append(spec(f"C/hist/{mi}", 0, kid, default_view(SCENES[0]), W, H, mi=mi, thr=0.0))
+    for sid in (0, 2, 1):
+        view = _vp_views(sid)[-1 if sid == 1 else 0][1]                    # the plane from its most grazing viewpoint
+        tc = _center_t(sid, view)
+        # below the camera's distance to the object; just past the central hit, so the far plane cuts between the object's
+        # near and far surface and the silhouette rays' hits lie beyond it; then far planes only the plane's horizon reaches
+        for what, far in (("below", round(0.5 * tc, 6)), ("between", round(1.02 * tc, 6)), ("1e4", 1e4), ("1e9", 1e9)):
+            for kid in range(len(STRAT_KEYS)):
+                out.append(spec(f"C/far/{what}", sid, kid, view, W, H, far=far, mi=2048 if sid == 1 else 512))
+    for sid in (0, 11, 10, 9, 2):                                             # 10: no bound of its own; 11: bound 2.0
+        for lip in (0.1, 0.5, 2.0, 4.0):
+            out.append(spec(f"C/lip/{lip:g}", sid, 10, default_view(SCENES[sid]), W, H, lip=lip, mi=256))
+    for kid, ctor, lit in PARAM_ENDS:
+        for sid, mi, thr in ((0, 100, 1e-3), (9, 64, 1e-2), (10, 150, 1e-5), (12, 300, 3e-4)):
+            out.append(spec(f"C/prm/{kid}", sid, kid, default_view(SCENES[sid]), W, H, mi=mi, thr=thr, ctor=ctor, lit=lit))
+    return out
+
+
+def family_d():
+    out = []
+    up = (0.0, 1.0, 0.0)
+    cams = [("inside", ((0.0, 0.0, 0.3), (0.0, 0.0, -1.0), up, 60.0)),
+            ("inside-offaxis", ((0.2, -0.1, 0.15), (1.0, 1.0, 1.0), up, 90.0)),
+            ("on-surface-in", ((0.0, 0.0, 1.0), (0.0, 0.0, 0.0), up, 60.0)),       # sdf == 0 at the rays' origin, looking in
+            ("on-surface-out", ((0.0, 0.0, 1.0), (0.0, 0.0, 3.0), up, 60.0)),      # ... and looking away
+            ("on-surface-along", ((0.0, 0.0, 1.0), (0.0, 3.0, 1.0), (0.0, 0.0, 1.0), 60.0)),
+            ("down-parallel-up", ((0.0, 5.0, 0.0), (0.0, 0.0, 0.0), up, 60.0)),    # forward x up == 0: right and up are zero
+            ("up-zero", ((0.0, 0.0, 5.0), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 60.0)),
+            ("no-forward", ((0.0, 0.0, 5.0), (0.0, 0.0, 5.0), up, 60.0)),          # target == position: every basis vector zero
+            ("up+z", ((3.0, 3.0, 1.0), (0.0, 0.0, 0.0), (0.0, 0.0, 1.0), 60.0)),
+            ("up+xy", ((0.0, 0.5, 4.0), (0.0, 0.0, 0.0), (1.0, 1.0, 0.0), 60.0)),
+            ("up-y", ((1.0, 2.0, 4.0), (0.0, 0.0, 0.0), (0.0, -1.0, 0.0), 60.0)),
+            ("fov5", ((0.0, 0.0, 5.0), (0.0, 0.0, 0.0), up, 5.0)),
+            ("fov150", ((0.0, 0.0, 3.0), (0.0, 0.0, 0.0), up, 150.0))]
+    rot = 0
+    for name, view in cams:
+        for sid in (0, 2, 4, 11):
+            if name.startswith("on-surface"):
+                assert SCENES[sid].sdf(Vec3(*view[0])) == 0.0, (sid, view)
+            for _ in range(3):
+                kid = rot % len(STRAT_KEYS)
+                rot += 1
+                out.append(spec(f"D/cam/{name}", sid, kid, view, 12, 9, mi=128, stats=True))
+    for kid in (0, 6, 10):
+        out.append(spec("D/cam/inside", 10, kid, cams[0][1], 12, 9, mi=128, stats=True))
+    shapes = [(1, 1, 0, 1), (1, 7, 0, 7), (9, 1, 0, 1), (63, 3, 0, 3), (64, 4, 0, 4), (65, 5, 0, 5),
+              (20, 17, 3, 5), (20, 17, 1, 1), (20, 17, 6, 11), (33, 10, 7, 2)]
+    for W, H, row0, rows in shapes:
+        for sid, kid in ((0, 0), (9, 6), (10, 10), (12, 2), (1, 4)):
+            out.append(spec(f"D/shape/{W}x{H}+{row0}+{rows}", sid, kid, default_view(SCENES[sid]), W, H, row0, rows, mi=256, stats=True))
+    return out
+
+
+def family_e(n=320):
+    """Seeded draws over every scene, every strategy and every axis the other families pick values on by hand."""
+    rng = random.Random(CONFIG_SEED)
+    out = []
+    for i in range(n):
+        sid, kid = (i % 20, (i // 20 + i) % 11) if i < 220 else (rng.randrange(20), rng.randrange(11))   # every pair's scene and strategy met
+        W, H = rng.randint(1, 24), rng.randint(1, 18)
+        row0 = 0 if rng.random() < 0.7 else rng.randrange(H)
+        rows = H - row0 if rng.random() < 0.7 else rng.randint(1, H - row0)
+        pos, tgt, _, _ = default_view(SCENES[sid])
+        s = rng.choice((0.3, 1.0, 1.0, 3.0, 12.0))
+        pos = tuple(c * s + rng.gauss(0.0, 0.3) for c in pos)
+        tgt = tuple(c + rng.gauss(0.0, 0.2) for c in tgt)
+        upv = rng.choice(((0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 1.0, 0.0), (0.0, -1.0, 0.0)))
+        fov = rng.choice((5.0, 30.0, 60.0, 90.0, 150.0))
+        mi = rng.choice((0, 1, 2, 3, 15, 16, 17, 32, 64, 128, 256, 512, 700, 2048))
+        if sid in HEAVY_SCENES:
+            mi = min(mi, 300)
+        thr = rng.choice((0.0, 1e-2, 3e-3, 1e-3, 3e-4, 1e-4, 3e-5, 1e-5, 1e-9, 0.5))
+        far = rng.choice((0.5, 2.0, 9.0, 30.0, 100.0, 1e4, 1e9))
+        lip = rng.choice((None, 0.1, 0.5, 1.0, 2.0, 4.0)) if kid == 10 else None
+        ctor, lit = {}, None
+        if rng.random() < 0.6:
+            if kid == 1:
+                ctor = dict(omega=rng.uniform(1.0, 2.5))
+            elif kid == 2:
+                ctor = dict(omega_min=rng.uniform(1.0, 1.3), omega_max=rng.uniform(1.3, 2.5), smoothing=rng.uniform(0.0, 1.0),
+                            growth_rate=rng.uniform(1.0, 1.3), decay_rate=rng.uniform(0.3, 1.0))
+                lit = rng.choice((None, 1.0, 1.7))
+            elif kid == 3:
+                ctor = dict(beta=rng.uniform(0.0, 1.0))
+            elif kid == 6:
+                ctor = dict(min_step_factor=rng.choice((0.0, 0.001, 0.01, 0.1, 1.0)), bisection_steps=rng.randint(0, 64))
+            elif kid == 9:
+                ctor = dict(stuck_threshold=rng.randint(0, 20), stuck_step_ratio=rng.choice((0.0, 1e-4, 1e-3, 1e-2, 1.0)),
+                            min_step_factor=rng.choice((0.0, 0.005, 0.1, 1.0)))
+            elif kid == 7:
+                lit = rng.choice((0.0, 0.02, 0.1, 0.5))
+            elif kid in (8, 10):
+                lit = rng.randint(0, 64)
+        out.append(spec(f"E/{i}", sid, kid, (pos, tgt, upv, fov), W, H, row0, rows, mi=mi, thr=thr, far=far, lip=lip, ctor=ctor, lit=lit))
+    return out
+
+
+def gen_config(jobs):
+    import multiprocessing
+    fams = {"A": family_a(), "B": family_b(), "C": family_c(), "D": family_d(), "E": family_e()}
+    skipped, drawn = [], 0
+    with multiprocessing.Pool(jobs) as pool:
+        for fam, specs in fams.items():
+            t0 = time.time()
+            done = [(sp, one) for sp, one, err in pool.imap(run_spec, specs, chunksize=4)
+                    if err is None or skipped.append(dict(sp, reason=err))]
+            drawn += len(specs)
+            store = {k: np.stack([one[k] for _, one in done]) for k in ("prm", "meta", "cam", "sha_t", "sha_fs", "sha_depth32", "t_bits", "refstats")}
+            store["ids"] = np.array([[sp["sid"], sp["kid"]] for sp, _ in done], dtype=np.int32)
+            store["view"] = np.array([sp["view"] for sp, _ in done], dtype=np.float64)
+            store["iters"] = np.concatenate([one["iters"].reshape(-1) for _, one in done])
+            store["off"] = np.cumsum([0] + [one["iters"].size for _, one in done]).astype(np.int64)
+            store["hitbits"] = np.packbits(np.concatenate([one["hit"] for _, one in done]))
+            store["tag"] = np.array([sp["tag"] for sp, _ in done])
+            save_npz(os.path.join(OUT, f"frames_config_{fam}.npz"), store)
+            print(f"  [config] family {fam}: {len(done)} cases of {len(specs)}, {int(store['off'][-1])} rays, "
+                  f"{int(store['iters'].astype(np.int64).sum())} iterations, max {int(store['iters'].max())}  ({time.time() - t0:.0f}s)", flush=True)
+    for s in skipped:
+        print(f"  [config] SKIPPED (the reference raised) {s['tag']}: {s['reason']}", flush=True)
+    with open(os.path.join(OUT, "frames_config_skipped.json"), "w", encoding="utf-8") as f:
+        json.dump({"seed": CONFIG_SEED, "drawn": drawn, "skipped": skipped}, f, indent=1)
+
+
+# (scene, strategy, MarchConfig arguments, constructor arguments, literal): Mandelbulb with three strategies is the team form
+RAY_PAIRS = [(0, 0, dict(), {}, None), (2, 6, dict(max_iterations=64, hit_threshold=1e-3), dict(bisection_steps=5), None),
+             (3, 10, dict(max_distance=9.0), {}, 3), (9, 4, dict(max_iterations=100), {}, None),
+             (12, 9, dict(hit_threshold=1e-5, max_distance=30.0), dict(stuck_threshold=2), None),
+             (1, 1, dict(max_iterations=2048, max_distance=1e4), dict(omega=1.6), None), (13, 7, dict(max_iterations=17), {}, 0.1),
+             (16, 8, dict(max_iterations=200, hit_threshold=3e-3), {}, None),
+             (10, 0, dict(max_iterations=300), {}, None), (10, 6, dict(max_iterations=40, hit_threshold=3e-4), {}, None),
+             (10, 10, dict(max_iterations=128, max_distance=9.0), {}, 12)]
+
+
+def ray_inputs(rng, scene, far, n=300):
+    """Origins and directions as a caller of MarchStrategy.march may pass them: unit and un-normalised directions, exactly
+    zero ones, lengths on both sides of Vec3.normalized()'s 1e-12, origins inside the object and beyond the far plane."""
+    pos = default_view(scene)[0]
+
+    def unit():
+        while True:
+            d = [rng.gauss(0.0, 1.0) for _ in range(3)]
+            l = sum(c * c for c in d) ** 0.5
+            if l > 0.1:
+                return [c / l for c in d]
+
+    def toward(o, spread):
+        d = [-c for c in o]
+        l = sum(c * c for c in d) ** 0.5 or 1.0
+        return [c / l + rng.gauss(0.0, spread) for c in d]
+    o, d = [], []
+    for i in range(n):
+        oi = [c + rng.gauss(0.0, 0.05) for c in pos]
+        di = toward(oi, 0.25)
+        if i < 100:                                                   # unit
+            l = sum(c * c for c in di) ** 0.5
+            di = [c / l for c in di]
+        elif i < 170:                                                 # un-normalised, 1e-6 .. 1e6
+            s = 10.0 ** rng.uniform(-6.0, 6.0)
+            di = [c * s for c in di]
+        elif i < 180:                                                 # exactly zero (one of them -0.0)
+            di = [0.0, 0.0, -0.0 if i == 179 else 0.0]
+        elif i < 200:                                                 # length just below 1e-12: normalises to the zero vector
+            di = [c * rng.choice((0.999e-12, 0.9e-12, 1e-13, 1e-30)) for c in unit()]
+        elif i < 220:                                                 # ... and just above
+            di = [c * rng.choice((1.001e-12, 1.1e-12, 1e-11)) for c in unit()]
+        elif i < 270:                                                 # origins in or near the object, any direction
+            oi = [rng.uniform(-0.6, 0.6) for _ in range(3)]
+            di = unit()
+        else:                                                         # origins beyond the far plane, looking back
+            u = unit()
+            oi = [c * far * rng.uniform(1.01, 3.0) for c in u]
+            di = toward(oi, 0.01)
+        o.append(oi)
+        d.append(di)
+    return np.array(o, dtype=np.float64), np.array(d, dtype=np.float64)
+
+
+def run_ray_pair(args):
+    from raymarching_benchmark.core.ray import Ray
+    n, (sid, kid, mckw, ctor, lit) = args
+    scene = SCENES[sid]
+    strategy, lip, overrides = build_strategy(scene, kid, ctor, lit, None)
+    mc = MarchConfig(**mckw)
+    o, d = ray_inputs(random.Random(CONFIG_SEED + n), scene, mc.max_distance)
+    res = [strategy.march(Ray(Vec3(*oi), Vec3(*di)), scene.sdf, mc) for oi, di in zip(o.tolist(), d.tolist())]
+    prm = dict(PARAM_DEFAULTS, **overrides)
+    pre = f"p{n}_"
+    return {pre + "ids": np.array([sid, kid], dtype=np.int32), pre + "o": o, pre + "d": d,
+            pre + "meta": np.array([mc.max_iterations, mc.hit_threshold, mc.max_distance, lip], dtype=np.float64),
+            pre + "prm": np.array([float(prm[k]) for k in PARAM_ORDER], dtype=np.float64),
+            pre + "hit": np.array([bool(r.hit) for r in res], dtype=np.uint8),
+            pre + "iters": np.array([r.iterations for r in res], dtype=np.int32),
+            pre + "t_bits": np.array([float(r.t) for r in res], dtype="<f8").view(np.uint64),
+            pre + "fs_bits": np.array([float(r.final_sdf) for r in res], dtype="<f8").view(np.uint64)}
+
+
+def gen_rays(jobs):
+    """rays_config.npz: MarchStrategy.march on explicit Ray(origin, direction) objects (Ray.__init__ normalises, core/ray.py:11-13).
+    Keys p{n}_: ids, meta (max_iterations, hit_threshold, max_distance, lipschitz), prm, o, d (inputs), hit, iters, t_bits, fs_bits."""
+    import multiprocessing
+    store = {}
+    with multiprocessing.Pool(jobs) as pool:
+        for part in pool.imap(run_ray_pair, list(enumerate(RAY_PAIRS))):
+            store.update(part)
+            n = next(iter(part)).split("_")[0]
+            print(f"  [rays] pair {n}: hits {int(part[n + '_hit'].sum())} iterations {int(part[n + '_iters'].sum())}", flush=True)
+    store["npairs"] = np.array([len(RAY_PAIRS)], dtype=np.int32)
+    save_npz(os.path.join(OUT, "rays_config.npz"), store)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="all")
+    ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1), help="worker processes of --only config / rays")
     a = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     all_pairs = [(s, k) for s in range(len(SCENES)) for k in range(len(STRAT_KEYS))]
@@ -404,6 +835,10 @@ def main():
         gen_params()
     if a.only in ("all", "schema"):
         gen_schema()
+    if a.only in ("all", "config"):
+        gen_config(a.jobs)
+    if a.only in ("all", "rays"):
+        gen_rays(a.jobs)
     if a.only in ("all", "small"):
         # max_iterations=100, 16x12: the configuration of the reference's own smoke test
         # (tests/test_smoke.py:31-43), every registry key on the Sphere.

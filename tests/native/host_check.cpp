@@ -36,11 +36,33 @@ static int render_s(int strategy, const MarchCfg& cfg, const CameraParams& cam, 
     return -2;
 }
 
-extern "C" {
+// Explicit rays, as march_rays_kernel (csrc/rm_kernels.h) marches them: the direction goes through normalized().
+template <class Scene, class Strat>
+static void rays_t(const MarchCfg& cfg, const double* origins, const double* dirs, size_t n,
+                   uint8_t* hit, double* t, int32_t* iters, double* fs)
+{
+    for (size_t i = 0; i < n; ++i) {
+        vec3 o = v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]);
+        vec3 d = normalized(v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+        Result res = march_one<Scene, Strat>(o, d, cfg);
+        hit[i] = (uint8_t)res.hit; t[i] = res.t; iters[i] = res.iters; fs[i] = res.final_sdf;
+    }
+}
 
-int rmh_render(int scene, int strategy, int max_iterations, double hit_threshold, double max_distance,
-               double lipschitz, int full, const double* cam14, int W, int H, int row0, int rows,
-               uint8_t* hit, double* t, int32_t* iters, double* fs, const double* prm18)
+template <class Scene>
+static int rays_s(int strategy, const MarchCfg& cfg, const double* origins, const double* dirs, size_t n,
+                  uint8_t* hit, double* t, int32_t* iters, double* fs)
+{
+    switch (strategy) {
+#define RM_X(id, S) case id: rays_t<Scene, S>(cfg, origins, dirs, n, hit, t, iters, fs); return 0;
+        RM_STRATEGY_LIST(RM_X)
+#undef RM_X
+    }
+    return -2;
+}
+
+static MarchCfg make_cfg(int max_iterations, double hit_threshold, double max_distance, double lipschitz, int full,
+                         const double* prm18)
 {
     MarchCfg cfg;
     cfg.hit_threshold = hit_threshold; cfg.max_distance = max_distance; cfg.lipschitz = lipschitz;
@@ -56,10 +78,33 @@ int rmh_render(int scene, int strategy, int max_iterations, double hit_threshold
         p.segment_bisection_steps = (int32_t)prm16[14]; p.revaa_bisection_steps = (int32_t)prm16[15];
         p.step_scale = prm18[16]; p.dense_min_step = prm18[17];
     }
+    return cfg;
+}
+
+extern "C" {
+
+int rmh_render(int scene, int strategy, int max_iterations, double hit_threshold, double max_distance,
+               double lipschitz, int full, const double* cam14, int W, int H, int row0, int rows,
+               uint8_t* hit, double* t, int32_t* iters, double* fs, const double* prm18)
+{
+    MarchCfg cfg = make_cfg(max_iterations, hit_threshold, max_distance, lipschitz, full, prm18);
     CameraParams cam;
     for (int i = 0; i < 14; ++i) cam.v[i] = cam14[i];
     switch (scene) {
 #define RM_X(id, S) case id: return render_s<S>(strategy, cfg, cam, W, H, row0, rows, hit, t, iters, fs);
+        RM_SCENE_LIST(RM_X)
+#undef RM_X
+    }
+    return -1;
+}
+
+int rmh_march_rays(int scene, int strategy, int max_iterations, double hit_threshold, double max_distance,
+                   double lipschitz, int full, const double* origins, const double* dirs, size_t n,
+                   uint8_t* hit, double* t, int32_t* iters, double* fs, const double* prm18)
+{
+    MarchCfg cfg = make_cfg(max_iterations, hit_threshold, max_distance, lipschitz, full, prm18);
+    switch (scene) {
+#define RM_X(id, S) case id: return rays_s<S>(strategy, cfg, origins, dirs, n, hit, t, iters, fs);
         RM_SCENE_LIST(RM_X)
 #undef RM_X
     }

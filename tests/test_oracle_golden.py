@@ -69,10 +69,17 @@ def test_multithreaded_render_is_identical():
 
 
 def test_edge_cases():
+    import config_cases as cc
     cam = oracle.camera14((0, 0, 5), (0, 0, 0), (0, 1, 0), 60.0, 8, 4)
-    # zero rows, zero iterations budget, budget below the bisection reserve (overstep_bisect.py:40-41)
+    # zero rows
     assert oracle.render(0, 0, cam, 8, 4, row0=2, rows=0).iters.shape == (0, 8)
-    fr = oracle.render(0, 0, cam, 8, 4, max_iterations=0)
-    assert (fr.iters == 0).all() and (fr.hit == 0).all()
-    fr = oracle.render(0, 6, cam, 8, 4, max_iterations=10)
-    assert (fr.iters == 0).all() and (fr.hit == 0).all()
+    # zero iterations budget, budget below the bisection reserve (overstep_bisect.py:40-41): the same two frames as the
+    # reference marched them (family B of tests/golden/frames_config_B.npz, tags B/edge/...)
+    edge = [c for c in cc.family("B") if c["tag"].startswith("B/edge/")]
+    assert [(c["sid"], c["kid"], c["max_iterations"]) for c in edge] == [(0, 0, 0), (0, 6, 10)]
+    for c in edge:
+        assert (c["cam"].view(np.uint64) == cam.view(np.uint64)).all() and (c["W"], c["H"], c["rows"]) == (8, 4, 4)
+        fr = oracle.render(c["sid"], c["kid"], cam, 8, 4, max_iterations=c["max_iterations"])
+        assert (fr.iters == c["iters"]).all() and (fr.hit == c["hit"]).all(), c["tag"]
+        assert sha_f64(fr.t) == c["sha_t"] and sha_f64(fr.final_sdf) == c["sha_fs"], c["tag"]
+        assert cc.sha_depth32(fr.hit, fr.t) == c["sha_depth32"], c["tag"]
