@@ -360,6 +360,48 @@ int rm_interval_march_rays(int scene_id, const RmIntervalConfig* cfg, const doub
 int rm_interval_render(const RmFrameDesc* desc, const RmIntervalConfig* cfg, double* depth, uint8_t* hit,
                        double* normal, int32_t* steps, RmTiming* timing);
 
+/* ---- Sound segment tracer (gpu/faithful_offline.py, gpu/interval_autodiff.py) -----------------------------------------
+ * The ceiling of the comparison: a Galin-style segment tracer whose Lipschitz bound is not sampled but proven.  Each trip
+ * evaluates f at the cursor t (the interval program at a degenerate box) -- a hit when |f| < tol -- and a dual interval
+ * (value enclosure + enclosure of the derivative along the ray, csrc/rm_segment.h) over [t, t + h]:
+ * K = clip(max |der|, k_min, l_global) bounds |g'| there, so step = min(|f| / K, h) is short of the surface;
+ * t += step, h = clip(max(step, |f| / K) * kappa, h_min, h_max); a miss once t > t_max or after `budget` trips.
+ * Scenes, errors, stream and timing conventions: exactly as the interval oracle above (the same 14 catalogue scenes and
+ * every live scene program; RM_E_BAD_SCENE otherwise).  Sphere, Grazing Plane, Cube and Thin Torus are the reference's
+ * COMPONENT_SCENES bit for bit.  l_global is a bound of |grad f| times the length of the direction: the default 1 is
+ * right for exact SDFs and unit directions only. */
+/* Ceiling of RmSegmentConfig.budget: every trip is two dependent evaluations of the scene's program (the point, then the
+ * dual interval over the probe), so 10x the reference's 4096 bounds one launch to seconds like RM_INTERVAL_MAX_STEPS. */
+#define RM_SEGMENT_MAX_STEPS 40960
+typedef struct RmSegmentConfig {   /* every field 0 = the reference's constant */
+    double t_max;                  /* 100    DEFAULT_T_MAX */
+    double tol;                    /* 1e-4   _TOL: a hit once |f| < tol at the cursor */
+    double h0;                     /* 0.1    _H0: first probe length */
+    double kappa;                  /* 1.5    _KAPPA: probe growth */
+    double h_min;                  /* 1e-5   _HMIN */
+    double h_max;                  /* 10     _HMAX */
+    double k_min;                  /* 1e-6   _KMIN: floor of the directional bound K */
+    double l_global;               /* 1      the global Lipschitz bound K is clamped to */
+    double bound_radius;           /* rm_segment_render's prune, as RmIntervalConfig.bound_radius */
+    int32_t budget;                /* 4096   _BUDGET: trips per ray (at most RM_SEGMENT_MAX_STEPS) */
+    int32_t reserved;              /* 0 */
+} RmSegmentConfig;
+/* Negative or non-finite fields, budget < 0 or > RM_SEGMENT_MAX_STEPS, reserved != 0: RM_E_BAD_ARG. */
+
+/* Same answer as rm_interval_supported.  Host only. */
+int rm_segment_supported(int scene_id);
+/* The dual interval over n ray segments: segs is n x 8 (origin, direction, t0, t1; the direction as given); out is n x 4
+ * (val.lo, val.hi, der.lo, der.hi).  val equals rm_interval_sdf_eval of the segment's box bit for bit. */
+int rm_segment_sdf_eval(int scene_id, const double* segs, size_t n, double* out);
+/* segment_trace over n explicit rays (directions as given).  t: the hit, +inf on a miss.  iters (n int32, optional): trips
+ * the ray was active.  cursor (n, optional): the final t.  cfg may be NULL; its bound_radius is not used here. */
+int rm_segment_march_rays(int scene_id, const RmSegmentConfig* cfg, const double* origins, const double* dirs,
+                          size_t n, double* t, int32_t* iters, double* cursor);
+/* faithful_capture over rows [row0, row0 + rows) of the frame desc describes (as rm_interval_render).  Per pixel: depth (t
+ * on a hit, 0 on a miss), hit, iters (optional; 0 for a pruned ray), cursor (optional; the final t, 0 for a pruned ray). */
+int rm_segment_render(const RmFrameDesc* desc, const RmSegmentConfig* cfg, double* depth, uint8_t* hit,
+                      int32_t* iters, double* cursor, RmTiming* timing);
+
 /* Same contract, evaluated by wavefront TEAMS (scenes whose SDF is a loop of independent
  * transcendental chains -- Mandelbulb: three waves carry the same 64 rays and each evaluates one
  * chain per trip; see rm_kernels.h).  Identical results; RM_E_BAD_SCENE for scenes without a team form. */

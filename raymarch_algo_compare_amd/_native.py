@@ -34,9 +34,11 @@ EXPORTS = [
     "rm_runtime_info", "rm_stream_create", "rm_stream_synchronize", "rm_stream_destroy", "rm_debug_poison_queues",
     "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy", "rm_debug_math_eval",
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
+    "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
 ]
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
+RM_SEGMENT_MAX_STEPS = 40960     # RmSegmentConfig.budget ceiling
 RM_SCENE_PROGRAM_BASE = 1024
 # RmMathFn (include/rm_hip.h): the device math routines rm_debug_math_eval evaluates
 MATH_FNS = {"POW": 0, "POW2": 1, "POW_HALF_DENSE": 2, "POW_HALF_SPARSE": 3, "POW_HALF_GUARD": 4, "SQRT": 5, "SIN": 6,
@@ -154,6 +156,13 @@ class RmIntervalConfig(ctypes.Structure):
                 ("max_steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class RmSegmentConfig(ctypes.Structure):
+    """The sound segment tracer's constants (include/rm_hip.h); every field 0 = the reference's value."""
+    _fields_ = [("t_max", ctypes.c_double), ("tol", ctypes.c_double), ("h0", ctypes.c_double), ("kappa", ctypes.c_double),
+                ("h_min", ctypes.c_double), ("h_max", ctypes.c_double), ("k_min", ctypes.c_double), ("l_global", ctypes.c_double),
+                ("bound_radius", ctypes.c_double), ("budget", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class RmDeviceInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 128), ("arch", ctypes.c_char * 64),
                 ("device_id", ctypes.c_int32), ("compute_units", ctypes.c_int32),
@@ -239,6 +248,11 @@ def load() -> ctypes.CDLL:
         L.rm_interval_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmIntervalConfig), dp, dp, ctypes.c_size_t, dp, vp, vp]
         L.rm_interval_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmIntervalConfig), vp, vp, vp, vp,
                                          ctypes.POINTER(RmTiming)]
+        L.rm_segment_supported.argtypes = [ctypes.c_int]
+        L.rm_segment_sdf_eval.argtypes = [ctypes.c_int, dp, ctypes.c_size_t, dp]
+        L.rm_segment_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmSegmentConfig), dp, dp, ctypes.c_size_t, dp, vp, vp]
+        L.rm_segment_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmSegmentConfig), vp, vp, vp, vp,
+                                        ctypes.POINTER(RmTiming)]
         for name in EXPORTS:
             if name not in ("rm_shutdown", "rm_last_error", "rm_stats_device_bytes", "rm_default_strategy_params"):
                 getattr(L, name).restype = ctypes.c_int
@@ -522,6 +536,66 @@ def interval_render(scene_id: int, cam14, width: int, height: int, cfg: RmInterv
     shape = (int(d.rows), int(width))
     out = {"depth": depth.reshape(shape), "hit": hit.reshape(shape), "normal": normal.reshape(shape + (3,)),
            "steps": steps.reshape(shape)}
+    if tm is not None:
+        out["timing"] = timing_dict(tm)
+    return out
+
+
+def segment_config(t_max=0.0, tol=0.0, h0=0.0, kappa=0.0, h_min=0.0, h_max=0.0, k_min=0.0, l_global=0.0, bound_radius=0.0,
+                   budget=0) -> RmSegmentConfig:
+    """RmSegmentConfig; 0 = the reference's constant (bound_radius 0: the library's bound for the scene, < 0: no prune)."""
+    c = RmSegmentConfig()
+    c.t_max, c.tol, c.h0, c.kappa, c.h_min, c.h_max = float(t_max), float(tol), float(h0), float(kappa), float(h_min), float(h_max)
+    c.k_min, c.l_global, c.bound_radius, c.budget = float(k_min), float(l_global), float(bound_radius), int(budget)
+    return c
+
+
+def segment_supported(scene_id: int) -> bool:
+    """rm_segment_supported (no GPU needed)."""
+    return load().rm_segment_supported(int(scene_id)) == 1
+
+
+def segment_sdf_eval(scene_id: int, segs):
+    """rm_segment_sdf_eval: (n, 4) val.lo, val.hi, der.lo, der.hi of the scene's SDF over each ray segment (n x 8: origin,
+    direction, t0, t1)."""
+    L = init()
+    segs = np.ascontiguousarray(segs, dtype=np.float64).reshape(-1, 8)
+    out = np.empty((len(segs), 4))
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_segment_sdf_eval(int(scene_id), segs.ctypes.data_as(dp), len(segs), out.ctypes.data_as(dp)))
+    return out
+
+
+def segment_march_rays(scene_id: int, origins, dirs, cfg: RmSegmentConfig | None = None):
+    """rm_segment_march_rays: (t (+inf on a miss), iters, cursor) of n explicit rays."""
+    L = init()
+    origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    if origins.shape != dirs.shape:
+        raise ValueError("origins and dirs differ in shape")
+    n = len(dirs)
+    t, iters, cursor = np.empty(n), np.empty(n, np.int32), np.empty(n)
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_segment_march_rays(int(scene_id), ctypes.byref(cfg) if cfg is not None else None, origins.ctypes.data_as(dp),
+                                  dirs.ctypes.data_as(dp), n, t.ctypes.data_as(dp), _ptr(iters), _ptr(cursor)))
+    return t, iters, cursor
+
+
+def segment_render(scene_id: int, cam14, width: int, height: int, cfg: RmSegmentConfig | None = None, row0=0, rows=None,
+                   warmup=0, repeats=0) -> dict:
+    """rm_segment_render: depth (0 on a miss), hit, iters, cursor of rows [row0, row0 + rows); `timing` with repeats > 0."""
+    L = init()
+    d = make_desc(scene_id, 0, cam14, width, height, row0, rows)
+    n = int(width) * int(d.rows)
+    depth, hit, iters, cursor = np.empty(n), np.empty(n, np.uint8), np.empty(n, np.int32), np.empty(n)
+    tm = None
+    if repeats > 0:
+        tm = RmTiming()
+        tm.warmup, tm.repeats = int(warmup), int(repeats)
+    check(L.rm_segment_render(ctypes.byref(d), ctypes.byref(cfg) if cfg is not None else None, _ptr(depth), _ptr(hit),
+                              _ptr(iters), _ptr(cursor), ctypes.byref(tm) if tm is not None else None))
+    shape = (int(d.rows), int(width))
+    out = {"depth": depth.reshape(shape), "hit": hit.reshape(shape), "iters": iters.reshape(shape), "cursor": cursor.reshape(shape)}
     if tm is not None:
         out["timing"] = timing_dict(tm)
     return out

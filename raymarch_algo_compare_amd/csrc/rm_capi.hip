@@ -24,6 +24,7 @@
 #include "rm_scene_program.h"
 #include "rm_interval.h"
 #include "rm_interval_catalogue.h"
+#include "rm_segment.h"
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
 static_assert(RM_NUM_SCENES == 20 && RM_NUM_STRATEGIES == 11 && RM_NUM_STRATEGY_KERNELS == 13, "registry size");
@@ -52,6 +53,12 @@ hipError_t launch_interval_march(const void* prog, const IntervalParams& P, cons
                                  double* t, int32_t* steps, double* normals, hipStream_t s);
 hipError_t launch_interval_render(const void* prog, const IntervalParams& P, const CameraParams& cam, int width, int height,
                                   int row0, int rows, double* depth, uint8_t* hit, double* normal, int32_t* steps, hipStream_t s);
+// rm_segment.hip: the sound segment tracer (rm_segment_*)
+hipError_t launch_segment_sdf(const void* prog, const double* segs, size_t n, double* out, hipStream_t s);
+hipError_t launch_segment_march(const void* prog, const SegmentParams& P, const double* origins, const double* dirs, size_t n,
+                                double* t, int32_t* iters, double* cursor, hipStream_t s);
+hipError_t launch_segment_render(const void* prog, const SegmentParams& P, const CameraParams& cam, int width, int height,
+                                 int row0, int rows, double* depth, uint8_t* hit, int32_t* iters, double* cursor, hipStream_t s);
 static const SceneLaunchers* scene(int id)
 {
     switch (id) {
@@ -1920,6 +1927,97 @@ int rm_interval_render(const RmFrameDesc* d, const RmIntervalConfig* cfg, double
         return (int)RM_OK;
     };
     // (a timed call waits twice: timed() before it reads its events, finish() for the maps)
+    if ((rc = timing ? timed(e, timing, g.stream, go) : go())) return rc;
+    return st.finish();
+}
+
+// ---- sound segment tracer (rm_segment.h, rm_segment.hip): scenes and programs as the interval oracle ------------------
+
+namespace {
+
+int segment_params(int id, const RmSegmentConfig* cfg, rm::SegmentParams* P)
+{
+    char why[160];
+    if (!rm::segment_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
+        return fail(RM_E_BAD_ARG, "RmSegmentConfig: %s", why);
+    return RM_OK;
+}
+
+}  // namespace
+
+int rm_segment_supported(int scene_id) { return rm_interval_supported(scene_id); }
+
+int rm_segment_sdf_eval(int scene_id, const double* segs, size_t n, double* out)
+{
+    int rc = interval_check_scene(scene_id);
+    if (rc) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+    if (n == 0) return RM_OK;
+    if (!segs || !out) return fail(RM_E_BAD_ARG, "NULL buffer");
+    const void* prog = nullptr;
+    if ((rc = interval_program(e, scene_id, &prog))) return rc;
+    Staged st(e);
+    const double* d_segs = st.in(g.in[0], segs, n * 64);
+    double* d_out = st.out(g.out[0], out, n * 32);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_segment_sdf(prog, d_segs, n, d_out, g.stream));
+    return st.finish();
+}
+
+int rm_segment_march_rays(int scene_id, const RmSegmentConfig* cfg, const double* origins, const double* dirs, size_t n,
+                          double* t, int32_t* iters, double* cursor)
+{
+    int rc = interval_check_scene(scene_id);
+    if (rc) return rc;
+    rm::SegmentParams P;
+    if ((rc = segment_params(scene_id, cfg, &P))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+    if (n == 0) return RM_OK;
+    if (!origins || !dirs || !t) return fail(RM_E_BAD_ARG, "NULL buffer");
+    const void* prog = nullptr;
+    if ((rc = interval_program(e, scene_id, &prog))) return rc;
+    Staged st(e);
+    const double* d_origins = st.in(g.in[0], origins, n * 24);
+    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
+    double* d_t = st.out(g.out[0], t, n * 8);
+    int32_t* d_iters = st.out(g.out[1], iters, n * 4);
+    double* d_cursor = st.out(g.out[2], cursor, n * 8);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_segment_march(prog, P, d_origins, d_dirs, n, d_t, d_iters, d_cursor, g.stream));
+    return st.finish();
+}
+
+int rm_segment_render(const RmFrameDesc* d, const RmSegmentConfig* cfg, double* depth, uint8_t* hit, int32_t* iters,
+                      double* cursor, RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    int rc = interval_check_scene(d->scene_id);
+    if (rc) return rc;
+    rm::SegmentParams P;
+    if ((rc = segment_params(d->scene_id, cfg, &P))) return rc;
+    if ((rc = check_slice(d, false))) return rc;
+    if (timing && (rc = check_timing(timing))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    if (n == 0) return RM_OK;
+    if (!depth || !hit) return fail(RM_E_BAD_ARG, "depth and hit are required");
+    const void* prog = nullptr;
+    if ((rc = interval_program(e, d->scene_id, &prog))) return rc;
+    Staged st(e);
+    double* d_depth = st.out(g.out[0], depth, n * 8);
+    uint8_t* d_hit = st.out(g.out[1], hit, n);
+    int32_t* d_iters = st.out(g.out[2], iters, n * 4);
+    double* d_cursor = st.out(g.out[3], cursor, n * 8);
+    if ((rc = st.begin())) return rc;
+    rm::CameraParams cam;
+    for (int i = 0; i < 14; ++i) cam.v[i] = d->cam[i];
+    auto go = [&] {
+        HIP_TRY(rm::launch_segment_render(prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_iters, d_cursor, g.stream));
+        return (int)RM_OK;
+    };
     if ((rc = timing ? timed(e, timing, g.stream, go) : go())) return rc;
     return st.finish();
 }

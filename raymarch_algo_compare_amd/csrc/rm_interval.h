@@ -192,6 +192,11 @@ RM_HD Ival i_smooth_intersect(Ival a, Ival b, double k)
     return iv(op_smooth_intersect(a.lo, b.lo, k), op_smooth_intersect(a.hi, b.hi, k));
 }
 
+// op_union / op_subtract / op_intersect: min and max are monotone, end for end
+RM_HD Ival i_union(Ival a, Ival b) { return iv(py_min(a.lo, b.lo), py_min(a.hi, b.hi)); }
+RM_HD Ival i_subtract(Ival a, Ival b) { return iv(py_max(a.lo, -b.hi), py_max(a.hi, -b.lo)); }
+RM_HD Ival i_intersect(Ival a, Ival b) { return iv(py_max(a.lo, b.lo), py_max(a.hi, b.hi)); }
+
 // ---- the interpreter ----------------------------------------------------------------------------------------------
 #define RM_IV_GET(i, r)                                                                                                 \
     do {                                                                                                                \
@@ -278,9 +283,9 @@ RM_HD Ival program_eval_interval(const Src& src, IVec3 p)
             } else {                                                                 // combinators: d1 = a, d2 = b
                 RM_IV_GET(slot + 1, b);
                 switch (op) {
-                    case RM_SOP_UNION: r = iv(py_min(a.lo, b.lo), py_min(a.hi, b.hi)); break;
-                    case RM_SOP_SUBTRACT: r = iv(py_max(a.lo, -b.hi), py_max(a.hi, -b.lo)); break;
-                    case RM_SOP_INTERSECT: r = iv(py_max(a.lo, b.lo), py_max(a.hi, b.hi)); break;
+                    case RM_SOP_UNION: r = i_union(a, b); break;
+                    case RM_SOP_SUBTRACT: r = i_subtract(a, b); break;
+                    case RM_SOP_INTERSECT: r = i_intersect(a, b); break;
                     case RM_SOP_SMOOTH_UNION: r = i_smooth_union(a, b, src.k(ko)); break;
                     case RM_SOP_SMOOTH_SUBTRACT: r = i_smooth_subtract(a, b, src.k(ko)); break;
                     default: r = i_smooth_intersect(a, b, src.k(ko)); break;

@@ -95,3 +95,50 @@ def score_capture(method: Dict, reference: Dict, *, compute_ssim: bool = False) 
     report["secondary"] = {"depth": report["depth"], "normal": report["normal"]}
     report["tertiary"] = report["ssim"]
     return report
+
+
+# ---- the calibration residual (the reference's gpu/oracle_calibration.py: silhouette_band, residual) ---------------------
+
+def _grow(mask: np.ndarray, k: int) -> np.ndarray:
+    """the mask grown k times by its 4-neighbourhood"""
+    m = _mask(mask).copy()
+    for _ in range(int(k)):
+        g = m.copy()
+        g[1:, :] |= m[:-1, :]
+        g[:-1, :] |= m[1:, :]
+        g[:, 1:] |= m[:, :-1]
+        g[:, :-1] |= m[:, 1:]
+        m = g
+    return m
+
+
+def silhouette_band(hit, k: int = 2) -> np.ndarray:
+    """Pixels within k (4-connected steps) of the boundary of a hit mask: hit pixels next to a miss and misses next to a
+    hit, grown k times."""
+    h = _mask(hit)
+    edge = (_grow(~h, 1) & h) | (_grow(h, 1) & ~h)
+    return _grow(edge, k)
+
+
+def residual(method_hit, method_depth, truth_hit, truth_depth, band) -> Dict[str, float]:
+    """A method's frame against the truth's, with the reference's keys: iou (0 over an empty union, as the reference
+    divides by max(union, 1)), core_iou (outside `band`), false_hit (of the method's hits), false_miss (of the truth's),
+    depth_rmse / depth_med / depth_p95 / depth_signed over the co-hit pixels (NaN without any) and the three counts."""
+    mine, truth, core = _mask(method_hit), _mask(truth_hit), ~_mask(band)
+    both, either = mine & truth, mine | truth
+    n_mine, n_truth, n_both = int(mine.sum()), int(truth.sum()), int(both.sum())
+    out = {
+        "iou": n_both / max(int(either.sum()), 1),
+        "core_iou": int((both & core).sum()) / max(int((either & core).sum()), 1),
+        "false_hit": int((mine & ~truth).sum()) / max(n_mine, 1),
+        "false_miss": int((truth & ~mine).sum()) / max(n_truth, 1),
+    }
+    if n_both:
+        gap = np.asarray(method_depth, dtype=np.float64)[both] - np.asarray(truth_depth, dtype=np.float64)[both]
+        mag = np.abs(gap)
+        out.update(depth_rmse=float(np.sqrt(np.mean(gap * gap))), depth_med=float(np.median(mag)),
+                   depth_p95=float(np.percentile(mag, 95)), depth_signed=float(np.mean(gap)))
+    else:
+        out.update(depth_rmse=NAN, depth_med=NAN, depth_p95=NAN, depth_signed=NAN)
+    out.update(n_analytic_hit=n_truth, n_method_hit=n_mine, n_co_hit=n_both)
+    return out

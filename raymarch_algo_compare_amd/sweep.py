@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import interval_oracle, registry, scoring
+from . import faithful_segment, interval_oracle, registry, scoring
 from .camera import Camera
 from .collector import HipCollector
 from .config import MarchConfig
@@ -72,6 +72,12 @@ ROW_FIELDS = ["scene", "strategy", "params", "viewpoint", "category", "sweep_axi
 ORACLE_FIELDS = ["oracle_iou", "oracle_false_hit", "oracle_false_miss", "oracle_depth_mae", "oracle_depth_rmse",
                  "oracle_depth_p95"]
 ORACLES = ("interval",)
+# with a ceiling (run_sweep(ceiling="segment")): the sound segment tracer's frame of the viewpoint (faithful_segment.
+# faithful_capture) against the interval oracle's (scoring.residual) and its steps over the hit rays -- what a tracer that
+# cannot tunnel reaches there and pays for it; the same four values on every row of a scene and viewpoint, empty cells for a
+# scene without an interval extension
+CEILING_FIELDS = ["ceiling_iou", "ceiling_depth_med", "ceiling_iters_median", "ceiling_iters_p95"]
+CEILINGS = ("segment",)
 
 
 def build_levels(mode: str, *, budgets: Sequence[int] = DEFAULT_BUDGETS, epsilons: Sequence[float] = DEFAULT_EPSILONS,
@@ -102,10 +108,12 @@ def finest_index(mode: str, levels) -> int:
 
 
 def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, width: int, height: int, grid: bool = False,
-               oracle_frames: Optional[Dict[str, Optional[Dict]]] = None) -> List[Dict]:
+               oracle_frames: Optional[Dict[str, Optional[Dict]]] = None,
+               ceiling_cols: Optional[Dict[str, Dict]] = None) -> List[Dict]:
     """All viewpoints x parameter combos x levels of one (scene, strategy) in one batched launch -> one row per
     frame.  `grid` brute-forces the strategy's tunable parameters (reference sweep.py:181,222-223).  `oracle_frames`
-    (viewpoint name -> oracle capture, None without one) adds the ORACLE_FIELDS columns."""
+    (viewpoint name -> oracle capture, None without one) adds the ORACLE_FIELDS columns, `ceiling_cols` (viewpoint name ->
+    CEILING_FIELDS values) those."""
     from .runner import GPURunner
     vps = viewpoints_for(scene)
     combos = param_combos(strategy.key) if grid else [{}]
@@ -143,6 +151,8 @@ def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, widt
         })
         if oracle_frames is not None:
             rows[-1].update(oracle_columns({"hit": st.hit_map, "depth": st.depth_map}, oracle_frames.get(vp.name)))
+        if ceiling_cols is not None:
+            rows[-1].update(ceiling_cols[vp.name])
     return rows
 
 
@@ -166,18 +176,44 @@ def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float) -
             for vp in vps}
 
 
+def ceiling_columns(frame: Optional[Dict], oracle: Optional[Dict]) -> Dict:
+    """CEILING_FIELDS of one faithful_capture frame against the oracle capture of its viewpoint; None (empty cells) without
+    them."""
+    if frame is None or oracle is None:
+        return {k: None for k in CEILING_FIELDS}
+    res = scoring.residual(frame["hit"], frame["depth"], oracle["hit"], oracle["depth"], scoring.silhouette_band(oracle["hit"], k=2))
+    c = faithful_segment.cost(frame)
+    return {"ceiling_iou": res["iou"], "ceiling_depth_med": res["depth_med"], "ceiling_iters_median": c["iters_median"],
+            "ceiling_iters_p95": c["iters_p95"]}
+
+
+def ceiling_columns_for(scene, width: int, height: int, oracle_frames: Dict[str, Optional[Dict]], tol: float) -> Dict[str, Dict]:
+    """ceiling_columns of every curated viewpoint of `scene` (oracle_frames: oracle_frames_for of the same scene and size)."""
+    out = {}
+    for vp in viewpoints_for(scene):
+        truth = oracle_frames.get(vp.name)
+        frame = None if truth is None else faithful_segment.faithful_capture(
+            scene, Camera(vp.position, vp.target, vp.up, 60.0, width, height), tol=tol)
+        out[vp.name] = ceiling_columns(frame, truth)
+    return out
+
+
 def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optional[Sequence[str]] = None, mode: str = "budget",
               width: int = 384, height: int = 384, budgets: Sequence[int] = DEFAULT_BUDGETS,
               epsilons: Sequence[float] = DEFAULT_EPSILONS, cap: int = 512, hit_threshold: float = 1e-4,
               out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False,
-              oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL) -> List[Dict]:
+              oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL,
+              ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
     interval oracle's first hit of its viewpoint (ORACLE_FIELDS; one oracle frame per scene and viewpoint, tolerance
-    `oracle_tol`)."""
+    `oracle_tol`).  ceiling="segment": every row also carries the sound segment tracer's result at its viewpoint
+    (CEILING_FIELDS; hit tolerance `ceiling_tol`, scored against the interval oracle at `oracle_tol`)."""
     if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
         raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
+    if ceiling is not None and ceiling not in CEILINGS:
+        raise ValueError(f"unknown ceiling {ceiling!r}: one of {CEILINGS}")
     scenes = registry.get_all_scenes() if not scene_names else [_need(registry.get_scene_by_name(n), "scene", n) for n in scene_names]
     strats = ([registry.get_strategy_by_name(k) for k in registry.list_strategies()] if not strategy_names
               else [_need(registry.get_shader_strategy(n) or registry.get_strategy_by_name(n), "strategy", n) for n in strategy_names])
@@ -185,11 +221,13 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     collector = HipCollector(MarchConfig(), device_id=device_id)
     rows: List[Dict] = []
     for scene in scenes:
-        ofr = oracle_frames_for(scene, width, height, oracle, oracle_tol) if oracle is not None else None
+        truth = oracle_frames_for(scene, width, height, "interval", oracle_tol) if oracle is not None or ceiling is not None else None
+        ofr = truth if oracle is not None else None
+        ccols = ceiling_columns_for(scene, width, height, truth, ceiling_tol) if ceiling is not None else None
         for strat in strats:
             if strat.has_lipschitz:
                 strat.lipschitz = scene.known_lipschitz_bound() or 1.0      # run_once wiring (reference main.py:58-61)
-            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid, ofr)
+            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid, ofr, ccols)
             rows.extend(cell)
             if verbose:
                 print(f"{scene.name:24s} {strat.short_name:24s} {len(cell):3d} frames  "
@@ -204,7 +242,8 @@ def write_rows(rows: List[Dict], path: str) -> None:
         with open(path, "w", encoding="utf-8") as f:
             json.dump(rows, f, indent=1, ensure_ascii=False)
         return
-    fields = ROW_FIELDS + ORACLE_FIELDS if rows and "oracle_iou" in rows[0] else ROW_FIELDS
+    fields = ROW_FIELDS + (ORACLE_FIELDS if rows and "oracle_iou" in rows[0] else []) + \
+        (CEILING_FIELDS if rows and "ceiling_iou" in rows[0] else [])
     with open(path, "w", newline="", encoding="utf-8") as f:
         w = csv.DictWriter(f, fieldnames=fields)
         w.writeheader()
@@ -233,10 +272,14 @@ def main(argv=None) -> int:
     ap.add_argument("--oracle", default=None, choices=list(ORACLES),
                     help="score every frame against a sound first-hit oracle (adds the oracle_* columns)")
     ap.add_argument("--oracle-tol", type=float, default=interval_oracle.DEFAULT_TOL, help="the oracle's hit tolerance")
+    ap.add_argument("--ceiling", default=None, choices=list(CEILINGS),
+                    help="add the sound segment tracer's result per scene and viewpoint (the ceiling_* columns)")
+    ap.add_argument("--ceiling-tol", type=float, default=faithful_segment.DEFAULT_TOL, help="the ceiling tracer's hit tolerance")
     a = ap.parse_args(argv)
     rows = run_sweep([s for s in a.scenes.split(",") if s], [s for s in a.strategies.split(",") if s], a.mode, a.width, a.height,
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
-                     a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol)
+                     a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol,
+                     ceiling=a.ceiling, ceiling_tol=a.ceiling_tol)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 

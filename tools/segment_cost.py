@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""Per-frame cost of the sound segment tracer (rm_segment_render) on the GPU next to the interval oracle
+(rm_interval_render) and the Standard sphere tracer (rm_render) of the same frame, in one process: kernel ms per frame
+(hipEvent timing, median of `--repeats` after `--warmup`) and the tracer's iters over the hit rays (median / p95 / max)
+for the 14 catalogue scenes with an interval extension, on each scene's default camera (its suggested camera, else
+(0, 0, 5) looking at the origin; fov 60), at the given sizes.  No time is gated: there is no earlier version of the
+tracer and the reference's NumPy loop is not a time to compare with.  Writes one JSON line per scene and size to `--out`
+and prints a markdown table ("Segment ceiling").  Only the two-pass evaluation (the point, then
+the segment) is built, so one form is timed.
+
+Usage:  python tools/segment_cost.py [--sizes 512x512,1920x1080] [--repeats 7] [--warmup 2] [--out profiles/segment/cost.jsonl]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+from raymarch_algo_compare_amd import _native, registry  # noqa: E402
+from raymarch_algo_compare_amd.camera import Camera  # noqa: E402
+from raymarch_algo_compare_amd import faithful_segment as fs  # noqa: E402
+
+
+def commit() -> str:
+    try:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
+    except (OSError, subprocess.CalledProcessError):
+        return "unknown"
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="512x512,1920x1080")
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segment", "cost.jsonl"))
+    ap.add_argument("--label", default=None, help="what the library was built from (default: git's short HEAD)")
+    a = ap.parse_args()
+    if a.repeats < 7:
+        ap.error("--repeats must be at least 7")
+    _native.init(0)
+    label = a.label or commit()
+    sizes = [tuple(int(v) for v in s.split("x")) for s in a.sizes.split(",")]
+    standard = registry.STRATEGIES["Standard"]
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    print("| scene | size | segment ms | interval ms | Standard ms | iters median | p95 | max | budget used up | hit pixels |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    with open(a.out, "w", encoding="utf-8") as f:
+        for scene in registry.get_all_scenes():
+            if not _native.segment_supported(scene.id):
+                continue
+            pos = scene.camera_position or (0.0, 0.0, 5.0)
+            tgt = scene.camera_target or (0.0, 0.0, 0.0)
+            for W, H in sizes:
+                cam = Camera(pos, tgt, (0.0, 1.0, 0.0), 60.0, W, H).params14()
+                seg = _native.segment_render(scene.id, cam, W, H, warmup=a.warmup, repeats=a.repeats)
+                ivl = _native.interval_render(scene.id, cam, W, H, warmup=a.warmup, repeats=a.repeats)
+                std = _native.render(_native.make_desc(scene.id, standard, cam, W, H), warmup=a.warmup, repeats=a.repeats)
+                hit = seg["hit"] > 0
+                c = fs.cost({"iters": seg["iters"], "hit": hit})
+                spent = int((~hit & (seg["iters"] >= 4096)).sum())
+                row = {"commit": label, "scene": scene.name, "width": W, "height": H, "repeats": a.repeats, "warmup": a.warmup,
+                       "segment_ms": seg["timing"]["ms_median"], "segment_ms_each": seg["timing"]["ms_each"],
+                       "interval_ms": ivl["timing"]["ms_median"], "standard_ms": std["timing"]["ms_median"],
+                       "evaluation": "two-pass", **c, "budget_used_up": spent, "hit_pixels": int(hit.sum())}
+                f.write(json.dumps(row) + "\n")
+                f.flush()
+                print(f"| {scene.name} | {W}x{H} | {row['segment_ms']:.3f} | {row['interval_ms']:.3f} | {row['standard_ms']:.3f} | "
+                      f"{c['iters_median']:.0f} | {c['iters_p95']:.0f} | {c['iters_max']} | {spent} | {row['hit_pixels']} |", flush=True)
+
+
+if __name__ == "__main__":
+    main()
