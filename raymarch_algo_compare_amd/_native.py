@@ -343,6 +343,38 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _ref(record):
+    """byref of an optional ctypes record (NULL for None)"""
+    return ctypes.byref(record) if record is not None else None
+
+
+def _timing(warmup, repeats):
+    """RmTiming for repeats > 0, else None (an untimed call)"""
+    if repeats <= 0:
+        return None
+    tm = RmTiming()
+    tm.warmup, tm.repeats = int(warmup), int(repeats)
+    return tm
+
+
+def _rays(origins, dirs):
+    """(origins, dirs) as contiguous (n, 3) float64 arrays of one shape"""
+    origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    if origins.shape != dirs.shape:
+        raise ValueError("origins and dirs differ in shape")
+    return origins, dirs
+
+
+def _frame_maps(d: RmFrameDesc, tm, **maps) -> dict:
+    """the flat per-pixel outputs of a render of `d` as (rows, width[, 3]) arrays, with `timing` for a timed call"""
+    shape = (int(d.rows), int(d.width))
+    out = {k: a.reshape(shape + a.shape[1:]) for k, a in maps.items()}
+    if tm is not None:
+        out["timing"] = timing_dict(tm)
+    return out
+
+
 def timing_dict(t: RmTiming) -> dict:
     return {"warmup": t.warmup, "repeats": t.repeats, "ms_median": float(t.ms_median),
             "ms_mean": float(t.ms_mean), "ms_min": float(t.ms_min), "ms_max": float(t.ms_max),
@@ -372,16 +404,12 @@ def render(desc: RmFrameDesc, want_t_raw=False, want_final_sdf=False, want_block
     if want_block_var:
         out["block_var"] = np.empty((rows // 4, W // 8), np.int64)
     st = RmStats()
-    tm = None
-    if repeats > 0:
-        tm = RmTiming()
-        tm.warmup, tm.repeats = int(warmup), int(repeats)
+    tm = _timing(warmup, repeats)
     def addr(a):
         return None if a is None else a.ctypes.data
     o = RmOutputs(addr(out["depth"]), addr(out["iters"]), addr(out["hit"]), addr(out["t_raw"]), addr(out["final_sdf"]),
                   addr(out["block_var"]), addr(out["evals"]))
-    check(L.rm_render_outputs(ctypes.byref(desc), ctypes.byref(o), ctypes.byref(st),
-                              ctypes.byref(tm) if tm is not None else None))
+    check(L.rm_render_outputs(ctypes.byref(desc), ctypes.byref(o), ctypes.byref(st), _ref(tm)))
     out["stats"] = stats_dict(st)
     out["timing"] = timing_dict(tm) if tm is not None else None
     return out
@@ -506,15 +534,12 @@ def interval_sdf_eval(scene_id: int, lo, hi):
 def interval_march_rays(scene_id: int, origins, dirs, cfg: RmIntervalConfig | None = None, want_normals=True):
     """rm_interval_march_rays: (t (+inf on a miss), steps, normals or None) of n explicit rays."""
     L = init()
-    origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
-    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
-    if origins.shape != dirs.shape:
-        raise ValueError("origins and dirs differ in shape")
+    origins, dirs = _rays(origins, dirs)
     n = len(dirs)
     t, steps = np.empty(n), np.empty(n, np.int32)
     normals = np.empty((n, 3)) if want_normals else None
     dp = ctypes.POINTER(ctypes.c_double)
-    check(L.rm_interval_march_rays(int(scene_id), ctypes.byref(cfg) if cfg is not None else None, origins.ctypes.data_as(dp),
+    check(L.rm_interval_march_rays(int(scene_id), _ref(cfg), origins.ctypes.data_as(dp),
                                    dirs.ctypes.data_as(dp), n, t.ctypes.data_as(dp), _ptr(steps), _ptr(normals)))
     return t, steps, normals
 
@@ -527,18 +552,9 @@ def interval_render(scene_id: int, cam14, width: int, height: int, cfg: RmInterv
     n = int(width) * int(d.rows)
     depth, hit = np.empty(n), np.empty(n, np.uint8)
     normal, steps = np.empty((n, 3)), np.empty(n, np.int32)
-    tm = None
-    if repeats > 0:
-        tm = RmTiming()
-        tm.warmup, tm.repeats = int(warmup), int(repeats)
-    check(L.rm_interval_render(ctypes.byref(d), ctypes.byref(cfg) if cfg is not None else None, _ptr(depth), _ptr(hit),
-                               _ptr(normal), _ptr(steps), ctypes.byref(tm) if tm is not None else None))
-    shape = (int(d.rows), int(width))
-    out = {"depth": depth.reshape(shape), "hit": hit.reshape(shape), "normal": normal.reshape(shape + (3,)),
-           "steps": steps.reshape(shape)}
-    if tm is not None:
-        out["timing"] = timing_dict(tm)
-    return out
+    tm = _timing(warmup, repeats)
+    check(L.rm_interval_render(ctypes.byref(d), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(normal), _ptr(steps), _ref(tm)))
+    return _frame_maps(d, tm, depth=depth, hit=hit, normal=normal, steps=steps)
 
 
 def segment_config(t_max=0.0, tol=0.0, h0=0.0, kappa=0.0, h_min=0.0, h_max=0.0, k_min=0.0, l_global=0.0, bound_radius=0.0,
@@ -569,14 +585,11 @@ def segment_sdf_eval(scene_id: int, segs):
 def segment_march_rays(scene_id: int, origins, dirs, cfg: RmSegmentConfig | None = None):
     """rm_segment_march_rays: (t (+inf on a miss), iters, cursor) of n explicit rays."""
     L = init()
-    origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
-    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
-    if origins.shape != dirs.shape:
-        raise ValueError("origins and dirs differ in shape")
+    origins, dirs = _rays(origins, dirs)
     n = len(dirs)
     t, iters, cursor = np.empty(n), np.empty(n, np.int32), np.empty(n)
     dp = ctypes.POINTER(ctypes.c_double)
-    check(L.rm_segment_march_rays(int(scene_id), ctypes.byref(cfg) if cfg is not None else None, origins.ctypes.data_as(dp),
+    check(L.rm_segment_march_rays(int(scene_id), _ref(cfg), origins.ctypes.data_as(dp),
                                   dirs.ctypes.data_as(dp), n, t.ctypes.data_as(dp), _ptr(iters), _ptr(cursor)))
     return t, iters, cursor
 
@@ -588,14 +601,6 @@ def segment_render(scene_id: int, cam14, width: int, height: int, cfg: RmSegment
     d = make_desc(scene_id, 0, cam14, width, height, row0, rows)
     n = int(width) * int(d.rows)
     depth, hit, iters, cursor = np.empty(n), np.empty(n, np.uint8), np.empty(n, np.int32), np.empty(n)
-    tm = None
-    if repeats > 0:
-        tm = RmTiming()
-        tm.warmup, tm.repeats = int(warmup), int(repeats)
-    check(L.rm_segment_render(ctypes.byref(d), ctypes.byref(cfg) if cfg is not None else None, _ptr(depth), _ptr(hit),
-                              _ptr(iters), _ptr(cursor), ctypes.byref(tm) if tm is not None else None))
-    shape = (int(d.rows), int(width))
-    out = {"depth": depth.reshape(shape), "hit": hit.reshape(shape), "iters": iters.reshape(shape), "cursor": cursor.reshape(shape)}
-    if tm is not None:
-        out["timing"] = timing_dict(tm)
-    return out
+    tm = _timing(warmup, repeats)
+    check(L.rm_segment_render(ctypes.byref(d), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(iters), _ptr(cursor), _ref(tm)))
+    return _frame_maps(d, tm, depth=depth, hit=hit, iters=iters, cursor=cursor)

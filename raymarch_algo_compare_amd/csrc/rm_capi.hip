@@ -15,6 +15,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 #include "../../include/rm_hip.h"
@@ -476,13 +477,21 @@ rm::LaunchPlan plan_for(const RmFrameDesc* d, int batch_frames = 0, const RmMarc
     return rm::plan_launch(*d, f, batch_frames, configs);
 }
 
+// The camera record of 14 doubles as the kernels take it.
+rm::CameraParams camera_of(const double* cam14)
+{
+    rm::CameraParams c;
+    for (int i = 0; i < 14; ++i) c.v[i] = cam14[i];
+    return c;
+}
+
 // Kernel arguments of one frame of `d` (a batch sets frames / nframes / full / evals itself): pointers and plan fields.
 int make_args(const RmFrameDesc* d, const rm::LaunchPlan& p, float* depth, int32_t* iters, uint8_t* hit, double* traw, double* fs,
               long long* bvar, unsigned long long* stats, rm::KernelArgs* a)
 {
     memset(a, 0, sizeof *a);
     if (int rc = scene_data(d->scene_id, &a->scene_data)) return rc;
-    for (int i = 0; i < 14; ++i) a->single.cam.v[i] = d->cam[i];
+    a->single.cam = camera_of(d->cam);
     a->single.cfg = to_cfg(d->march);
     a->frames = nullptr;
     a->nframes = 1;
@@ -859,6 +868,13 @@ int timed(const Entry&, RmTiming* t, hipStream_t s, Once once)
     for (int i = 0; i < t->repeats; ++i) HIP_TRY(hipEventElapsedTime(&t->ms_each[i], g.ev[2 * i], g.ev[2 * i + 1]));
     summarise(t);
     return RM_OK;
+}
+
+// `once` alone, or under timed() when the caller asked for a timing.
+template <class Once>
+int once_or_timed(const Entry& e, RmTiming* t, hipStream_t s, Once once)
+{
+    return t ? timed(e, t, s, once) : once();
 }
 
 // The events of timed() bracket one whole frame: stats reset, optional tile ordering, render kernel.
@@ -1279,7 +1295,7 @@ int rm_render_batch_outputs(const RmFrameDesc* shape, int32_t nframes, const dou
     // the frame table: one camera + march configuration per frame
     std::vector<rm::FrameParams> fp((size_t)nframes);
     for (int f = 0; f < nframes; ++f) {
-        for (int i = 0; i < 14; ++i) fp[f].cam.v[i] = cams[(size_t)f * 14 + i];
+        fp[f].cam = camera_of(cams + (size_t)f * 14);
         fp[f].cfg = to_cfg(configs ? configs[f] : shape->march);
     }
     Staged st(e);
@@ -1845,6 +1861,29 @@ int interval_program(const Entry&, int id, const void** prog)
     return RM_OK;
 }
 
+// The common head of the rm_interval_* / rm_segment_* calls, in the order every one of them checks: the scene, the
+// call's configuration (`resolve`, an RM_ code), for a render its slice `d` and `timing`, then the Entry, nothing to do
+// for n == 0, the required buffers (`have`, else `missing` is the error) and the device image of the program.  After
+// RM_OK `prog` is NULL exactly when n == 0.
+extern "C++" struct SoundCall {
+    std::optional<Entry> e;
+    const void* prog = nullptr;
+    template <class Resolve>
+    int open(int scene_id, Resolve resolve, const RmFrameDesc* d, const RmTiming* timing, size_t n, bool have, const char* missing)
+    {
+        int rc = interval_check_scene(scene_id);
+        if (rc || (rc = resolve())) return rc;
+        if (d && (rc = check_slice(d, false))) return rc;       // not check_desc: most of its fields mean nothing here
+        if (timing && (rc = check_timing(timing))) return rc;
+        e.emplace();
+        if ((rc = e->rc()) || n == 0) return rc;
+        if (!have) return fail(RM_E_BAD_ARG, "%s", missing);
+        return interval_program(*e, scene_id, &prog);
+    }
+};
+
+int no_config() { return RM_OK; }
+
 }  // namespace
 
 int rm_interval_supported(int scene_id)
@@ -1855,45 +1894,34 @@ int rm_interval_supported(int scene_id)
 
 int rm_interval_sdf_eval(int scene_id, const double* lo, const double* hi, size_t n, double* out_lo, double* out_hi)
 {
-    int rc = interval_check_scene(scene_id);
-    if (rc) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-    if (n == 0) return RM_OK;
-    if (!lo || !hi || !out_lo || !out_hi) return fail(RM_E_BAD_ARG, "NULL buffer");
-    const void* prog = nullptr;
-    if ((rc = interval_program(e, scene_id, &prog))) return rc;
-    Staged st(e);
+    SoundCall c;
+    int rc = c.open(scene_id, no_config, nullptr, nullptr, n, lo && hi && out_lo && out_hi, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
     const double* d_lo = st.in(g.in[0], lo, n * 24);
     const double* d_hi = st.in(g.in[1], hi, n * 24);
     double* d_out_lo = st.out(g.out[0], out_lo, n * 8);
     double* d_out_hi = st.out(g.out[1], out_hi, n * 8);
     if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_interval_sdf(prog, d_lo, d_hi, n, d_out_lo, d_out_hi, g.stream));
+    HIP_TRY(rm::launch_interval_sdf(c.prog, d_lo, d_hi, n, d_out_lo, d_out_hi, g.stream));
     return st.finish();
 }
 
 int rm_interval_march_rays(int scene_id, const RmIntervalConfig* cfg, const double* origins, const double* dirs, size_t n,
                            double* t, int32_t* steps, double* normals)
 {
-    int rc = interval_check_scene(scene_id);
-    if (rc) return rc;
     rm::IntervalParams P;
-    if ((rc = interval_params(scene_id, cfg, &P))) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-    if (n == 0) return RM_OK;
-    if (!origins || !dirs || !t) return fail(RM_E_BAD_ARG, "NULL buffer");
-    const void* prog = nullptr;
-    if ((rc = interval_program(e, scene_id, &prog))) return rc;
-    Staged st(e);
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return interval_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
     const double* d_origins = st.in(g.in[0], origins, n * 24);
     const double* d_dirs = st.in(g.in[1], dirs, n * 24);
     double* d_t = st.out(g.out[0], t, n * 8);
     int32_t* d_steps = st.out(g.out[1], steps, n * 4);
     double* d_normals = st.out(g.out[2], normals, n * 24);
     if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_interval_march(prog, P, d_origins, d_dirs, n, d_t, d_steps, d_normals, g.stream));
+    HIP_TRY(rm::launch_interval_march(c.prog, P, d_origins, d_dirs, n, d_t, d_steps, d_normals, g.stream));
     return st.finish();
 }
 
@@ -1901,34 +1929,25 @@ int rm_interval_render(const RmFrameDesc* d, const RmIntervalConfig* cfg, double
                        int32_t* steps, RmTiming* timing)
 {
     if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    int rc = interval_check_scene(d->scene_id);
-    if (rc) return rc;
     rm::IntervalParams P;
-    if ((rc = interval_params(d->scene_id, cfg, &P))) return rc;
-    if ((rc = check_slice(d, false))) return rc;       // not check_desc: most of its fields mean nothing here
-    if (timing && (rc = check_timing(timing))) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
     const size_t n = (size_t)d->width * (size_t)d->rows;
-    if (n == 0) return RM_OK;
-    if (!depth || !hit) return fail(RM_E_BAD_ARG, "depth and hit are required");
-    const void* prog = nullptr;
-    if ((rc = interval_program(e, d->scene_id, &prog))) return rc;
-    Staged st(e);
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return interval_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
+                    "depth and hit are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
     double* d_depth = st.out(g.out[0], depth, n * 8);
     uint8_t* d_hit = st.out(g.out[1], hit, n);
     double* d_normal = st.out(g.out[2], normal, n * 24);
     int32_t* d_steps = st.out(g.out[3], steps, n * 4);
     if ((rc = st.begin())) return rc;
-    rm::CameraParams cam;
-    for (int i = 0; i < 14; ++i) cam.v[i] = d->cam[i];
-    auto go = [&] {
-        HIP_TRY(rm::launch_interval_render(prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_normal, d_steps, g.stream));
-        return (int)RM_OK;
-    };
+    const rm::CameraParams cam = camera_of(d->cam);
     // (a timed call waits twice: timed() before it reads its events, finish() for the maps)
-    if ((rc = timing ? timed(e, timing, g.stream, go) : go())) return rc;
-    return st.finish();
+    rc = once_or_timed(*c.e, timing, g.stream, [&] {
+        HIP_TRY(rm::launch_interval_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_normal, d_steps, g.stream));
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
 }
 
 // ---- sound segment tracer (rm_segment.h, rm_segment.hip): scenes and programs as the interval oracle ------------------
@@ -1949,43 +1968,32 @@ int rm_segment_supported(int scene_id) { return rm_interval_supported(scene_id);
 
 int rm_segment_sdf_eval(int scene_id, const double* segs, size_t n, double* out)
 {
-    int rc = interval_check_scene(scene_id);
-    if (rc) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-    if (n == 0) return RM_OK;
-    if (!segs || !out) return fail(RM_E_BAD_ARG, "NULL buffer");
-    const void* prog = nullptr;
-    if ((rc = interval_program(e, scene_id, &prog))) return rc;
-    Staged st(e);
+    SoundCall c;
+    int rc = c.open(scene_id, no_config, nullptr, nullptr, n, segs && out, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
     const double* d_segs = st.in(g.in[0], segs, n * 64);
     double* d_out = st.out(g.out[0], out, n * 32);
     if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_segment_sdf(prog, d_segs, n, d_out, g.stream));
+    HIP_TRY(rm::launch_segment_sdf(c.prog, d_segs, n, d_out, g.stream));
     return st.finish();
 }
 
 int rm_segment_march_rays(int scene_id, const RmSegmentConfig* cfg, const double* origins, const double* dirs, size_t n,
                           double* t, int32_t* iters, double* cursor)
 {
-    int rc = interval_check_scene(scene_id);
-    if (rc) return rc;
     rm::SegmentParams P;
-    if ((rc = segment_params(scene_id, cfg, &P))) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-    if (n == 0) return RM_OK;
-    if (!origins || !dirs || !t) return fail(RM_E_BAD_ARG, "NULL buffer");
-    const void* prog = nullptr;
-    if ((rc = interval_program(e, scene_id, &prog))) return rc;
-    Staged st(e);
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return segment_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
     const double* d_origins = st.in(g.in[0], origins, n * 24);
     const double* d_dirs = st.in(g.in[1], dirs, n * 24);
     double* d_t = st.out(g.out[0], t, n * 8);
     int32_t* d_iters = st.out(g.out[1], iters, n * 4);
     double* d_cursor = st.out(g.out[2], cursor, n * 8);
     if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_segment_march(prog, P, d_origins, d_dirs, n, d_t, d_iters, d_cursor, g.stream));
+    HIP_TRY(rm::launch_segment_march(c.prog, P, d_origins, d_dirs, n, d_t, d_iters, d_cursor, g.stream));
     return st.finish();
 }
 
@@ -1993,33 +2001,24 @@ int rm_segment_render(const RmFrameDesc* d, const RmSegmentConfig* cfg, double* 
                       double* cursor, RmTiming* timing)
 {
     if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    int rc = interval_check_scene(d->scene_id);
-    if (rc) return rc;
     rm::SegmentParams P;
-    if ((rc = segment_params(d->scene_id, cfg, &P))) return rc;
-    if ((rc = check_slice(d, false))) return rc;
-    if (timing && (rc = check_timing(timing))) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
     const size_t n = (size_t)d->width * (size_t)d->rows;
-    if (n == 0) return RM_OK;
-    if (!depth || !hit) return fail(RM_E_BAD_ARG, "depth and hit are required");
-    const void* prog = nullptr;
-    if ((rc = interval_program(e, d->scene_id, &prog))) return rc;
-    Staged st(e);
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return segment_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
+                    "depth and hit are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
     double* d_depth = st.out(g.out[0], depth, n * 8);
     uint8_t* d_hit = st.out(g.out[1], hit, n);
     int32_t* d_iters = st.out(g.out[2], iters, n * 4);
     double* d_cursor = st.out(g.out[3], cursor, n * 8);
     if ((rc = st.begin())) return rc;
-    rm::CameraParams cam;
-    for (int i = 0; i < 14; ++i) cam.v[i] = d->cam[i];
-    auto go = [&] {
-        HIP_TRY(rm::launch_segment_render(prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_iters, d_cursor, g.stream));
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, g.stream, [&] {
+        HIP_TRY(rm::launch_segment_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_iters, d_cursor, g.stream));
         return (int)RM_OK;
-    };
-    if ((rc = timing ? timed(e, timing, g.stream, go) : go())) return rc;
-    return st.finish();
+    });
+    return rc ? rc : st.finish();
 }
 
 }  // extern "C"

@@ -12,8 +12,8 @@
 //    oracle", gives the soundness argument of each op and lists where a degenerate value differs from program_eval.
 // Rounding is to nearest, as in the reference: the enclosure is exact in real arithmetic only.
 //
-// Register discipline as program_eval: the eight value intervals and the four saved boxes are named locals reached by
-// selects on the wave-uniform slot number (a struct read through a switch would live in scratch).
+// The walk over the program is program_eval's (program_walk, rm_scene_program.h) with IntervalAlgebra: the eight value
+// intervals and the four saved boxes are its register slots.
 #pragma once
 
 #include "rm_camera.h"
@@ -80,6 +80,14 @@ RM_HD IVec3 ipoint(vec3 p) { return ivec3(iv(p.x, p.x), iv(p.y, p.y), iv(p.z, p.
 RM_HD Ival idot(IVec3 p, vec3 n) { return p.x * n.x + p.y * n.y + p.z * n.z; }
 // _length3 / IVec3.length
 RM_HD Ival ilength3(Ival x, Ival y, Ival z) { return isqrt(isquare(x) + isquare(y) + isquare(z)); }
+
+// seed_segment (gpu/interval_autodiff.py; first_hit builds the same box): the box of ro + rd * [t0, t1]
+RM_HD IVec3 seed_segment(vec3 o, vec3 d, double t0, double t1)
+{
+    const double ax = d.x * t0, bx = d.x * t1, ay = d.y * t0, by = d.y * t1, az = d.z * t0, bz = d.z * t1;
+    return ivec3(iv(np_min(ax, bx), np_max(ax, bx)) + o.x, iv(np_min(ay, by), np_max(ay, by)) + o.y,
+                 iv(np_min(az, bz), np_max(az, bz)) + o.z);
+}
 
 // ---- gpu/interval.py: the metric primitives ---------------------------------------------------------------------------
 RM_HD Ival i_sphere(IVec3 p, double radius) { return ilength3(p.x, p.y, p.z) - radius; }
@@ -198,109 +206,37 @@ RM_HD Ival i_subtract(Ival a, Ival b) { return iv(py_max(a.lo, -b.hi), py_max(a.
 RM_HD Ival i_intersect(Ival a, Ival b) { return iv(py_max(a.lo, b.lo), py_max(a.hi, b.hi)); }
 
 // ---- the interpreter ----------------------------------------------------------------------------------------------
-#define RM_IV_GET(i, r)                                                                                                 \
-    do {                                                                                                                \
-        r.lo = l7; r.lo = (i) == 6 ? l6 : r.lo; r.lo = (i) == 5 ? l5 : r.lo; r.lo = (i) == 4 ? l4 : r.lo;               \
-        r.lo = (i) == 3 ? l3 : r.lo; r.lo = (i) == 2 ? l2 : r.lo; r.lo = (i) == 1 ? l1 : r.lo; r.lo = (i) == 0 ? l0 : r.lo; \
-        r.hi = h7; r.hi = (i) == 6 ? h6 : r.hi; r.hi = (i) == 5 ? h5 : r.hi; r.hi = (i) == 4 ? h4 : r.hi;               \
-        r.hi = (i) == 3 ? h3 : r.hi; r.hi = (i) == 2 ? h2 : r.hi; r.hi = (i) == 1 ? h1 : r.hi; r.hi = (i) == 0 ? h0 : r.hi; \
-    } while (0)
-#define RM_IV_SET1(j, i, x)                                                                                             \
-    do {                                                                                                                \
-        l##j = (i) == j ? (x).lo : l##j; h##j = (i) == j ? (x).hi : h##j;                                               \
-    } while (0)
-#define RM_IB_SET1(j, i, q)                                                                                             \
-    do {                                                                                                                \
-        xl##j = (i) == j ? q.x.lo : xl##j; xh##j = (i) == j ? q.x.hi : xh##j; yl##j = (i) == j ? q.y.lo : yl##j;        \
-        yh##j = (i) == j ? q.y.hi : yh##j; zl##j = (i) == j ? q.z.lo : zl##j; zh##j = (i) == j ? q.z.hi : zh##j;        \
-    } while (0)
-#define RM_IB_GET1(j, i, q)                                                                                             \
-    do {                                                                                                                \
-        q.x.lo = (i) == j ? xl##j : q.x.lo; q.x.hi = (i) == j ? xh##j : q.x.hi; q.y.lo = (i) == j ? yl##j : q.y.lo;     \
-        q.y.hi = (i) == j ? yh##j : q.y.hi; q.z.lo = (i) == j ? zl##j : q.z.lo; q.z.hi = (i) == j ? zh##j : q.z.hi;     \
-    } while (0)
+
+// evaluation over a box (program_walk, rm_scene_program.h)
+struct IntervalAlgebra {
+    typedef Ival Value;
+    typedef IVec3 Point;
+    RM_HD Ival sphere(IVec3 p, double r) const { return i_sphere(p, r); }
+    RM_HD Ival box(IVec3 p, double h0, double h1, double h2) const { return i_box(p, h0, h1, h2); }
+    RM_HD Ival plane(IVec3 p, double n0, double n1, double n2, double offset) const { return i_plane(p, n0, n1, n2, offset); }
+    RM_HD Ival cylinder(IVec3 p, double radius, double half_height) const { return i_cylinder(p, radius, half_height); }
+    RM_HD Ival torus(IVec3 p, double major_radius, double minor_radius) const { return i_torus(p, major_radius, minor_radius); }
+    RM_HD Ival capsule(IVec3 p, vec3 a, vec3 b, double radius) const { return i_capsule(p, a, b, radius); }
+    RM_HD Ival capped_torus(IVec3 p, double sc0, double sc1, double ra, double rb) const { return i_capped_torus(p, sc0, sc1, ra, rb); }
+    RM_HD Ival cone(IVec3 p, double c, double s, double height) const { return i_cone(p, c, s, height); }
+    RM_HD IVec3 translate(IVec3 p, double kx, double ky, double kz) const { return ivec3(p.x - kx, p.y - ky, p.z - kz); }
+    RM_HD Ival repeat(Ival x, double spacing, bool pow2) const { return irepeat_axis(x, spacing, pow2); }
+    RM_HD Ival round(Ival a, double k) const { return a - k; }
+    RM_HD Ival abs(Ival a) const { return iabs_pw(a); }
+    RM_HD Ival union_(Ival a, Ival b) const { return i_union(a, b); }
+    RM_HD Ival subtract(Ival a, Ival b) const { return i_subtract(a, b); }
+    RM_HD Ival intersect(Ival a, Ival b) const { return i_intersect(a, b); }
+    RM_HD Ival smooth_union(Ival a, Ival b, double k) const { return i_smooth_union(a, b, k); }
+    RM_HD Ival smooth_subtract(Ival a, Ival b, double k) const { return i_smooth_subtract(a, b, k); }
+    RM_HD Ival smooth_intersect(Ival a, Ival b, double k) const { return i_smooth_intersect(a, b, k); }
+};
 
 // The interval of the program's value over the box p (same image, words and constants as program_eval).
 template <class Src>
 RM_HD Ival program_eval_interval(const Src& src, IVec3 p)
 {
-    double l0 = 0.0, l1 = 0.0, l2 = 0.0, l3 = 0.0, l4 = 0.0, l5 = 0.0, l6 = 0.0, l7 = 0.0;
-    double h0 = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0, h5 = 0.0, h6 = 0.0, h7 = 0.0;
-    double xl0 = p.x.lo, xh0 = p.x.hi, yl0 = p.y.lo, yh0 = p.y.hi, zl0 = p.z.lo, zh0 = p.z.hi;
-    double xl1 = xl0, xh1 = xh0, yl1 = yl0, yh1 = yh0, zl1 = zl0, zh1 = zh0;
-    double xl2 = xl0, xh2 = xh0, yl2 = yl0, yh2 = yh0, zl2 = zl0, zh2 = zh0;
-    double xl3 = xl0, xh3 = xh0, yl3 = yl0, yh3 = yh0, zl3 = zl0, zh3 = zh0;
-    const int n = src.nops();
-    for (int pc = 0; pc < n; ++pc) {
-        const uint32_t w = src.word(pc);
-        const int slot = (int)((w >> 6) & 15u);
-        const int pslot = (int)((w >> 10) & 7u);
-        int ko = (int)(w >> 16);
-        const int op = (int)(w & 63u);
-        if (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) {
-            if (op == RM_SOP_POP_POINT) {
-                IVec3 r = p;
-                RM_IB_GET1(3, pslot, r); RM_IB_GET1(2, pslot, r); RM_IB_GET1(1, pslot, r); RM_IB_GET1(0, pslot, r);
-                p = r;
-            } else {
-                RM_IB_SET1(0, pslot, p); RM_IB_SET1(1, pslot, p); RM_IB_SET1(2, pslot, p); RM_IB_SET1(3, pslot, p);
-                const double kx = src.k(ko), ky = src.k(ko + 1), kz = src.k(ko + 2);
-                if (op == RM_SOP_TRANSLATE) {
-                    p = ivec3(p.x - kx, p.y - ky, p.z - kz);
-                } else {
-                    if (w & (1u << 13)) p.x = irepeat_axis(p.x, kx, (w & (1u << 6)) != 0);
-                    if (w & (1u << 14)) p.y = irepeat_axis(p.y, ky, (w & (1u << 7)) != 0);
-                    if (w & (1u << 15)) p.z = irepeat_axis(p.z, kz, (w & (1u << 8)) != 0);
-                }
-            }
-            continue;
-        }
-        Ival r;
-        if (op <= RM_SOP_CONE) {                                                     // primitives: push
-            IVec3 q = p;
-            if (w & kProgTranslated) {                                               // fused op_translate
-                q = ivec3(q.x - src.k(ko), q.y - src.k(ko + 1), q.z - src.k(ko + 2));
-                ko += 3;
-            }
-            switch (op) {
-                case RM_SOP_SPHERE: r = i_sphere(q, src.k(ko)); break;
-                case RM_SOP_BOX: r = i_box(q, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
-                case RM_SOP_PLANE: r = i_plane(q, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
-                case RM_SOP_CYLINDER: r = i_cylinder(q, src.k(ko), src.k(ko + 1)); break;
-                case RM_SOP_TORUS: r = i_torus(q, src.k(ko), src.k(ko + 1)); break;
-                case RM_SOP_CAPSULE:
-                    r = i_capsule(q, v3(src.k(ko), src.k(ko + 1), src.k(ko + 2)), v3(src.k(ko + 3), src.k(ko + 4), src.k(ko + 5)),
-                                  src.k(ko + 6));
-                    break;
-                case RM_SOP_CAPPED_TORUS: r = i_capped_torus(q, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
-                default: r = i_cone(q, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
-            }
-        } else {
-            Ival a, b;
-            RM_IV_GET(slot, a);
-            if (op >= RM_SOP_ROUND) {                                                // distance modifiers
-                r = op == RM_SOP_ROUND ? a - src.k(ko) : iabs_pw(a) - src.k(ko);
-            } else {                                                                 // combinators: d1 = a, d2 = b
-                RM_IV_GET(slot + 1, b);
-                switch (op) {
-                    case RM_SOP_UNION: r = i_union(a, b); break;
-                    case RM_SOP_SUBTRACT: r = i_subtract(a, b); break;
-                    case RM_SOP_INTERSECT: r = i_intersect(a, b); break;
-                    case RM_SOP_SMOOTH_UNION: r = i_smooth_union(a, b, src.k(ko)); break;
-                    case RM_SOP_SMOOTH_SUBTRACT: r = i_smooth_subtract(a, b, src.k(ko)); break;
-                    default: r = i_smooth_intersect(a, b, src.k(ko)); break;
-                }
-            }
-        }
-        RM_IV_SET1(0, slot, r); RM_IV_SET1(1, slot, r); RM_IV_SET1(2, slot, r); RM_IV_SET1(3, slot, r);
-        RM_IV_SET1(4, slot, r); RM_IV_SET1(5, slot, r); RM_IV_SET1(6, slot, r); RM_IV_SET1(7, slot, r);
-    }
-    return iv(l0, h0);
+    return program_walk(IntervalAlgebra{}, src, p);
 }
-#undef RM_IV_GET
-#undef RM_IV_SET1
-#undef RM_IB_SET1
-#undef RM_IB_GET1
 
 // ---- gpu/interval_oracle.py ---------------------------------------------------------------------------------------
 
@@ -320,9 +256,7 @@ RM_HD double interval_first_hit(const Src& src, vec3 o, vec3 d, const IntervalPa
     int32_t s = 0;
     while (s < P.max_steps) {
         const double t1 = t + h;
-        const double ax = d.x * t, bx = d.x * t1, ay = d.y * t, by = d.y * t1, az = d.z * t, bz = d.z * t1;
-        const IVec3 box = ivec3(iv(np_min(ax, bx), np_max(ax, bx)) + o.x, iv(np_min(ay, by), np_max(ay, by)) + o.y,
-                                iv(np_min(az, bz), np_max(az, bz)) + o.z);
+        const IVec3 box = seed_segment(o, d, t, t1);
         const Ival f = program_eval_interval(src, box);
         ++s;
         if (f.lo > 0.0) {                      // proven empty: jump and grow the probe

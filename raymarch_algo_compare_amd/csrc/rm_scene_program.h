@@ -45,6 +45,18 @@ struct ProgramImage {
     double k[kProgMaxConst];
 };
 
+// One instruction word of a ProgramImage, decoded (the only place that knows the bit layout besides program_encode).
+struct ProgWord {
+    uint32_t w;
+    RM_HD int op() const { return (int)(w & 63u); }
+    RM_HD int slot() const { return (int)((w >> 6) & 15u); }           // value slot written (a combinator also reads slot + 1)
+    RM_HD int pslot() const { return (int)((w >> 10) & 7u); }          // point slot saved to / restored from
+    RM_HD int ko() const { return (int)(w >> 16); }                    // offset of the constants in k[]
+    RM_HD bool translated() const { return (w & kProgTranslated) != 0; }           // a primitive fused with its translate
+    RM_HD bool axis(int a) const { return (w & (1u << (13 + a))) != 0; }           // RM_SOP_REPEAT: axis a is repeated
+    RM_HD bool pow2(int a) const { return (w & (1u << (6 + a))) != 0; }            // ... with a power-of-two spacing
+};
+
 // constants each opcode reads (RmSceneOp.f)
 RM_HD int program_op_args(int op)
 {
@@ -117,7 +129,127 @@ RM_HD double repeat_axis_any(double x, double spacing, bool pow2)
 
 // ---- the interpreter ----------------------------------------------------------------------------------------------
 
-// The register stacks are plain local variables of program_eval -- eight value slots v0..v7, four saved points
+// N register slots of a T (a record of doubles: double, vec3, Ival, IVec3, DIval), kept lane by lane.  Slot i
+// (wave-uniform) is reached by selects on i (v_cndmask with a scalar mask): after unrolling every index below is a
+// constant, so the array is split into plain locals and nothing can move it to scratch -- selecting whole records
+// instead makes the compiler select an address and load from it, and then the slots live in scratch.
+template <class T, int N>
+struct Slots {
+    static constexpr int kLanes = (int)(sizeof(T) / sizeof(double));
+    static_assert(sizeof(T) == kLanes * sizeof(double), "a slot holds doubles only");
+    double s[N][kLanes];
+
+    RM_HD explicit Slots(const T& x)
+    {
+#pragma unroll
+        for (int j = 0; j < N; ++j) __builtin_memcpy(s[j], &x, sizeof x);
+    }
+    RM_HD T at(int j) const
+    {
+        T r;
+        __builtin_memcpy(&r, s[j], sizeof r);
+        return r;
+    }
+    // slot i; `r` where i is no slot (cannot occur after program_encode)
+    RM_HD T get(int i, T r) const
+    {
+        double t[kLanes];
+        __builtin_memcpy(t, &r, sizeof r);
+#pragma unroll
+        for (int l = 0; l < kLanes; ++l)
+#pragma unroll
+            for (int j = N - 1; j >= 0; --j) t[l] = i == j ? s[j][l] : t[l];
+        __builtin_memcpy(&r, t, sizeof r);
+        return r;
+    }
+    // writes slot i, nothing where i is no slot
+    RM_HD void set(int i, const T& x)
+    {
+        double t[kLanes];
+        __builtin_memcpy(t, &x, sizeof x);
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int l = 0; l < kLanes; ++l) s[j][l] = i == j ? t[l] : s[j][l];
+    }
+};
+
+// The walk over a program image for the two sound evaluations of a program: over a box (IntervalAlgebra, rm_interval.h)
+// and over a box with the derivative along a ray (DualAlgebra, rm_segment.h).  (program_eval below keeps its own loop:
+// DESIGN.md section 3, "Interval oracle".)
+// An algebra names its Value and its Point (a record with members x, y, z) and provides the eight primitives, translate,
+// repeat of one coordinate, the two modifiers and the six combinators; it is an object because the dual one carries the
+// ray's direction.  Src: nops(), word(i) (wave-uniform), k(i).
+template <class A, class Src>
+RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::Point p)
+{
+    typedef typename A::Value V;
+    typedef typename A::Point P;
+    Slots<V, RM_SCENE_PROGRAM_MAX_VALUES> vals{ V() };
+    Slots<P, RM_SCENE_PROGRAM_MAX_POINTS> saved{ p };
+    const int n = src.nops();
+    for (int pc = 0; pc < n; ++pc) {
+        const ProgWord w{ src.word(pc) };
+        const int slot = w.slot(), pslot = w.pslot(), op = w.op();
+        int ko = w.ko();
+        if (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) {
+            if (op == RM_SOP_POP_POINT) {
+                p = saved.get(pslot, p);
+            } else {
+                saved.set(pslot, p);
+                const double kx = src.k(ko), ky = src.k(ko + 1), kz = src.k(ko + 2);
+                if (op == RM_SOP_TRANSLATE) {
+                    p = alg.translate(p, kx, ky, kz);                                // :99-100
+                } else {                                                             // :102-108
+                    if (w.axis(0)) p.x = alg.repeat(p.x, kx, w.pow2(0));
+                    if (w.axis(1)) p.y = alg.repeat(p.y, ky, w.pow2(1));
+                    if (w.axis(2)) p.z = alg.repeat(p.z, kz, w.pow2(2));
+                }
+            }
+            continue;
+        }
+        V r;
+        if (op <= RM_SOP_CONE) {                                                     // primitives: push
+            P q = p;
+            if (w.translated()) {                                                    // fused op_translate (:99-100)
+                q = alg.translate(q, src.k(ko), src.k(ko + 1), src.k(ko + 2));
+                ko += 3;
+            }
+            switch (op) {
+                case RM_SOP_SPHERE: r = alg.sphere(q, src.k(ko)); break;
+                case RM_SOP_BOX: r = alg.box(q, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
+                case RM_SOP_PLANE: r = alg.plane(q, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
+                case RM_SOP_CYLINDER: r = alg.cylinder(q, src.k(ko), src.k(ko + 1)); break;
+                case RM_SOP_TORUS: r = alg.torus(q, src.k(ko), src.k(ko + 1)); break;
+                case RM_SOP_CAPSULE:
+                    r = alg.capsule(q, v3(src.k(ko), src.k(ko + 1), src.k(ko + 2)), v3(src.k(ko + 3), src.k(ko + 4), src.k(ko + 5)),
+                                    src.k(ko + 6));
+                    break;
+                case RM_SOP_CAPPED_TORUS: r = alg.capped_torus(q, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
+                default: r = alg.cone(q, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
+            }
+        } else {
+            const V a = vals.get(slot, vals.at(RM_SCENE_PROGRAM_MAX_VALUES - 1));
+            if (op >= RM_SOP_ROUND) {                                                // distance modifiers
+                r = op == RM_SOP_ROUND ? alg.round(a, src.k(ko)) : alg.round(alg.abs(a), src.k(ko));   // :110-111, :113-114
+            } else {                                                                 // combinators: d1 = a, d2 = b
+                const V b = vals.get(slot + 1, vals.at(RM_SCENE_PROGRAM_MAX_VALUES - 1));
+                switch (op) {
+                    case RM_SOP_UNION: r = alg.union_(a, b); break;                                     // :70
+                    case RM_SOP_SUBTRACT: r = alg.subtract(a, b); break;                                // :73
+                    case RM_SOP_INTERSECT: r = alg.intersect(a, b); break;                              // :77
+                    case RM_SOP_SMOOTH_UNION: r = alg.smooth_union(a, b, src.k(ko)); break;             // :80-86
+                    case RM_SOP_SMOOTH_SUBTRACT: r = alg.smooth_subtract(a, b, src.k(ko)); break;       // :88-89
+                    default: r = alg.smooth_intersect(a, b, src.k(ko)); break;                          // :91-92
+                }
+            }
+        }
+        vals.set(slot, r);
+    }
+    return vals.at(0);
+}
+
+// The point walk.  Its register stacks are plain local variables of program_eval -- eight value slots v0..v7, four saved points
 // (x0, y0, z0) .. (x3, y3, z3) -- and slot i (wave-uniform) is reached by selects on i (v_cndmask with a scalar mask).
 // No access has a computed address, so nothing can move them to scratch: a struct of slots read through a switch or a
 // chain of selects is turned back into a load from a selected address by the compiler, and then lives in scratch.
@@ -146,11 +278,8 @@ RM_HD double program_eval(const Src& src, vec3 p)
     double x2 = p.x, y2 = p.y, z2 = p.z, x3 = p.x, y3 = p.y, z3 = p.z;
     const int n = src.nops();
     for (int pc = 0; pc < n; ++pc) {
-        const uint32_t w = src.word(pc);
-        const int slot = (int)((w >> 6) & 15u);
-        const int pslot = (int)((w >> 10) & 7u);
-        const int ko = (int)(w >> 16);
-        const int op = (int)(w & 63u);
+        const ProgWord w{ src.word(pc) };
+        const int slot = w.slot(), pslot = w.pslot(), ko = w.ko(), op = w.op();
         if (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) {
             if (op == RM_SOP_POP_POINT) {
                 vec3 r = v3(x3, y3, z3);
@@ -164,9 +293,9 @@ RM_HD double program_eval(const Src& src, vec3 p)
                 if (op == RM_SOP_TRANSLATE) {
                     p = p - v3(kx, ky, kz);                                          // :99-100
                 } else {                                                             // :102-108
-                    if (w & (1u << 13)) p.x = repeat_axis_any(p.x, kx, (w & (1u << 6)) != 0);
-                    if (w & (1u << 14)) p.y = repeat_axis_any(p.y, ky, (w & (1u << 7)) != 0);
-                    if (w & (1u << 15)) p.z = repeat_axis_any(p.z, kz, (w & (1u << 8)) != 0);
+                    if (w.axis(0)) p.x = repeat_axis_any(p.x, kx, w.pow2(0));
+                    if (w.axis(1)) p.y = repeat_axis_any(p.y, ky, w.pow2(1));
+                    if (w.axis(2)) p.z = repeat_axis_any(p.z, kz, w.pow2(2));
                 }
             }
             continue;
@@ -174,8 +303,8 @@ RM_HD double program_eval(const Src& src, vec3 p)
         double r;
         if (op <= RM_SOP_CONE) {                                                     // primitives: push
             vec3 p0 = p;
-            int ko = (int)(w >> 16);
-            if (w & kProgTranslated) {                                               // fused op_translate (:99-100)
+            int ko = w.ko();
+            if (w.translated()) {                                               // fused op_translate (:99-100)
                 p = p - v3(src.k(ko), src.k(ko + 1), src.k(ko + 2));
                 ko += 3;
             }

@@ -12,8 +12,6 @@
 //    soundness argument of each rule.
 // A translated or repeated coordinate keeps d/dtau = rd_c, so the point is a box (IVec3) plus the constant direction and
 // the four saved boxes need no derivative slots.  Rounding is to nearest, as in the reference.
-//
-// Register discipline as program_eval_interval: named locals reached by selects on the wave-uniform slot number.
 #pragma once
 
 #include "rm_interval.h"
@@ -94,14 +92,6 @@ RM_HD DVec3 dvec3(IVec3 p, vec3 rd)
 RM_HD IVec3 dvals(DVec3 p) { return ivec3(p.x.val, p.y.val, p.z.val); }
 RM_HD DIval dlength3(DIval x, DIval y, DIval z) { return dsqrt(dsquare(x) + dsquare(y) + dsquare(z)); }     // _length3
 
-// seed_segment: the box of ro + rd * [t0, t1]
-RM_HD IVec3 seed_segment(vec3 o, vec3 d, double t0, double t1)
-{
-    const double ax = d.x * t0, bx = d.x * t1, ay = d.y * t0, by = d.y * t1, az = d.z * t0, bz = d.z * t1;
-    return ivec3(iv(np_min(ax, bx), np_max(ax, bx)) + o.x, iv(np_min(ay, by), np_max(ay, by)) + o.y,
-                 iv(np_min(az, bz), np_max(az, bz)) + o.z);
-}
-
 // ---- gpu/interval.py: the metric primitives over component objects -----------------------------------------------------
 RM_HD DIval d_sphere(DVec3 p, double radius) { return dlength3(p.x, p.y, p.z) - radius; }
 RM_HD DIval d_plane(DVec3 p, double n0, double n1, double n2, double offset) { return p.x * n0 + p.y * n1 + p.z * n2 - offset; }
@@ -175,120 +165,40 @@ RM_HD DIval d_cone(DVec3 p, double c, double s, double height)
 }
 
 // ---- the interpreter ----------------------------------------------------------------------------------------------
-#define RM_DV_GET1(i, r, n)                                                                                          \
-    do {                                                                                                                \
-        r = n##7; r = (i) == 6 ? n##6 : r; r = (i) == 5 ? n##5 : r; r = (i) == 4 ? n##4 : r; r = (i) == 3 ? n##3 : r;   \
-        r = (i) == 2 ? n##2 : r; r = (i) == 1 ? n##1 : r; r = (i) == 0 ? n##0 : r;                                      \
-    } while (0)
-#define RM_DV_GET(i, r)                                                                                                 \
-    do {                                                                                                                \
-        RM_DV_GET1(i, r.val.lo, l); RM_DV_GET1(i, r.val.hi, h);                                                       \
-        RM_DV_GET1(i, r.der.lo, dl); RM_DV_GET1(i, r.der.hi, dh);                                                   \
-    } while (0)
-#define RM_DV_SET1(j, i, x)                                                                                             \
-    do {                                                                                                                \
-        l##j = (i) == j ? (x).val.lo : l##j; h##j = (i) == j ? (x).val.hi : h##j;                                       \
-        dl##j = (i) == j ? (x).der.lo : dl##j; dh##j = (i) == j ? (x).der.hi : dh##j;                                   \
-    } while (0)
-#define RM_DB_SET1(j, i, q)                                                                                             \
-    do {                                                                                                                \
-        xl##j = (i) == j ? q.x.lo : xl##j; xh##j = (i) == j ? q.x.hi : xh##j; yl##j = (i) == j ? q.y.lo : yl##j;        \
-        yh##j = (i) == j ? q.y.hi : yh##j; zl##j = (i) == j ? q.z.lo : zl##j; zh##j = (i) == j ? q.z.hi : zh##j;        \
-    } while (0)
-#define RM_DB_GET1(j, i, q)                                                                                             \
-    do {                                                                                                                \
-        q.x.lo = (i) == j ? xl##j : q.x.lo; q.x.hi = (i) == j ? xh##j : q.x.hi; q.y.lo = (i) == j ? yl##j : q.y.lo;     \
-        q.y.hi = (i) == j ? yh##j : q.y.hi; q.z.lo = (i) == j ? zl##j : q.z.lo; q.z.hi = (i) == j ? zh##j : q.z.hi;     \
-    } while (0)
+
+// evaluation over the box of a ray segment with direction rd (program_walk, rm_scene_program.h).  The point is the
+// interval walk's box; a primitive lifts it to a dual point.  A smooth combinator's partial derivatives are h and 1 - h
+// (h in [0, 1]) up to the signs of its arguments: the hull of the two ders.
+struct DualAlgebra : IntervalAlgebra {
+    typedef DIval Value;
+    vec3 rd;
+    RM_HD DIval sphere(IVec3 p, double r) const { return d_sphere(dvec3(p, rd), r); }
+    RM_HD DIval box(IVec3 p, double h0, double h1, double h2) const { return d_box(dvec3(p, rd), h0, h1, h2); }
+    RM_HD DIval plane(IVec3 p, double n0, double n1, double n2, double offset) const { return d_plane(dvec3(p, rd), n0, n1, n2, offset); }
+    RM_HD DIval cylinder(IVec3 p, double radius, double half_height) const { return d_cylinder(dvec3(p, rd), radius, half_height); }
+    RM_HD DIval torus(IVec3 p, double major_radius, double minor_radius) const { return d_torus(dvec3(p, rd), major_radius, minor_radius); }
+    RM_HD DIval capsule(IVec3 p, vec3 a, vec3 b, double radius) const { return d_capsule(dvec3(p, rd), a, b, radius); }
+    RM_HD DIval capped_torus(IVec3 p, double sc0, double sc1, double ra, double rb) const { return d_capped_torus(dvec3(p, rd), sc0, sc1, ra, rb); }
+    RM_HD DIval cone(IVec3 p, double c, double s, double height) const { return d_cone(dvec3(p, rd), c, s, height); }
+    RM_HD DIval round(DIval a, double k) const { return a - k; }
+    RM_HD DIval abs(DIval a) const { return dabs_pw(a); }
+    RM_HD DIval union_(DIval a, DIval b) const { return dv(i_union(a.val, b.val), min_der(a, b)); }
+    RM_HD DIval subtract(DIval a, DIval b) const { return dv(i_subtract(a.val, b.val), max_der(a, -b)); }
+    RM_HD DIval intersect(DIval a, DIval b) const { return dv(i_intersect(a.val, b.val), max_der(a, b)); }
+    RM_HD DIval smooth_union(DIval a, DIval b, double k) const { return dv(i_smooth_union(a.val, b.val, k), seg_hull(a.der, b.der)); }
+    RM_HD DIval smooth_subtract(DIval a, DIval b, double k) const { return dv(i_smooth_subtract(a.val, b.val, k), seg_hull(a.der, -b.der)); }
+    RM_HD DIval smooth_intersect(DIval a, DIval b, double k) const { return dv(i_smooth_intersect(a.val, b.val, k), seg_hull(a.der, b.der)); }
+};
 
 // The dual interval of the program over the box p of a ray segment with direction rd: val == program_eval_interval(src,
 // p) bit for bit, der encloses d/dtau of the program's value along the ray wherever that derivative exists.
 template <class Src>
 RM_HD DIval program_eval_dual(const Src& src, IVec3 p, vec3 rd)
 {
-    double l0 = 0.0, l1 = 0.0, l2 = 0.0, l3 = 0.0, l4 = 0.0, l5 = 0.0, l6 = 0.0, l7 = 0.0;
-    double h0 = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0, h5 = 0.0, h6 = 0.0, h7 = 0.0;
-    double dl0 = 0.0, dl1 = 0.0, dl2 = 0.0, dl3 = 0.0, dl4 = 0.0, dl5 = 0.0, dl6 = 0.0, dl7 = 0.0;
-    double dh0 = 0.0, dh1 = 0.0, dh2 = 0.0, dh3 = 0.0, dh4 = 0.0, dh5 = 0.0, dh6 = 0.0, dh7 = 0.0;
-    double xl0 = p.x.lo, xh0 = p.x.hi, yl0 = p.y.lo, yh0 = p.y.hi, zl0 = p.z.lo, zh0 = p.z.hi;
-    double xl1 = xl0, xh1 = xh0, yl1 = yl0, yh1 = yh0, zl1 = zl0, zh1 = zh0;
-    double xl2 = xl0, xh2 = xh0, yl2 = yl0, yh2 = yh0, zl2 = zl0, zh2 = zh0;
-    double xl3 = xl0, xh3 = xh0, yl3 = yl0, yh3 = yh0, zl3 = zl0, zh3 = zh0;
-    const int n = src.nops();
-    for (int pc = 0; pc < n; ++pc) {
-        const uint32_t w = src.word(pc);
-        const int slot = (int)((w >> 6) & 15u);
-        const int pslot = (int)((w >> 10) & 7u);
-        int ko = (int)(w >> 16);
-        const int op = (int)(w & 63u);
-        if (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) {                      // the point: as program_eval_interval
-            if (op == RM_SOP_POP_POINT) {
-                IVec3 r = p;
-                RM_DB_GET1(3, pslot, r); RM_DB_GET1(2, pslot, r); RM_DB_GET1(1, pslot, r); RM_DB_GET1(0, pslot, r);
-                p = r;
-            } else {
-                RM_DB_SET1(0, pslot, p); RM_DB_SET1(1, pslot, p); RM_DB_SET1(2, pslot, p); RM_DB_SET1(3, pslot, p);
-                const double kx = src.k(ko), ky = src.k(ko + 1), kz = src.k(ko + 2);
-                if (op == RM_SOP_TRANSLATE) {
-                    p = ivec3(p.x - kx, p.y - ky, p.z - kz);
-                } else {
-                    if (w & (1u << 13)) p.x = irepeat_axis(p.x, kx, (w & (1u << 6)) != 0);
-                    if (w & (1u << 14)) p.y = irepeat_axis(p.y, ky, (w & (1u << 7)) != 0);
-                    if (w & (1u << 15)) p.z = irepeat_axis(p.z, kz, (w & (1u << 8)) != 0);
-                }
-            }
-            continue;
-        }
-        DIval r;
-        if (op <= RM_SOP_CONE) {                                                     // primitives: push
-            IVec3 qb = p;
-            if (w & kProgTranslated) {                                               // fused op_translate
-                qb = ivec3(qb.x - src.k(ko), qb.y - src.k(ko + 1), qb.z - src.k(ko + 2));
-                ko += 3;
-            }
-            const DVec3 q = dvec3(qb, rd);
-            switch (op) {
-                case RM_SOP_SPHERE: r = d_sphere(q, src.k(ko)); break;
-                case RM_SOP_BOX: r = d_box(q, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
-                case RM_SOP_PLANE: r = d_plane(q, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
-                case RM_SOP_CYLINDER: r = d_cylinder(q, src.k(ko), src.k(ko + 1)); break;
-                case RM_SOP_TORUS: r = d_torus(q, src.k(ko), src.k(ko + 1)); break;
-                case RM_SOP_CAPSULE:
-                    r = d_capsule(q, v3(src.k(ko), src.k(ko + 1), src.k(ko + 2)), v3(src.k(ko + 3), src.k(ko + 4), src.k(ko + 5)),
-                                  src.k(ko + 6));
-                    break;
-                case RM_SOP_CAPPED_TORUS: r = d_capped_torus(q, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
-                default: r = d_cone(q, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
-            }
-        } else {
-            DIval a, b;
-            RM_DV_GET(slot, a);
-            if (op >= RM_SOP_ROUND) {                                                // distance modifiers
-                r = op == RM_SOP_ROUND ? a - src.k(ko) : dabs_pw(a) - src.k(ko);
-            } else {                                                                 // combinators: d1 = a, d2 = b
-                RM_DV_GET(slot + 1, b);
-                // a smooth combinator's partial derivatives are h and 1 - h (h in [0, 1]) up to the signs of its
-                // arguments: the hull of the two ders
-                switch (op) {
-                    case RM_SOP_UNION: r = dv(i_union(a.val, b.val), min_der(a, b)); break;
-                    case RM_SOP_SUBTRACT: r = dv(i_subtract(a.val, b.val), max_der(a, -b)); break;
-                    case RM_SOP_INTERSECT: r = dv(i_intersect(a.val, b.val), max_der(a, b)); break;
-                    case RM_SOP_SMOOTH_UNION: r = dv(i_smooth_union(a.val, b.val, src.k(ko)), seg_hull(a.der, b.der)); break;
-                    case RM_SOP_SMOOTH_SUBTRACT: r = dv(i_smooth_subtract(a.val, b.val, src.k(ko)), seg_hull(a.der, -b.der)); break;
-                    default: r = dv(i_smooth_intersect(a.val, b.val, src.k(ko)), seg_hull(a.der, b.der)); break;
-                }
-            }
-        }
-        RM_DV_SET1(0, slot, r); RM_DV_SET1(1, slot, r); RM_DV_SET1(2, slot, r); RM_DV_SET1(3, slot, r);
-        RM_DV_SET1(4, slot, r); RM_DV_SET1(5, slot, r); RM_DV_SET1(6, slot, r); RM_DV_SET1(7, slot, r);
-    }
-    return dv(iv(l0, h0), iv(dl0, dh0));
+    DualAlgebra alg;
+    alg.rd = rd;
+    return program_walk(alg, src, p);
 }
-#undef RM_DV_GET1
-#undef RM_DV_GET
-#undef RM_DV_SET1
-#undef RM_DB_SET1
-#undef RM_DB_GET1
 
 // ---- gpu/faithful_offline.py -----------------------------------------------------------------------------------------
 

@@ -10,9 +10,6 @@ themselves.  Scalar spills go to VGPR lanes (v_writelane / v_readlane), not to m
 interpreter hold 58-122 of them (the catalogue's Pillar Forest 62-100)."""
 import importlib.util
 import os
-import re
-import subprocess
-import tempfile
 
 import pytest
 
@@ -38,21 +35,7 @@ def kernels():
 @pytest.fixture(scope="module")
 def memory_ops():
     """symbol -> scratch / buffer instructions of every function in the code object"""
-    tool = _tool()
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for co in tool.code_objects(OBJ, td):
-            dis = subprocess.run([os.path.join(tool.LLVM, "llvm-objdump"), "-d", co], check=True, capture_output=True,
-                                 text=True).stdout
-            cur = None
-            for line in dis.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-                if m:
-                    cur = m.group(1)
-                    found.setdefault(cur, [])
-                elif cur and re.search(r"\b(scratch|buffer)_(load|store)", line):
-                    found[cur].append(line.strip())
-    return found
+    return _tool().matching_instructions(OBJ, r"\b(scratch|buffer)_(load|store)")
 
 
 def test_every_form_is_built(kernels):

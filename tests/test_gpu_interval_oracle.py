@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_interval_host import (CATALOGUE_IDS, _cfg, bits, check_frame, frame_cases, host_eval, host_march, host_render,
+from test_interval_host import (CATALOGUE_IDS, DEEP_PROGRAMS, _cfg, bits, check_frame, frame_cases, host_eval, host_march, host_render,
                                 load_host_lib, ray_cases)
 
 from raymarch_algo_compare_amd import _native, analytic, registry, scoring, sweep
@@ -71,7 +71,7 @@ def test_march_rays_matches_reference():
 def _trees(k=6):
     with open(os.path.join(GOLDEN, "programs_trees.json"), encoding="utf-8") as f:
         trees = json.load(f)["trees"]
-    return [sp.expr_from_json(t) for t in trees[:k]]
+    return [sp.expr_from_json(t) for t in trees[:k]] + [e for _, e in DEEP_PROGRAMS]
 
 
 def _compare(host, sid_dev, expr, scene_bound, cam14, W, H, what):

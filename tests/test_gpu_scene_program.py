@@ -99,6 +99,27 @@ def test_sdf_eval_matches_reference_bits(hip, tree_programs):
         assert sha(out) == want_sha, (i, "a result beyond the stored bits differs")
 
 
+def test_deep_program_is_the_fold_of_its_primitives(hip):
+    """value slots 6-7 and point slot 3 (test_interval_host.py: DEEP): a union selects exactly, so the program's value is
+    the py_min fold of its eight primitives under the same transforms, bit for bit; FUSED likewise from its two halves"""
+    from test_interval_host import DEEP, DEEP_PRIMS, FUSED, deep_wrap, fold_min
+    pts = np.random.default_rng(77).uniform(-6.0, 6.0, size=(3000, 3))
+    ids = [_create(deep_wrap(prim)) for prim in DEEP_PRIMS] + [_create(DEEP), _create(FUSED)]
+    try:
+        vals = [hip.sdf_eval(i, pts) for i in ids]
+    finally:
+        for i in ids:
+            _native.scene_program_destroy(i)
+    assert np.array_equal(vals[8].view(np.uint64), fold_min(vals[:8]).view(np.uint64))
+    torus, box = _create(sp.op_translate((0.4, -0.3, 0.2), sp.sd_torus(0.8, 0.2))), _create(sp.sd_box((0.3, 0.5, 0.2)))
+    try:
+        a, b = hip.sdf_eval(torus, pts), hip.sdf_eval(box, pts)
+    finally:
+        _native.scene_program_destroy(torus)
+        _native.scene_program_destroy(box)
+    assert np.array_equal(vals[9].view(np.uint64), np.where(b < a, b, a).view(np.uint64))
+
+
 def test_frames_match_reference_all_strategies(hip, tree_programs):
     doc = _trees()
     z = np.load(os.path.join(GOLDEN, "programs_frames.npz"))

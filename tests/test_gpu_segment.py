@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from test_interval_host import DEEP_PROGRAMS
 from test_segment_host import (CATALOGUE_IDS, bits, check_frame, dsdf_cases, frame_cases, host_eval, host_march, host_render,
                                load_host_lib, random_segments, ray_cases, seg_cfg)
 
@@ -82,7 +83,7 @@ def test_sdf_eval_matches_reference():
 def _trees(k=6):
     with open(os.path.join(GOLDEN, "programs_trees.json"), encoding="utf-8") as f:
         trees = json.load(f)["trees"]
-    return [sp.expr_from_json(t) for t in trees[:k]]
+    return [sp.expr_from_json(t) for t in trees[:k]] + [e for _, e in DEEP_PROGRAMS]
 
 
 def _compare(host, sid_dev, expr, scene_bound, cam14, W, H, what):

@@ -206,7 +206,63 @@ def _programs():
     return out
 
 
-PROGRAMS = _programs()
+# The programs above reach value slots 0-5 and point slots 0-2 only.  DEEP fills both register stacks: eight distinct
+# primitives pushed before any combinator (value slots 0-7), seven op_unions, all under four nested transforms (point
+# slots 0-3; the inner translate holds the union tree, so program_encode fuses nothing).  FUSED is a small program whose
+# `translate, primitive, pop point` does get fused into one word.
+DEEP_PRIMS = [sp.sd_sphere(0.6), sp.sd_box((0.5, 0.3, 0.4)), sp.sd_plane((0.0, 1.0, 0.0), -0.8), sp.sd_cylinder(0.3, 0.7),
+              sp.sd_torus(0.9, 0.15), sp.sd_capsule((-0.4, 0.1, 0.2), (0.5, 0.6, -0.3), 0.12),
+              sp.sd_capped_torus((0.6, 0.8), 0.7, 0.1), sp.sd_cone(0.5, 0.9)]
+
+
+def deep_wrap(expr):
+    """translate, repeat x by a power of two, repeat y by 3, translate"""
+    return sp.op_translate((0.3, -0.2, 0.1), sp.op_repeat((4.0, 0.0, 0.0), sp.op_repeat((0.0, 3.0, 0.0),
+                           sp.op_translate((-0.15, 0.25, 0.35), expr))))
+
+
+def _deep():
+    tree = DEEP_PRIMS[7]
+    for prim in reversed(DEEP_PRIMS[:7]):
+        tree = sp.op_union(prim, tree)          # postfix: the eight primitives, then the seven unions
+    return deep_wrap(tree)
+
+
+DEEP = _deep()
+FUSED = sp.op_union(sp.op_translate((0.4, -0.3, 0.2), sp.sd_torus(0.8, 0.2)), sp.sd_box((0.3, 0.5, 0.2)))
+DEEP_PROGRAMS = [("tree deep stacks", DEEP), ("tree fused translate", FUSED)]      # "tree": segments inside one cell of the repeats
+PROGRAMS = _programs() + DEEP_PROGRAMS
+
+
+def fold_min(values):
+    """the seven unions of DEEP in program order on arrays: py_min(a, b) = b if b < a else a, innermost pair first"""
+    r = values[7]
+    for a in reversed(values[:7]):
+        r = np.where(r < a, r, a)
+    return r
+
+
+def test_deep_program_shape():
+    """RM_SOP_*: primitives 0-7, union 8, translate 14, repeat 15, pop point 16"""
+    assert [o for o, _ in sp.compile_ops(DEEP)] == [14, 15, 15, 14] + list(range(8)) + [8] * 7 + [16] * 4
+    assert [o for o, _ in sp.compile_ops(FUSED)] == [14, 4, 16, 1, 8]
+
+
+def test_deep_program_is_the_fold_of_its_primitives(lib, prog_lib):
+    """a union selects one of its arguments exactly: the point value and both ends of the enclosure of DEEP are the
+    py_min fold of the eight single-primitive programs under the same transforms, bit for bit"""
+    rng = np.random.default_rng(77)
+    pts = rng.uniform(-6.0, 6.0, size=(3000, 3))
+    edge = 10.0 ** rng.uniform(-6.0, 0.0, size=pts.shape)
+    lo, hi = pts - 0.5 * edge, pts + 0.5 * edge
+    singles = [_ops(deep_wrap(prim)) for prim in DEEP_PRIMS]
+    ops, nops = _ops(DEEP)
+    want = fold_min([pointwise(prog_lib, o, n, pts) for o, n in singles])
+    assert np.array_equal(bits(pointwise(prog_lib, ops, nops, pts)), bits(want))
+    enc = [host_eval(lib, o, n, lo, hi) for o, n in singles]
+    got_lo, got_hi = host_eval(lib, ops, nops, lo, hi)
+    assert np.array_equal(bits(got_lo), bits(fold_min([e[0] for e in enc])))
+    assert np.array_equal(bits(got_hi), bits(fold_min([e[1] for e in enc])))
 
 
 @pytest.mark.parametrize("idx", range(len(PROGRAMS)), ids=[p[0] for p in PROGRAMS])
@@ -423,19 +479,7 @@ def test_code_object_no_scratch_no_spills():
     kernels = [k for k in tool.collect([OBJ]) if "interval_" in k["demangled"]]
     assert sorted(re.search(r"interval_\w+_kernel", k["demangled"]).group(0) for k in kernels) == \
         ["interval_march_kernel", "interval_render_kernel", "interval_sdf_kernel"]
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for co in tool.code_objects(OBJ, td):
-            dis = subprocess.run([os.path.join(tool.LLVM, "llvm-objdump"), "-d", co], check=True, capture_output=True,
-                                 text=True).stdout
-            cur = None
-            for line in dis.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-                if m:
-                    cur = m.group(1)
-                    found.setdefault(cur, [])
-                elif cur and re.search(r"\b(scratch|buffer)_", line):
-                    found[cur].append(line.strip())
+    found = tool.matching_instructions(OBJ, r"\b(scratch|buffer)_")
     for k in kernels:
         assert found.get(k["name"]) == [], (k["demangled"], found.get(k["name"], "not disassembled")[:4])
         assert k["vgpr_spill_count"] == 0, k["demangled"]

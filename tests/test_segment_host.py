@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, build_native
+from test_interval_host import DEEP_PROGRAMS
 
 from raymarch_algo_compare_amd import _native, scoring
 from raymarch_algo_compare_amd import faithful_segment as fs
@@ -196,7 +197,7 @@ def _programs():
     return out
 
 
-PROGRAMS = _programs()
+PROGRAMS = _programs() + DEEP_PROGRAMS      # value slots 6-7 and point slot 3; a fused translate (test_interval_host.py)
 IDS = [p[0] for p in PROGRAMS]
 REGION = 3.0
 
@@ -441,19 +442,7 @@ def test_code_object_no_scratch_no_spills():
     kernels = [k for k in tool.collect([OBJ]) if "_kernel" in k["demangled"]]
     assert sorted(re.search(r"\w+_kernel", k["demangled"]).group(0) for k in kernels) == \
         ["segment_march_kernel", "segment_render_kernel", "segment_sdf_kernel"]
-    found = {}
-    with tempfile.TemporaryDirectory() as td:
-        for co in tool.code_objects(OBJ, td):
-            dis = subprocess.run([os.path.join(tool.LLVM, "llvm-objdump"), "-d", co], check=True, capture_output=True,
-                                 text=True).stdout
-            cur = None
-            for line in dis.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-                if m:
-                    cur = m.group(1)
-                    found.setdefault(cur, [])
-                elif cur and re.search(r"\b(scratch|buffer)_", line):
-                    found[cur].append(line.strip())
+    found = tool.matching_instructions(OBJ, r"\b(scratch|buffer)_")
     for k in kernels:
         assert found.get(k["name"]) == [], (k["demangled"], found.get(k["name"], "not disassembled")[:4])
         assert k["vgpr_spill_count"] == 0, k["demangled"]

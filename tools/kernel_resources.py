@@ -46,6 +46,25 @@ def kernels_of(code_object):
     return [k for k in res if "name" in k]
 
 
+def matching_instructions(obj, pattern):
+    """{symbol: [disassembled lines that `pattern` (a regular expression) matches]} over every function of the gfx950
+    code objects bundled in `obj`; a function without a match has an empty list"""
+    rx = re.compile(pattern)
+    found = {}
+    with tempfile.TemporaryDirectory() as td:
+        for co in code_objects(obj, td):
+            dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
+            cur = None
+            for line in dis.splitlines():
+                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+                if m:
+                    cur = m.group(1)
+                    found.setdefault(cur, [])
+                elif cur and rx.search(line):
+                    found[cur].append(line.strip())
+    return found
+
+
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
     return [re.sub(r"rm::", "", n) for n in out]
