@@ -402,6 +402,34 @@ int rm_segment_march_rays(int scene_id, const RmSegmentConfig* cfg, const double
 int rm_segment_render(const RmFrameDesc* desc, const RmSegmentConfig* cfg, double* depth, uint8_t* hit,
                       int32_t* iters, double* cursor, RmTiming* timing);
 
+/* ---- Affine range (gpu/affine.py) ----------------------------------------------------------------------------------------
+ * The third sound evaluation of a scene over a ray segment: revised affine arithmetic with one noise symbol for the march
+ * parameter (csrc/rm_affine.h), and the interval oracle's march with that range plugged in (the reference's march_count).
+ * What it measures is tightness: SDF segment evaluations (`steps`) needed against rm_interval_render at the same hit map.
+ *   RM_RANGE_AFFINE  the reference's range: range() of the affine form.  Sphere, Grazing Plane, Cube and Thin Torus are
+ *                    its COMPONENT_SCENES over AAForm bit for bit.
+ *   RM_RANGE_MEET    lo = max(lo_affine, lo_interval), hi = min(hi_affine, hi_interval), the interval half being the
+ *                    interval oracle's enclosure of the same segment: sound because both are, per probe at least as tight
+ *                    as either, one more walk over the program per probe.
+ * Scenes, errors, stream and timing conventions: exactly as the interval oracle above.  The march's constants are
+ * RmIntervalConfig's (normal_eps is not used); the mode travels as its own argument, any other value is RM_E_BAD_ARG. */
+#define RM_RANGE_AFFINE 1
+#define RM_RANGE_MEET 2
+/* Same answer as rm_interval_supported.  Host only. */
+int rm_affine_supported(int scene_id);
+/* The range over n ray segments: segs is n x 8 as in rm_segment_sdf_eval; out_range is n x 2 (lo, hi); out_form (n x 3:
+ * x0, x1, e; optional) receives the affine form and must be NULL in RM_RANGE_MEET, whose range is no form's. */
+int rm_affine_range_eval(int scene_id, int mode, const double* segs, size_t n, double* out_range, double* out_form);
+/* march_count over n explicit rays (directions as given).  t: the hit, +inf on a miss.  steps (n int32, optional): the
+ * ray's range evaluations.  cfg may be NULL; its bound_radius is not used here. */
+int rm_affine_march_rays(int scene_id, int mode, const RmIntervalConfig* cfg, const double* origins, const double* dirs,
+                         size_t n, double* t, int32_t* steps);
+/* _capture over rows [row0, row0 + rows) of the frame desc describes (as rm_interval_render, without normals).  Per
+ * pixel: depth (t on a hit, 0 on a miss), hit, steps (optional; 0 for a pruned ray).  The sum of steps is the
+ * reference's eval count. */
+int rm_affine_render(const RmFrameDesc* desc, int mode, const RmIntervalConfig* cfg, double* depth, uint8_t* hit,
+                     int32_t* steps, RmTiming* timing);
+
 /* Same contract, evaluated by wavefront TEAMS (scenes whose SDF is a loop of independent
  * transcendental chains -- Mandelbulb: three waves carry the same 64 rays and each evaluates one
  * chain per trip; see rm_kernels.h).  Identical results; RM_E_BAD_SCENE for scenes without a team form. */

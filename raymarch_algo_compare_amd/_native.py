@@ -35,10 +35,12 @@ EXPORTS = [
     "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy", "rm_debug_math_eval",
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
+    "rm_affine_supported", "rm_affine_range_eval", "rm_affine_march_rays", "rm_affine_render",
 ]
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
 RM_SEGMENT_MAX_STEPS = 40960     # RmSegmentConfig.budget ceiling
+RM_RANGE_AFFINE, RM_RANGE_MEET = 1, 2   # the `mode` of the rm_affine_* calls
 RM_SCENE_PROGRAM_BASE = 1024
 # RmMathFn (include/rm_hip.h): the device math routines rm_debug_math_eval evaluates
 MATH_FNS = {"POW": 0, "POW2": 1, "POW_HALF_DENSE": 2, "POW_HALF_SPARSE": 3, "POW_HALF_GUARD": 4, "SQRT": 5, "SIN": 6,
@@ -253,6 +255,11 @@ def load() -> ctypes.CDLL:
         L.rm_segment_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmSegmentConfig), dp, dp, ctypes.c_size_t, dp, vp, vp]
         L.rm_segment_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmSegmentConfig), vp, vp, vp, vp,
                                         ctypes.POINTER(RmTiming)]
+        L.rm_affine_supported.argtypes = [ctypes.c_int]
+        L.rm_affine_range_eval.argtypes = [ctypes.c_int, ctypes.c_int, dp, ctypes.c_size_t, dp, vp]
+        L.rm_affine_march_rays.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(RmIntervalConfig), dp, dp, ctypes.c_size_t, dp, vp]
+        L.rm_affine_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.c_int, ctypes.POINTER(RmIntervalConfig), vp, vp, vp,
+                                       ctypes.POINTER(RmTiming)]
         for name in EXPORTS:
             if name not in ("rm_shutdown", "rm_last_error", "rm_stats_device_bytes", "rm_default_strategy_params"):
                 getattr(L, name).restype = ctypes.c_int
@@ -545,16 +552,18 @@ def interval_march_rays(scene_id: int, origins, dirs, cfg: RmIntervalConfig | No
 
 
 def interval_render(scene_id: int, cam14, width: int, height: int, cfg: RmIntervalConfig | None = None, row0=0, rows=None,
-                    warmup=0, repeats=0) -> dict:
-    """rm_interval_render: depth (0 on a miss), hit, normal, steps of rows [row0, row0 + rows); `timing` with repeats > 0."""
+                    warmup=0, repeats=0, want_normal=True) -> dict:
+    """rm_interval_render: depth (0 on a miss), hit, normal (unless want_normal is False), steps of rows [row0, row0 + rows);
+    `timing` with repeats > 0."""
     L = init()
     d = make_desc(scene_id, 0, cam14, width, height, row0, rows)
     n = int(width) * int(d.rows)
     depth, hit = np.empty(n), np.empty(n, np.uint8)
-    normal, steps = np.empty((n, 3)), np.empty(n, np.int32)
+    normal, steps = np.empty((n, 3)) if want_normal else None, np.empty(n, np.int32)
     tm = _timing(warmup, repeats)
     check(L.rm_interval_render(ctypes.byref(d), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(normal), _ptr(steps), _ref(tm)))
-    return _frame_maps(d, tm, depth=depth, hit=hit, normal=normal, steps=steps)
+    maps = dict(depth=depth, hit=hit, normal=normal, steps=steps) if want_normal else dict(depth=depth, hit=hit, steps=steps)
+    return _frame_maps(d, tm, **maps)
 
 
 def segment_config(t_max=0.0, tol=0.0, h0=0.0, kappa=0.0, h_min=0.0, h_max=0.0, k_min=0.0, l_global=0.0, bound_radius=0.0,
@@ -604,3 +613,46 @@ def segment_render(scene_id: int, cam14, width: int, height: int, cfg: RmSegment
     tm = _timing(warmup, repeats)
     check(L.rm_segment_render(ctypes.byref(d), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(iters), _ptr(cursor), _ref(tm)))
     return _frame_maps(d, tm, depth=depth, hit=hit, iters=iters, cursor=cursor)
+
+
+def affine_supported(scene_id: int) -> bool:
+    """rm_affine_supported (no GPU needed)."""
+    return load().rm_affine_supported(int(scene_id)) == 1
+
+
+def affine_range_eval(scene_id: int, segs, mode: int = RM_RANGE_AFFINE, want_form=None):
+    """rm_affine_range_eval: ((n, 2) lo, hi; (n, 3) x0, x1, e or None) of the scene's SDF over each ray segment (n x 8:
+    origin, direction, t0, t1).  The form is returned in RM_RANGE_AFFINE unless want_form is False."""
+    L = init()
+    segs = np.ascontiguousarray(segs, dtype=np.float64).reshape(-1, 8)
+    if want_form is None:
+        want_form = int(mode) == RM_RANGE_AFFINE
+    rng = np.empty((len(segs), 2))
+    form = np.empty((len(segs), 3)) if want_form else None
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_affine_range_eval(int(scene_id), int(mode), segs.ctypes.data_as(dp), len(segs), rng.ctypes.data_as(dp), _ptr(form)))
+    return rng, form
+
+
+def affine_march_rays(scene_id: int, origins, dirs, mode: int = RM_RANGE_AFFINE, cfg: RmIntervalConfig | None = None):
+    """rm_affine_march_rays: (t (+inf on a miss), steps) of n explicit rays."""
+    L = init()
+    origins, dirs = _rays(origins, dirs)
+    n = len(dirs)
+    t, steps = np.empty(n), np.empty(n, np.int32)
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_affine_march_rays(int(scene_id), int(mode), _ref(cfg), origins.ctypes.data_as(dp), dirs.ctypes.data_as(dp), n,
+                                 t.ctypes.data_as(dp), _ptr(steps)))
+    return t, steps
+
+
+def affine_render(scene_id: int, cam14, width: int, height: int, mode: int = RM_RANGE_AFFINE, cfg: RmIntervalConfig | None = None,
+                  row0=0, rows=None, warmup=0, repeats=0) -> dict:
+    """rm_affine_render: depth (0 on a miss), hit, steps of rows [row0, row0 + rows); `timing` with repeats > 0."""
+    L = init()
+    d = make_desc(scene_id, 0, cam14, width, height, row0, rows)
+    n = int(width) * int(d.rows)
+    depth, hit, steps = np.empty(n), np.empty(n, np.uint8), np.empty(n, np.int32)
+    tm = _timing(warmup, repeats)
+    check(L.rm_affine_render(ctypes.byref(d), int(mode), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(steps), _ref(tm)))
+    return _frame_maps(d, tm, depth=depth, hit=hit, steps=steps)

@@ -26,6 +26,7 @@
 #include "rm_interval.h"
 #include "rm_interval_catalogue.h"
 #include "rm_segment.h"
+#include "rm_affine.h"
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
 static_assert(RM_NUM_SCENES == 20 && RM_NUM_STRATEGIES == 11 && RM_NUM_STRATEGY_KERNELS == 13, "registry size");
@@ -60,6 +61,13 @@ hipError_t launch_segment_march(const void* prog, const SegmentParams& P, const 
                                 double* t, int32_t* iters, double* cursor, hipStream_t s);
 hipError_t launch_segment_render(const void* prog, const SegmentParams& P, const CameraParams& cam, int width, int height,
                                  int row0, int rows, double* depth, uint8_t* hit, int32_t* iters, double* cursor, hipStream_t s);
+// rm_affine.hip: the affine range and its march (rm_affine_*)
+hipError_t launch_affine_range(const void* prog, int mode, const double* segs, size_t n, double* out_range, double* out_form,
+                               hipStream_t s);
+hipError_t launch_affine_march(const void* prog, int mode, const IntervalParams& P, const double* origins, const double* dirs,
+                               size_t n, double* t, int32_t* steps, hipStream_t s);
+hipError_t launch_affine_render(const void* prog, int mode, const IntervalParams& P, const CameraParams& cam, int width, int height,
+                                int row0, int rows, double* depth, uint8_t* hit, int32_t* steps, hipStream_t s);
 static const SceneLaunchers* scene(int id)
 {
     switch (id) {
@@ -2016,6 +2024,86 @@ int rm_segment_render(const RmFrameDesc* d, const RmSegmentConfig* cfg, double* 
     const rm::CameraParams cam = camera_of(d->cam);
     rc = once_or_timed(*c.e, timing, g.stream, [&] {
         HIP_TRY(rm::launch_segment_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_iters, d_cursor, g.stream));
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
+}
+
+// ---- affine range (rm_affine.h, rm_affine.hip): scenes and programs as the interval oracle -----------------------------
+
+namespace {
+
+int affine_mode(int mode)
+{
+    if (!rm::affine_mode_ok(mode))
+        return fail(RM_E_BAD_ARG, "mode %d is neither RM_RANGE_AFFINE (%d) nor RM_RANGE_MEET (%d)", mode, RM_RANGE_AFFINE, RM_RANGE_MEET);
+    return RM_OK;
+}
+
+// the mode, then the march's constants
+int affine_params(int id, int mode, const RmIntervalConfig* cfg, rm::IntervalParams* P)
+{
+    int rc = affine_mode(mode);
+    return rc ? rc : interval_params(id, cfg, P);
+}
+
+}  // namespace
+
+int rm_affine_supported(int scene_id) { return rm_interval_supported(scene_id); }
+
+int rm_affine_range_eval(int scene_id, int mode, const double* segs, size_t n, double* out_range, double* out_form)
+{
+    SoundCall c;
+    int rc = c.open(scene_id, [&] {
+        int r = affine_mode(mode);
+        if (!r && mode == RM_RANGE_MEET && out_form) r = fail(RM_E_BAD_ARG, "out_form must be NULL in RM_RANGE_MEET: the meet is no form's range");
+        return r;
+    }, nullptr, nullptr, n, segs && out_range, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_segs = st.in(g.in[0], segs, n * 64);
+    double* d_range = st.out(g.out[0], out_range, n * 16);
+    double* d_form = st.out(g.out[1], out_form, n * 24);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_affine_range(c.prog, mode, d_segs, n, d_range, d_form, g.stream));
+    return st.finish();
+}
+
+int rm_affine_march_rays(int scene_id, int mode, const RmIntervalConfig* cfg, const double* origins, const double* dirs, size_t n,
+                         double* t, int32_t* steps)
+{
+    rm::IntervalParams P;
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return affine_params(scene_id, mode, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_origins = st.in(g.in[0], origins, n * 24);
+    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
+    double* d_t = st.out(g.out[0], t, n * 8);
+    int32_t* d_steps = st.out(g.out[1], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_affine_march(c.prog, mode, P, d_origins, d_dirs, n, d_t, d_steps, g.stream));
+    return st.finish();
+}
+
+int rm_affine_render(const RmFrameDesc* d, int mode, const RmIntervalConfig* cfg, double* depth, uint8_t* hit, int32_t* steps,
+                     RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    rm::IntervalParams P;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return affine_params(d->scene_id, mode, cfg, &P); }, d, timing, n, depth && hit,
+                    "depth and hit are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    double* d_depth = st.out(g.out[0], depth, n * 8);
+    uint8_t* d_hit = st.out(g.out[1], hit, n);
+    int32_t* d_steps = st.out(g.out[2], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, g.stream, [&] {
+        HIP_TRY(rm::launch_affine_render(c.prog, mode, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_steps, g.stream));
         return (int)RM_OK;
     });
     return rc ? rc : st.finish();

@@ -248,16 +248,17 @@ struct IntervalParams {
 };
 
 // first_hit for one ray: t of the first segment [t, t + h] whose enclosure reaches 0 with h <= tol, +inf on a miss.
-// `steps`: the loop trips the ray was active for (the reference's active iterations).
-template <class Src>
-RM_HD double interval_first_hit(const Src& src, vec3 o, vec3 d, const IntervalParams& P, int32_t* steps)
+// `steps`: the loop trips the ray was active for (the reference's active iterations).  `range(t, t1)` is the sound
+// enclosure (an Ival) of the scene over the segment: the interval program here, the affine one in rm_affine.h
+// (gpu/affine.py's march_count is this loop with its range function plugged in).
+template <class Range>
+RM_HD double sound_first_hit(const Range& range, const IntervalParams& P, int32_t* steps)
 {
     double t = 0.0, h = P.h0, res = __builtin_inf();
     int32_t s = 0;
     while (s < P.max_steps) {
         const double t1 = t + h;
-        const IVec3 box = seed_segment(o, d, t, t1);
-        const Ival f = program_eval_interval(src, box);
+        const Ival f = range(t, t1);
         ++s;
         if (f.lo > 0.0) {                      // proven empty: jump and grow the probe
             t = t1;
@@ -272,6 +273,12 @@ RM_HD double interval_first_hit(const Src& src, vec3 o, vec3 d, const IntervalPa
     }
     *steps = s;
     return res;
+}
+
+template <class Src>
+RM_HD double interval_first_hit(const Src& src, vec3 o, vec3 d, const IntervalParams& P, int32_t* steps)
+{
+    return sound_first_hit([&](double t, double t1) { return program_eval_interval(src, seed_segment(o, d, t, t1)); }, P, steps);
 }
 
 // _scalar_sdf: the interval program at a degenerate box, lo
