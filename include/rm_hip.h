@@ -635,6 +635,31 @@ int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, u
 int rm_bench_store_path(int32_t width, int32_t rows, void* d_depth, void* d_iters, void* d_hit,
                         RmTiming* timing);
 
+/* ---- SSIM and colour-RMSE scoring of captures (csrc/rm_ssim.h) ---------------------------------------------------
+ * The tertiary tier of the reference's metrics/scoring.py: the structural similarity (Wang et al. 2004, the defaults of
+ * skimage.metrics.structural_similarity: 7 x 7 uniform window, sample covariances, K1 = 0.01, K2 = 0.03, data range 255,
+ * the mean over the windows that lie inside the image) of the 8-bit depth, normal and colour images of two captures, and
+ * the RMSE of their colour images.  The images are made from the float maps exactly as the reference's
+ * data/capture_io.py makes them; the depth images share the reference capture's depth range over its hits.
+ *
+ * The maps of one width x height capture, row-major HOST arrays: depth (W*H), normal and color (W*H*3, interleaved),
+ * hit (W*H, non-zero = hit).  depth and hit are required.  normal, or color, may be NULL in the reference and in every
+ * method alike (captures without that map): the matching outputs are NaN.  NULL on one side only is RM_E_BAD_ARG. */
+typedef struct RmCaptureMaps {
+    const float* depth;
+    const float* normal;
+    const float* color;
+    const uint8_t* hit;
+} RmCaptureMaps;
+/* Scores `nmethods` captures against one reference in one call; out: nmethods x 4 doubles { depth_ssim, normal_ssim,
+ * color_ssim, color_rmse }.  The reference's images are made once.  Window sums are exact integers and every
+ * floating-point sum has a fixed order, so the same inputs give the same bits on every run, and a method scores the same
+ * alone or in a batch.  `timing` (optional) times the kernels -- reference images, tiles, final sums -- without the
+ * copies.  Checked before the device is touched: RM_E_BAD_ARG for a NULL argument or required map, nmethods outside
+ * [1, 65535] or a one-sided NULL map; RM_E_BAD_DIMS for a side below 7 (no window fits) or more than 2^31 - 1 pixels. */
+int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference, const RmCaptureMaps* methods,
+                   int32_t nmethods, double* out, RmTiming* timing);
+
 #ifdef __cplusplus
 }
 #endif

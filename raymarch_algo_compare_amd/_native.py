@@ -36,6 +36,7 @@ EXPORTS = [
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
     "rm_affine_supported", "rm_affine_range_eval", "rm_affine_march_rays", "rm_affine_render",
+    "rm_ssim_scores",
 ]
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
@@ -165,6 +166,11 @@ class RmSegmentConfig(ctypes.Structure):
                 ("bound_radius", ctypes.c_double), ("budget", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class RmCaptureMaps(ctypes.Structure):
+    """The host maps of one capture (include/rm_hip.h): float32 depth / normal / color, uint8 hit; normal and color may be NULL."""
+    _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("color", ctypes.c_void_p), ("hit", ctypes.c_void_p)]
+
+
 class RmDeviceInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 128), ("arch", ctypes.c_char * 64),
                 ("device_id", ctypes.c_int32), ("compute_units", ctypes.c_int32),
@@ -260,6 +266,8 @@ def load() -> ctypes.CDLL:
         L.rm_affine_march_rays.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(RmIntervalConfig), dp, dp, ctypes.c_size_t, dp, vp]
         L.rm_affine_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.c_int, ctypes.POINTER(RmIntervalConfig), vp, vp, vp,
                                        ctypes.POINTER(RmTiming)]
+        L.rm_ssim_scores.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(RmCaptureMaps), ctypes.POINTER(RmCaptureMaps),
+                                     ctypes.c_int32, dp, ctypes.POINTER(RmTiming)]
         for name in EXPORTS:
             if name not in ("rm_shutdown", "rm_last_error", "rm_stats_device_bytes", "rm_default_strategy_params"):
                 getattr(L, name).restype = ctypes.c_int
@@ -656,3 +664,42 @@ def affine_render(scene_id: int, cam14, width: int, height: int, mode: int = RM_
     tm = _timing(warmup, repeats)
     check(L.rm_affine_render(ctypes.byref(d), int(mode), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(steps), _ref(tm)))
     return _frame_maps(d, tm, depth=depth, hit=hit, steps=steps)
+
+
+def capture_maps(capture: dict, width: int, height: int):
+    """(RmCaptureMaps, the arrays it points into) of a capture dict: depth / normal / color as contiguous float32, hit
+    (non-zero = hit) as uint8; a missing or None map is NULL."""
+    shape = (int(height), int(width))
+    keep = []
+
+    def addr(key, tail=()):
+        a = capture.get(key)
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a) != 0, np.uint8) if key == "hit" else np.ascontiguousarray(a, np.float32)
+        if a.shape != shape + tail:
+            raise ValueError(f"{key} has shape {a.shape}, not {shape + tail}")
+        keep.append(a)
+        return a.ctypes.data
+
+    return RmCaptureMaps(addr("depth"), addr("normal", (3,)), addr("color", (3,)), addr("hit")), keep
+
+
+def ssim_scores(width: int, height: int, reference: dict, methods, warmup=0, repeats=0):
+    """rm_ssim_scores: the (n, 4) float64 array {depth_ssim, normal_ssim, color_ssim, color_rmse} of the capture dicts
+    `methods` against `reference` (NaN where the captures carry no normal / color); with repeats > 0 also the kernels'
+    timing dict."""
+    L = init()
+    n = len(methods)
+    keep = []
+    ref, k = capture_maps(reference, width, height)
+    keep.append(k)
+    marr = (RmCaptureMaps * max(n, 1))()
+    for i, c in enumerate(methods):
+        marr[i], k = capture_maps(c, width, height)
+        keep.append(k)
+    out = np.empty((n, 4), np.float64)
+    tm = _timing(warmup, repeats)
+    check(L.rm_ssim_scores(int(width), int(height), ctypes.byref(ref), marr, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                           _ref(tm)))
+    return (out, timing_dict(tm)) if tm is not None else out

@@ -27,6 +27,7 @@
 #include "rm_interval_catalogue.h"
 #include "rm_segment.h"
 #include "rm_affine.h"
+#include "rm_ssim.h"
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
 static_assert(RM_NUM_SCENES == 20 && RM_NUM_STRATEGIES == 11 && RM_NUM_STRATEGY_KERNELS == 13, "registry size");
@@ -68,6 +69,9 @@ hipError_t launch_affine_march(const void* prog, int mode, const IntervalParams&
                                size_t n, double* t, int32_t* steps, hipStream_t s);
 hipError_t launch_affine_render(const void* prog, int mode, const IntervalParams& P, const CameraParams& cam, int width, int height,
                                 int row0, int rows, double* depth, uint8_t* hit, int32_t* steps, hipStream_t s);
+// rm_ssim.hip
+hipError_t launch_ssim(const SsimLaunch& a, hipStream_t s);
+
 static const SceneLaunchers* scene(int id)
 {
     switch (id) {
@@ -189,6 +193,8 @@ struct State : Session {
     WsBuf busy;     // rm_march_rays_team: the counter its filler workgroups watch (its own word: a frame in flight owns `ctl`)
     WsBuf trace, trace_start, trace_detach;   // development trace of single-launch frames (rm_debug_set_trace)
     WsBuf ccost, corder;   // single-launch pipeline: the centre-out tile order of the frame shape `corder_key`
+    WsBuf ssim_depth, ssim_normal, ssim_color, ssim_hit;   // rm_ssim_scores: the methods' maps, then the reference's
+    WsBuf ssim_ref, ssim_part, ssim_ssd, ssim_out;         // its reference images, partial sums and scores
 } g;
 
 std::mutex g_mu;
@@ -2107,6 +2113,73 @@ int rm_affine_render(const RmFrameDesc* d, int mode, const RmIntervalConfig* cfg
         return (int)RM_OK;
     });
     return rc ? rc : st.finish();
+}
+
+// ---- SSIM and colour-RMSE scoring of captures (rm_ssim.h, rm_ssim.hip) ------------------------------------------------
+
+namespace {
+
+int ssim_check_maps(const RmCaptureMaps& c, const RmCaptureMaps& ref, const char* who, int index)
+{
+    if (!c.depth || !c.hit) return fail(RM_E_BAD_ARG, "%s %d: depth and hit are required", who, index);
+    if (!c.normal != !ref.normal) return fail(RM_E_BAD_ARG, "%s %d: normal is NULL on one side only", who, index);
+    if (!c.color != !ref.color) return fail(RM_E_BAD_ARG, "%s %d: color is NULL on one side only", who, index);
+    return RM_OK;
+}
+
+}  // namespace
+
+int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference, const RmCaptureMaps* methods, int32_t nmethods,
+                   double* out, RmTiming* timing)
+{
+    if (!reference || !methods || !out) return fail(RM_E_BAD_ARG, "reference, methods or out is NULL");
+    if (nmethods <= 0 || nmethods > rm::kSsimMaxMethods)
+        return fail(RM_E_BAD_ARG, "nmethods %d outside [1, %d]", nmethods, rm::kSsimMaxMethods);
+    if (width < rm::kSsimWin || height < rm::kSsimWin)
+        return fail(RM_E_BAD_DIMS, "a %dx%d image holds no %dx%d window", width, height, rm::kSsimWin, rm::kSsimWin);
+    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
+    int rc = ssim_check_maps(*reference, *reference, "reference", 0);
+    for (int m = 0; !rc && m < nmethods; ++m) rc = ssim_check_maps(methods[m], *reference, "method", m);
+    if (rc || (timing && (rc = check_timing(timing)))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const size_t npix = (size_t)width * (size_t)height, caps = (size_t)nmethods + 1;      // the reference is capture `nmethods`
+    const size_t ntiles = (size_t)rm::ssim_tiles_x(width) * (size_t)rm::ssim_tiles_y(height);
+    const bool has_normal = reference->normal != nullptr, has_color = reference->color != nullptr;
+    if ((rc = g.ssim_depth.ensure(caps * npix * 4)) || (rc = g.ssim_hit.ensure(caps * npix)) ||
+        (has_normal && (rc = g.ssim_normal.ensure(caps * npix * 12))) || (has_color && (rc = g.ssim_color.ensure(caps * npix * 12))) ||
+        (rc = g.ssim_ref.ensure(rm::kSsimChannels * npix)) || (rc = g.ssim_part.ensure((size_t)nmethods * rm::kSsimChannels * ntiles * 8)) ||
+        (rc = g.ssim_ssd.ensure((size_t)nmethods * 3 * ntiles * 8)) || (rc = g.ssim_out.ensure((size_t)nmethods * 32)))
+        return rc;
+    for (size_t m = 0; m < caps; ++m) {
+        const RmCaptureMaps& c = m < (size_t)nmethods ? methods[m] : *reference;
+        HIP_TRY(hipMemcpyAsync((float*)g.ssim_depth.p + m * npix, c.depth, npix * 4, hipMemcpyHostToDevice, g.stream));
+        HIP_TRY(hipMemcpyAsync((uint8_t*)g.ssim_hit.p + m * npix, c.hit, npix, hipMemcpyHostToDevice, g.stream));
+        if (has_normal) HIP_TRY(hipMemcpyAsync((float*)g.ssim_normal.p + m * npix * 3, c.normal, npix * 12, hipMemcpyHostToDevice, g.stream));
+        if (has_color) HIP_TRY(hipMemcpyAsync((float*)g.ssim_color.p + m * npix * 3, c.color, npix * 12, hipMemcpyHostToDevice, g.stream));
+    }
+    double lo, hi;
+    rm::ssim_depth_minmax(reference->depth, reference->hit, npix, &lo, &hi);
+    rm::SsimLaunch a;
+    a.width = width; a.height = height; a.nmethods = nmethods; a.has_normal = has_normal; a.has_color = has_color;
+    a.range = rm::ssim_depth_range(lo, hi);
+    a.depth = (const float*)g.ssim_depth.p; a.hit = (const uint8_t*)g.ssim_hit.p;
+    a.normal = has_normal ? (const float*)g.ssim_normal.p : nullptr;
+    a.color = has_color ? (const float*)g.ssim_color.p : nullptr;
+    a.ref_depth = a.depth + (size_t)nmethods * npix; a.ref_hit = a.hit + (size_t)nmethods * npix;
+    a.ref_normal = has_normal ? a.normal + (size_t)nmethods * npix * 3 : nullptr;
+    a.ref_color = has_color ? a.color + (size_t)nmethods * npix * 3 : nullptr;
+    a.ref_img = (uint8_t*)g.ssim_ref.p;
+    a.part = (double*)g.ssim_part.p; a.ssd = (long long*)g.ssim_ssd.p; a.out = (double*)g.ssim_out.p;
+    rc = once_or_timed(e, timing, g.stream, [&] {
+        HIP_TRY(rm::launch_ssim(a, g.stream));
+        return (int)RM_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)nmethods * 32, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RM_OK;
 }
 
 }  // extern "C"

@@ -78,6 +78,29 @@ SHADER_UNIFORMS = {"omega": ("omega", "ar_omega_init"), "beta": ("beta",), "marg
 _GLSL_ONLY_DEFAULTS = {"kappa": 2.0}
 
 
+def ray_directions(cam: Camera) -> np.ndarray:
+    """(H, W, 3) unit directions of the camera's pixel-centre rays (camera.py:37-38)"""
+    c = cam.params14()
+    w, h = cam.width, cam.height
+    u = (2.0 * (np.arange(w) + 0.5) / w - 1.0) * c[12]
+    v = (1.0 - 2.0 * (np.arange(h) + 0.5) / h) * c[13]
+    rd = c[3:6][None, None, :] + c[6:9][None, None, :] * u[None, :, None] + c[9:12][None, None, :] * v[:, None, None]
+    rd /= np.sqrt((rd * rd).sum(2, keepdims=True))
+    return rd
+
+
+def hit_normals(scene_id: int, cam: Camera, rd: np.ndarray, depth: np.ndarray, hit: np.ndarray) -> np.ndarray:
+    """(hits, 3) tetrahedron normals from four SDF evaluations (rm_sdf_eval) at the hit points `origin + depth * rd` of
+    the pixels of `hit` (calcNormal, main.glsl:26-35); `hit` must hold a hit."""
+    pos = cam.params14()[0:3][None, :] + depth[hit][:, None] * rd[hit]
+    e = 0.0005
+    ks = np.array([[1.0, -1.0, -1.0], [-1.0, -1.0, 1.0], [-1.0, 1.0, -1.0], [1.0, 1.0, 1.0]])
+    d4 = _native.sdf_eval(int(scene_id), (pos[:, None, :] + e * ks[None, :, :]).reshape(-1, 3)).reshape(-1, 4)
+    n = (d4[:, :, None] * ks[None, :, :]).sum(1)
+    n /= np.maximum(np.sqrt((n * n).sum(1, keepdims=True)), 1e-300)
+    return n
+
+
 class GPURunner:
     """`GPURunner.render` / `GPURunner.capture` with the reference's signatures and result layouts
     (gpu/runner.py:58-166, :168-268), evaluated by the gfx950 kernels with the CPU path's arithmetic.
@@ -166,23 +189,14 @@ class GPURunner:
         cam, out = self._frame(scene_id, self._strategy(strategy_id, strategy_key), render_cfg, march_cfg, lipschitz, False, True, params)
         h, w = out["iters"].shape
         hit = out["hit"] > 0
-        c = cam.params14()
-        u = (2.0 * (np.arange(w) + 0.5) / w - 1.0) * c[12]                   # camera.py:37-38
-        v = (1.0 - 2.0 * (np.arange(h) + 0.5) / h) * c[13]
-        rd = c[3:6][None, None, :] + c[6:9][None, None, :] * u[None, :, None] + c[9:12][None, None, :] * v[:, None, None]
-        rd /= np.sqrt((rd * rd).sum(2, keepdims=True))
+        rd = ray_directions(cam)
         depth = np.where(hit, out["t_raw"], 0.0)
         normal = np.zeros((h, w, 3))
         color = np.empty((h, w, 3))
         tb = 0.5 * (rd[..., 1] + 1.0)                                          # main.glsl background()
         color[:] = (1.0 - tb)[..., None] * np.array([0.06, 0.07, 0.09]) + tb[..., None] * np.array([0.12, 0.14, 0.18])
         if hit.any():
-            pos = c[0:3][None, :] + depth[hit][:, None] * rd[hit]
-            e = 0.0005                                                         # calcNormal, main.glsl:26-35
-            ks = np.array([[1.0, -1.0, -1.0], [-1.0, -1.0, 1.0], [-1.0, 1.0, -1.0], [1.0, 1.0, 1.0]])
-            d4 = _native.sdf_eval(int(scene_id), (pos[:, None, :] + e * ks[None, :, :]).reshape(-1, 3)).reshape(-1, 4)
-            n = (d4[:, :, None] * ks[None, :, :]).sum(1)
-            n /= np.maximum(np.sqrt((n * n).sum(1, keepdims=True)), 1e-300)
+            n = hit_normals(scene_id, cam, rd, depth, hit)
             normal[hit] = n
             L = np.array([0.6, 0.7, 0.5]) / np.sqrt(0.6 ** 2 + 0.7 ** 2 + 0.5 ** 2)   # shade(), main.glsl:40-47
             diff = np.maximum(n @ L, 0.0)

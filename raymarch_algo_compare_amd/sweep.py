@@ -78,6 +78,10 @@ ORACLES = ("interval",)
 # scene without an interval extension
 CEILING_FIELDS = ["ceiling_iou", "ceiling_depth_med", "ceiling_iters_median", "ceiling_iters_p95"]
 CEILINGS = ("segment",)
+# with ssim (run_sweep(oracle=..., ssim=True)): the tertiary tier of scoring.py -- each frame's depth and normal images
+# against the oracle capture's (ssim.py; the frame's normals as GPURunner.capture takes them, at its own hit points).  The
+# oracle captures carry no colour, so the two colour columns are empty cells, as are all four without an oracle capture.
+SSIM_FIELDS = list(scoring.SSIM_KEYS)
 
 
 def build_levels(mode: str, *, budgets: Sequence[int] = DEFAULT_BUDGETS, epsilons: Sequence[float] = DEFAULT_EPSILONS,
@@ -109,11 +113,12 @@ def finest_index(mode: str, levels) -> int:
 
 def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, width: int, height: int, grid: bool = False,
                oracle_frames: Optional[Dict[str, Optional[Dict]]] = None,
-               ceiling_cols: Optional[Dict[str, Dict]] = None) -> List[Dict]:
+               ceiling_cols: Optional[Dict[str, Dict]] = None, keep: Optional[List] = None) -> List[Dict]:
     """All viewpoints x parameter combos x levels of one (scene, strategy) in one batched launch -> one row per
     frame.  `grid` brute-forces the strategy's tunable parameters (reference sweep.py:181,222-223).  `oracle_frames`
     (viewpoint name -> oracle capture, None without one) adds the ORACLE_FIELDS columns, `ceiling_cols` (viewpoint name ->
-    CEILING_FIELDS values) those."""
+    CEILING_FIELDS values) those.  `keep` (a list) receives (row, viewpoint name, camera, hit map, depth map) of every row,
+    for ssim_columns."""
     from .runner import GPURunner
     vps = viewpoints_for(scene)
     combos = param_combos(strategy.key) if grid else [{}]
@@ -153,6 +158,8 @@ def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, widt
             rows[-1].update(oracle_columns({"hit": st.hit_map, "depth": st.depth_map}, oracle_frames.get(vp.name)))
         if ceiling_cols is not None:
             rows[-1].update(ceiling_cols[vp.name])
+        if keep is not None:
+            keep.append((rows[-1], vp.name, cams[i], st.hit_map, st.depth_map))
     return rows
 
 
@@ -164,6 +171,32 @@ def oracle_columns(frame: Dict, oracle: Optional[Dict]) -> Dict:
     d = scoring._depth_metrics(frame, oracle)
     return {"oracle_iou": h["iou"], "oracle_false_hit": h["false_hit_rate"], "oracle_false_miss": h["false_miss_rate"],
             "oracle_depth_mae": d["mae"], "oracle_depth_rmse": d["rmse"], "oracle_depth_p95": d["p95"]}
+
+
+def ssim_columns(scene, kept: List, oracle_frames: Dict[str, Optional[Dict]]) -> None:
+    """Adds the SSIM_FIELDS columns to the kept rows of one scene (sweep_cell's `keep`): all rows of a viewpoint -- every
+    strategy, parameter combo and level -- against that viewpoint's oracle capture in ONE rm_ssim_scores call."""
+    from . import ssim
+    from .runner import hit_normals, ray_directions
+    by_vp: Dict[str, List] = {}
+    for item in kept:
+        by_vp.setdefault(item[1], []).append(item)
+    for name, items in by_vp.items():
+        truth = oracle_frames.get(name)
+        if truth is None:
+            for row, *_ in items:
+                row.update(dict.fromkeys(SSIM_FIELDS))
+            continue
+        rd = ray_directions(items[0][2])
+        methods = []
+        for _, _, cam, hit, depth in items:
+            hit = np.asarray(hit, dtype=bool)
+            normal = np.zeros(hit.shape + (3,), np.float32)
+            if hit.any():
+                normal[hit] = hit_normals(scene.id, cam, rd, depth, hit)
+            methods.append({"hit": hit, "depth": depth, "normal": normal})
+        for (row, *_), cols in zip(items, ssim.ssim_scores_batch(methods, truth)):
+            row.update(cols)
 
 
 def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float) -> Dict[str, Optional[Dict]]:
@@ -203,17 +236,20 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
               epsilons: Sequence[float] = DEFAULT_EPSILONS, cap: int = 512, hit_threshold: float = 1e-4,
               out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False,
               oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL,
-              ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL) -> List[Dict]:
+              ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL, ssim: bool = False) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
     interval oracle's first hit of its viewpoint (ORACLE_FIELDS; one oracle frame per scene and viewpoint, tolerance
     `oracle_tol`).  ceiling="segment": every row also carries the sound segment tracer's result at its viewpoint
-    (CEILING_FIELDS; hit tolerance `ceiling_tol`, scored against the interval oracle at `oracle_tol`)."""
+    (CEILING_FIELDS; hit tolerance `ceiling_tol`, scored against the interval oracle at `oracle_tol`).  ssim=True (only
+    with an oracle): every row also carries SSIM_FIELDS against the oracle capture of its viewpoint."""
     if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
         raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
     if ceiling is not None and ceiling not in CEILINGS:
         raise ValueError(f"unknown ceiling {ceiling!r}: one of {CEILINGS}")
+    if ssim and oracle is None:
+        raise ValueError("ssim needs an oracle to score against: pass oracle=")
     scenes = registry.get_all_scenes() if not scene_names else [_need(registry.get_scene_by_name(n), "scene", n) for n in scene_names]
     strats = ([registry.get_strategy_by_name(k) for k in registry.list_strategies()] if not strategy_names
               else [_need(registry.get_shader_strategy(n) or registry.get_strategy_by_name(n), "strategy", n) for n in strategy_names])
@@ -224,14 +260,17 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
         truth = oracle_frames_for(scene, width, height, "interval", oracle_tol) if oracle is not None or ceiling is not None else None
         ofr = truth if oracle is not None else None
         ccols = ceiling_columns_for(scene, width, height, truth, ceiling_tol) if ceiling is not None else None
+        kept: Optional[List] = [] if ssim else None
         for strat in strats:
             if strat.has_lipschitz:
                 strat.lipschitz = scene.known_lipschitz_bound() or 1.0      # run_once wiring (reference main.py:58-61)
-            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid, ofr, ccols)
+            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid, ofr, ccols, kept)
             rows.extend(cell)
             if verbose:
                 print(f"{scene.name:24s} {strat.short_name:24s} {len(cell):3d} frames  "
                       f"{sum(r['ms_per_frame'] for r in cell):8.2f} ms", file=sys.stderr)
+        if kept:
+            ssim_columns(scene, kept, ofr)
     if out_path:
         write_rows(rows, out_path)
     return rows
@@ -243,7 +282,7 @@ def write_rows(rows: List[Dict], path: str) -> None:
             json.dump(rows, f, indent=1, ensure_ascii=False)
         return
     fields = ROW_FIELDS + (ORACLE_FIELDS if rows and "oracle_iou" in rows[0] else []) + \
-        (CEILING_FIELDS if rows and "ceiling_iou" in rows[0] else [])
+        (CEILING_FIELDS if rows and "ceiling_iou" in rows[0] else []) + (SSIM_FIELDS if rows and "depth_ssim" in rows[0] else [])
     with open(path, "w", newline="", encoding="utf-8") as f:
         w = csv.DictWriter(f, fieldnames=fields)
         w.writeheader()
@@ -275,11 +314,15 @@ def main(argv=None) -> int:
     ap.add_argument("--ceiling", default=None, choices=list(CEILINGS),
                     help="add the sound segment tracer's result per scene and viewpoint (the ceiling_* columns)")
     ap.add_argument("--ceiling-tol", type=float, default=faithful_segment.DEFAULT_TOL, help="the ceiling tracer's hit tolerance")
+    ap.add_argument("--ssim", action="store_true",
+                    help="with --oracle: add the SSIM columns of every frame against the oracle capture (depth_ssim, normal_ssim, ...)")
     a = ap.parse_args(argv)
+    if a.ssim and a.oracle is None:
+        ap.error("--ssim needs --oracle")
     rows = run_sweep([s for s in a.scenes.split(",") if s], [s for s in a.strategies.split(",") if s], a.mode, a.width, a.height,
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
                      a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol,
-                     ceiling=a.ceiling, ceiling_tol=a.ceiling_tol)
+                     ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 
