@@ -532,7 +532,10 @@ int rm_copy_frame_to_host(int32_t width, int32_t rows, const void* d_depth, cons
 /* ---- BASELINE config 5: one frame row-sharded over the GPUs of a node, one process per GPU ------------------
  * The frame shards with no exchange while it is rendered (rays are independent); its only communication is the
  * final gather of the three maps.  These entry points do that gather from C with RCCL over xGMI -- no PyTorch on the
- * path.  RCCL is loaded on first use (dlopen "librccl.so.1"); the library has no link-time dependency on it.
+ * path.  RCCL is loaded on first use (dlopen "librccl.so.1"); the library has no link-time dependency on it.  The
+ * environment variable RM_RCCL_LIBRARY, read once at that first load, names the one library to load instead (a particular
+ * RCCL build; the tests' loop-back stand-in): if it cannot be loaded or lacks a symbol the call fails with RM_E_RCCL and
+ * the message names the path -- the default names are not tried.  Unset or empty: the default names.
  *   rank 0:      rm_comm_unique_id(id);  ship the 128 bytes to the other ranks (any channel: a file, MPI, a socket)
  *   every rank:  rm_init(local device);  rm_comm_init(id, world_size, rank);
  *   per frame:   rm_render_device(shard desc, ...);  rm_gather_frame(...)  -> the whole frame on every rank
@@ -558,8 +561,9 @@ int rm_gather_frame(const RmFrameDesc* shard, const void* d_depth, const void* d
  * copies of it): every other rank sends its shard to `root` (grouped ncclSend / ncclRecv over the direct xGMI links: the
  * root receives 7/8 of the frame, nobody else receives anything).  Contiguous plan: the shards land straight in the image
  * (no second pass over the frame); band-cyclic plan: in a rank-major buffer that one placement pass turns into the image.
- * d_full_* are read on the root only (NULL elsewhere).  Asynchronous on the stream.  UNVERIFIED ON MORE THAN ONE RANK in
- * this build environment (one GPU): covered with a communicator of one and by construction (tests/test_gpu_gather.py). */
+ * d_full_* are read on the root only (NULL elsewhere).  Asynchronous on the stream.  Both gather forms: offsets, counts
+ * and pairing exercised for N = 2, 3, 4, 8 against a loop-back stand-in on one GPU (tests/test_gpu_loopback_gather.py);
+ * never run over real RCCL with N > 1; no scaling figure measured. */
 int rm_gather_frame_root(const RmFrameDesc* shard, const void* d_depth, const void* d_iters, const void* d_hit,
                          void* d_full_depth, void* d_full_iters, void* d_full_hit, int32_t root, void* stream);
 /* The second half of rm_gather_frame on its own: `d_gathered` holds the shards of all ranks one after the other

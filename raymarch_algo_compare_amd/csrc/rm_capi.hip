@@ -11,11 +11,13 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <optional>
+#include <string>
 #include <vector>
 
 #include "../../include/rm_hip.h"
@@ -928,15 +930,24 @@ struct Rccl {
 int rccl_load()
 {
     if (R.handle) return RM_OK;
+    // RM_RCCL_LIBRARY (read once, on the first load): the one library to use -- a particular RCCL build, or the tests'
+    // loop-back stand-in.  A named library that cannot be loaded is an error, never a reason to try the default names.
+    static const std::string named = [] { const char* v = getenv("RM_RCCL_LIBRARY"); return std::string(v ? v : ""); }();
     void* h = nullptr;
-    for (const char* name : { "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" }) {
-        h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-        if (h) break;
+    if (!named.empty()) {
+        h = dlopen(named.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!h) return fail(RM_E_RCCL, "RM_RCCL_LIBRARY=%s could not be loaded: %s", named.c_str(), dlerror());
+    } else {
+        for (const char* name : { "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" }) {
+            h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
+            if (h) break;
+        }
+        if (!h) return fail(RM_E_RCCL, "librccl.so.1 could not be loaded: %s", dlerror());
     }
-    if (!h) return fail(RM_E_RCCL, "librccl.so.1 could not be loaded: %s", dlerror());
+    const char* const where = named.empty() ? "librccl" : named.c_str();
 #define RM_SYM(field, sym)                                                                     \
     R.field = reinterpret_cast<decltype(R.field)>(dlsym(h, #sym));                              \
-    if (!R.field) { dlclose(h); return fail(RM_E_RCCL, "librccl lacks %s", #sym); }
+    if (!R.field) { dlclose(h); return fail(RM_E_RCCL, "%s lacks %s", where, #sym); }
     RM_SYM(GetUniqueId, ncclGetUniqueId)
     RM_SYM(CommInitRank, ncclCommInitRank)
     RM_SYM(CommDestroy, ncclCommDestroy)
@@ -1529,6 +1540,8 @@ int rm_gather_frame_root(const RmFrameDesc* d, const void* d_depth, const void* 
     if (sh.is_root && sh.cyclic)
         for (int k = 0; k < 3; ++k)
             if ((rc = R.gather[k].ensure(sh.bytes(k, per) * (size_t)N + 16))) return rc;
+    // (The min() below is a guard only: slot() is reached for ranks with rows_of(r) > 0, i.e. r * per < H, so it never
+    // clamps under the present callers and no test can tell it from r * per.)
     auto slot = [&](int k, int r) -> char* {
         return sh.cyclic ? (char*)R.gather[k].p + sh.bytes(k, (long long)r * per) : (char*)sh.dst[k] + sh.bytes(k, std::min(r * per, H));
     };
