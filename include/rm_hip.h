@@ -266,7 +266,7 @@ int rm_march_rays(int scene_id, int strategy_id, const RmMarchConfig* cfg, const
  * the matching RM_SOP_POP_POINT read; RM_SOP_POP_POINT restores the saved point.  Evaluation starts at the query point;
  * exactly one distance must be left at the end, and every transform must be matched.  Constants go in f[], in the
  * order of the reference's arguments; a constant the reference computes with a transcendental function is passed
- * already computed (the device never evaluates trigonometry).  `arg` is reserved (0), unused f[] entries too.
+ * already computed (the device evaluates trigonometry for RM_SOP_GYROID only).  `arg` is reserved (0), unused f[] entries too.
  *   op                          f[]                                              primitives.py
  *   RM_SOP_SPHERE               radius                                           :11-12
  *   RM_SOP_BOX                  half_extents x, y, z                             :14-18
@@ -283,6 +283,20 @@ int rm_march_rays(int scene_id, int strategy_id, const RmMarchConfig* cfg, const
  *   RM_SOP_POP_POINT            (none)
  *   RM_SOP_ROUND                radius                                           :110-111
  *   RM_SOP_ONION                thickness                                        :113-114
+ * Four ops that primitives.py does not have (the catalogue's Bad Lipschitz Sphere, Box Lattice, Menger and Gyroid are
+ * written with them; scenes/catalog.py lines on the right).  `py_mod` is Python's float `%`, min / max / abs Python's:
+ *   RM_SOP_SCALE                factor (finite, > 0): modifier, d * factor                            :320-321
+ *   RM_SOP_LIMITED_REPEAT       spacing x, y, z, limit x, y, z (each limit finite, >= 0): point transform closed by
+ *                               RM_SOP_POP_POINT; per axis with spacing c > 0
+ *                               x - c * max(-l, min(l, floor(x / c + 0.5))), an axis with spacing <= 0 is untouched   :581-590
+ *   RM_SOP_MENGER_CROSS         s (finite, > 0), s * 3.0 (as the caller's multiplication rounds it): primitive, one trip of
+ *                               the Menger loop: a = py_mod(p * s, 2.0) - 1.0, r = abs(1.0 - 3.0 * abs(a)) per axis,
+ *                               (min(max(r.x, r.y), min(max(r.y, r.z), max(r.z, r.x))) - 1.0) / (s * 3.0)         :221-237
+ *   RM_SOP_GYROID               freq, lipschitz (finite, > 0): primitive, with q = freq * p
+ *                               (sin(q.x) * cos(q.y) + sin(q.y) * cos(q.z) + sin(q.z) * cos(q.x)) / lipschitz      :510-514
+ * RM_SOP_GYROID is the one op that evaluates trigonometry on the device: sin and cos are the library's exact restatements
+ * of glibc's for |q| < 105414336 (0x1.921fbp+26) and NaN for larger or non-finite arguments, so the op's value is NaN
+ * there (the catalogue's Gyroid scene has the same limit).
  * Every result is bit-identical to the reference's functions (binary64, its evaluation order).
  * Ids of programs start at RM_SCENE_PROGRAM_BASE, increase monotonically and are never reused within a process.  A
  * program id is accepted by every frame entry point (rm_render*, rm_render_device, rm_bench_device, rm_render_batch*,
@@ -300,7 +314,8 @@ enum {
     RM_SOP_SMOOTH_UNION = 11, RM_SOP_SMOOTH_SUBTRACT = 12, RM_SOP_SMOOTH_INTERSECT = 13,
     RM_SOP_TRANSLATE = 14, RM_SOP_REPEAT = 15, RM_SOP_POP_POINT = 16,
     RM_SOP_ROUND = 17, RM_SOP_ONION = 18,
-    RM_SOP_COUNT = 19
+    RM_SOP_SCALE = 19, RM_SOP_LIMITED_REPEAT = 20, RM_SOP_MENGER_CROSS = 21, RM_SOP_GYROID = 22,
+    RM_SOP_COUNT = 23
 };
 typedef struct RmSceneOp {
     int32_t op;       /* RM_SOP_* */

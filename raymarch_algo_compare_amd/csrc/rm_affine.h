@@ -9,7 +9,8 @@
 // of the scene-program interpreter:
 //  * sphere, plane, box, torus: the reference's _sd_sphere / _sd_plane / _sd_box / _sd_torus over Aff, expression for
 //    expression -- its COMPONENT_SCENES, bit for bit in x0, x1 and e;
-//  * translate and round: x0 - k, exact and linear, x1 and e untouched;
+//  * translate and round: x0 - k, exact and linear, x1 and e untouched; scale: every part times the factor; a limited
+//    repeat whose range lies in one cell: the shift by that cell;
 //  * every other primitive and op: the hull fallback -- the operands' range(), the interval function of rm_interval.h on
 //    those intervals, aff_from_range of the result.  This is what the reference does for its own non-smooth ops (abs,
 //    max0, min0, maximum, minimum); it is sound because the interval function is, and it drops the correlation.
@@ -143,7 +144,18 @@ struct AffineAlgebra {
     RM_HD Aff cone(AVec3 p, double c, double s, double height) const { return aff_from_range(i_cone(aranges(p), c, s, height)); }
     RM_HD AVec3 translate(AVec3 p, double kx, double ky, double kz) const { return avec3(p.x - kx, p.y - ky, p.z - kz); }
     RM_HD Aff repeat(Aff x, double spacing, bool pow2) const { return aff_from_range(irepeat_axis(arange(x), spacing, pow2)); }
+    // same cell at both ends of the range: the exact shift x - c * n, the linear part kept; else the interval fallback
+    RM_HD Aff limited_repeat(Aff x, double c, double l) const
+    {
+        const Ival r = arange(x);
+        const double n = limited_repeat_cell(r.lo, c, l);
+        if (n == limited_repeat_cell(r.hi, c, l)) return x - c * n;
+        return aff_from_range(ilimited_repeat_axis(r, c, l));
+    }
+    RM_HD Aff menger_cross(AVec3 p, double s, double s3) const { return aff_from_range(i_menger_cross(aranges(p), s, s3)); }
+    RM_HD Aff gyroid(AVec3 p, double freq, double lipschitz) const { return aff_from_range(i_gyroid(aranges(p), freq, lipschitz)); }
     RM_HD Aff round(Aff a, double k) const { return a - k; }
+    RM_HD Aff scale(Aff a, double k) const { return a * k; }
     RM_HD Aff abs(Aff a) const { return aff_from_range(iabs_pw(arange(a))); }
     RM_HD Aff union_(Aff a, Aff b) const { return aff_from_range(i_union(arange(a), arange(b))); }
     RM_HD Aff subtract(Aff a, Aff b) const { return aff_from_range(i_subtract(arange(a), arange(b))); }

@@ -16,7 +16,7 @@ __global__ __launch_bounds__(kAffineBlock) void affine_range_kernel(const void* 
                                                                    double* __restrict__ out_form)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double* s = segs + 8 * i;
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kAffineBlock) void affine_march_kernel(const void* 
                                                                    double* __restrict__ t_out, int32_t* __restrict__ steps)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const vec3 o = v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]);
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kAffineBlock) void affine_render_kernel(const void*
                                                                     int32_t* __restrict__ steps)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int py = row0 + (int)(i / (size_t)width), px = (int)(i % (size_t)width);

@@ -45,8 +45,10 @@ RM_SCENE_LIST(RM_X)
 #undef RM_X
 #if defined(RM_DEV_STRATEGIES)
 const SceneLaunchers* scene_launchers_program() __attribute__((weak));
+const SceneLaunchers* scene_launchers_program_ext() __attribute__((weak));
 #else
 const SceneLaunchers* scene_launchers_program();
+const SceneLaunchers* scene_launchers_program_ext();      // ... of programs with an op beyond primitives.py (SceneExtProgram)
 #endif
 // rm_math_check.hip: the device math routines one by one (rm_debug_math_eval)
 hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1,
@@ -208,6 +210,7 @@ struct Program {
     std::unique_ptr<rm::ProgramImage> img;
     void* dev = nullptr;
     double lipschitz = 1.0;
+    bool ext = false;                         // holds RM_SOP_SCALE .. RM_SOP_GYROID: rendered by SceneExtProgram's kernels
 };
 std::mutex g_prog_mu;                          // guards g_programs and g_next_program; taken after g_mu where both are held
 std::map<int32_t, Program> g_programs;
@@ -215,22 +218,35 @@ int32_t g_next_program = RM_SCENE_PROGRAM_BASE;   // ids are never reused: no pe
 
 bool is_program_id(int id) { return id >= RM_SCENE_PROGRAM_BASE; }
 
-const rm::SceneLaunchers* program_launchers()
+const rm::SceneLaunchers* program_launchers(bool ext)
 {
 #if defined(RM_DEV_STRATEGIES)
+    if (ext) return rm::scene_launchers_program_ext ? rm::scene_launchers_program_ext() : nullptr;
     return rm::scene_launchers_program ? rm::scene_launchers_program() : nullptr;
 #else
-    return rm::scene_launchers_program();
+    return ext ? rm::scene_launchers_program_ext() : rm::scene_launchers_program();
 #endif
 }
 
-// The kernels of scene `id` (a catalogue scene or a program; check_scene has accepted the id)
-const rm::SceneLaunchers* launchers(int id) { return is_program_id(id) ? program_launchers() : rm::scene(id); }
-
-bool program_exists(int id)
+bool program_exists(int id, bool* ext = nullptr)
 {
     std::lock_guard<std::mutex> lk(g_prog_mu);
-    return g_programs.count(id) != 0;
+    auto it = g_programs.find(id);
+    if (it == g_programs.end()) return false;
+    if (ext) *ext = it->second.ext;
+    return true;
+}
+
+// The kernels of scene `id` (a catalogue scene or a program; check_scene has accepted the id): a program that holds an
+// op beyond primitives.py (RM_SOP_SCALE .. RM_SOP_GYROID) has its own instantiation of the interpreter
+// (looked up by id again rather than carried out of check_scene through plan_for / launch_frame; the program cannot
+// vanish in between: the caller holds g_mu, which rm_scene_program_destroy takes first)
+const rm::SceneLaunchers* launchers(int id)
+{
+    if (!is_program_id(id)) return rm::scene(id);
+    bool ext = false;
+    (void)program_exists(id, &ext);
+    return program_launchers(ext);
 }
 
 int no_such_program(int id) { return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id); }
@@ -238,8 +254,9 @@ int no_such_program(int id) { return fail(RM_E_BAD_SCENE, "scene program %d does
 int check_scene(int id)
 {
     if (is_program_id(id)) {
-        if (!program_exists(id)) return no_such_program(id);
-        if (!program_launchers()) return fail(RM_E_BAD_SCENE, "the scene-program kernels are not built into this (development) library");
+        bool ext = false;
+        if (!program_exists(id, &ext)) return no_such_program(id);
+        if (!program_launchers(ext)) return fail(RM_E_BAD_SCENE, "the scene-program kernels are not built into this (development) library");
         return RM_OK;
     }
     if (id < 0 || id >= RM_NUM_SCENES) return fail(RM_E_BAD_SCENE, "scene_id %d out of range", id);
@@ -1053,6 +1070,7 @@ int rm_scene_program_create(const RmSceneOp* ops, int32_t nops, double lipschitz
     if (g_next_program == INT32_MAX) return fail(RM_E_BAD_ARG, "scene program ids exhausted");
     const int32_t id = g_next_program++;
     Program& p = g_programs[id];
+    p.ext = rm::program_has_ext(*img);
     p.img = std::move(img);
     p.lipschitz = lipschitz;
     *scene_id = id;

@@ -205,6 +205,111 @@ RM_HD Ival i_union(Ival a, Ival b) { return iv(py_min(a.lo, b.lo), py_min(a.hi, 
 RM_HD Ival i_subtract(Ival a, Ival b) { return iv(py_max(a.lo, -b.hi), py_max(a.hi, -b.lo)); }
 RM_HD Ival i_intersect(Ival a, Ival b) { return iv(py_max(a.lo, b.lo), py_max(a.hi, b.hi)); }
 
+// ---- the four ops beyond primitives.py ("Program extensions") ------------------------------------
+
+// RM_SOP_SCALE: factor > 0, end for end
+RM_HD Ival i_scale(Ival a, double k) { return iv(a.lo * k, a.hi * k); }
+
+// RM_SOP_LIMITED_REPEAT, one axis with spacing c > 0: x -> x - c * n(x), n the clamped cell index.  The computed n is a
+// chain of monotone roundings of x, so it is non-decreasing in x: when both ends have the same n every point between them
+// has it too, the map is the same shift for the whole box and the ends map to the ends of the image.  Otherwise the map
+// is made of pieces of slope 1 separated by downward jumps at cell edges, where the value falls from c/2 (or, with a
+// fractional limit, from less) to -c/2 (or more); its supremum is taken at the upper end or just below a jump, its infimum
+// at the lower end or just above one: the hull of the two end values and [-c/2, c/2].  The end values are the pointwise
+// ones, so the clamped outer cells, where the value leaves [-c/2, c/2], are covered.  A degenerate box has one n.
+RM_HD Ival ilimited_repeat_axis(Ival x, double c, double l)
+{
+    const double flo = limited_repeat_axis(x.lo, c, l), fhi = limited_repeat_axis(x.hi, c, l);
+    if (limited_repeat_cell(x.lo, c, l) == limited_repeat_cell(x.hi, c, l)) return iv(flo, fhi);
+    return iv(py_min(py_min(flo, fhi), -(c * 0.5)), py_max(py_max(flo, fhi), c * 0.5));
+}
+
+// RM_SOP_MENGER_CROSS.  a = py_mod(x * s, 2) - 1 is irepeat_axis's situation with period 2 and no half-cell shift: the
+// same argument on the computed remainders (exact but for the sign fix m + 2) decides `same cell`; a box that may span a
+// jump, or is wider than half a period, gets the whole period [-1, 1].  |a| is continuous across the jump, so
+// r = |1 - 3 |a|| is a continuous function of x and everything after it is monotone min / max.
+RM_HD Ival imenger_a(Ival x, double s)
+{
+    const double ulo = x.lo * s, uhi = x.hi * s;
+    const double mlo = py_mod_pow2(ulo, 2.0), mhi = py_mod_pow2(uhi, 2.0);
+    if (uhi - ulo < 1.0 && mlo <= mhi) return iv(mlo - 1.0, mhi - 1.0);
+    return iv(-1.0, 1.0);
+}
+RM_HD Ival imenger_fold(Ival x, double s)
+{
+    const Ival b = iabs_pw(imenger_a(x, s));
+    return iabs_pw(iv(1.0 - 3.0 * b.hi, 1.0 - 3.0 * b.lo));
+}
+RM_HD Ival i_menger_cross(IVec3 p, double s, double s3)
+{
+    const Ival rx = imenger_fold(p.x, s), ry = imenger_fold(p.y, s), rz = imenger_fold(p.z, s);
+    const Ival da = i_intersect(rx, ry), db = i_intersect(ry, rz), dc = i_intersect(rz, rx);
+    const Ival m = i_union(da, i_union(db, dc));
+    return iv((m.lo - 1.0) / s3, (m.hi - 1.0) / s3);
+}
+
+// sin and cos over an interval.  A degenerate box is the pointwise value (NaN outside rm_sincos' exact range).  Otherwise:
+// the end values from rm_sincos, and +1 / -1 wherever the box may contain an extremum.  The extrema lie at q = j * pi/2
+// (sin: +1 at j = 1, -1 at j = 3 mod 4; cos: +1 at j = 0, -1 at j = 2 mod 4); v = q * (2 / pi) is computed with an error
+// below |v| * 2^-51, so every integer within |v| * 2^-50 of [v_lo, v_hi] counts as inside -- an extremum too many costs
+// less than 1e-14, one missed would be unsound.  A box of 2 pi or more contains all four residues and gets [-1, 1] by the
+// same test.  An end outside the exact range, or not finite, gives [-1, 1].
+struct ISinCos {
+    Ival s, c;
+};
+RM_HD bool icontains_residue(int32_t jlo, int32_t jhi, int32_t r) { return jlo + ((r - jlo) & 3) <= jhi; }
+RM_HD ISinCos isincos(Ival q)
+{
+    ISinCos o;
+    double slo, clo, shi, chi;
+    rm_sincos(q.lo, &slo, &clo);
+    rm_sincos(q.hi, &shi, &chi);
+    if (q.lo == q.hi) {
+        o.s = iv(slo, shi); o.c = iv(clo, chi);
+        return o;
+    }
+    const double lim = 0x1.921fbp+26;
+    if (!(rm_fabs(q.lo) < lim && rm_fabs(q.hi) < lim)) {
+        o.s = iv(-1.0, 1.0); o.c = iv(-1.0, 1.0);
+        return o;
+    }
+    const double two_over_pi = 0x1.45f306dc9c883p-1;
+    const double vlo = q.lo * two_over_pi, vhi = q.hi * two_over_pi;
+    const int32_t jlo = (int32_t)-rm_floor((rm_fabs(vlo) * 0x1p-50 + 0x1p-60) - vlo);
+    const int32_t jhi = (int32_t)rm_floor(vhi + (rm_fabs(vhi) * 0x1p-50 + 0x1p-60));
+    o.s = iv(icontains_residue(jlo, jhi, 3) ? -1.0 : py_min(slo, shi), icontains_residue(jlo, jhi, 1) ? 1.0 : py_max(slo, shi));
+    o.c = iv(icontains_residue(jlo, jhi, 2) ? -1.0 : py_min(clo, chi), icontains_residue(jlo, jhi, 0) ? 1.0 : py_max(clo, chi));
+    return o;
+}
+// sin and cos of the three coordinates of freq * p, one axis per trip of a loop that stays a loop (the axes rotate through
+// q0, the results shift through x, y, z): six inlined copies of rm_sincos side by side cost the segment kernels their
+// vector registers
+struct ISinCos3 {
+    ISinCos x, y, z;
+};
+RM_HD ISinCos3 isincos3(IVec3 p, double freq)
+{
+    Ival q0 = p.x * freq, q1 = p.y * freq, q2 = p.z * freq;
+    ISinCos3 o;
+    o.x.s = o.x.c = o.y.s = o.y.c = o.z.s = o.z.c = iv(0.0, 0.0);
+#pragma unroll 1
+    for (int a = 0; a < 3; ++a) {
+        const ISinCos r = isincos(q0);
+        o.x = o.y; o.y = o.z; o.z = r;
+        const Ival t = q0;
+        q0 = q1; q1 = q2; q2 = t;
+    }
+    return o;
+}
+// RM_SOP_GYROID: the pointwise expression over intervals, summed left to right
+RM_HD Ival i_gyroid(IVec3 p, double freq, double lipschitz)
+{
+    const ISinCos3 sc = isincos3(p, freq);
+    const ISinCos x = sc.x, y = sc.y, z = sc.z;
+    const Ival g = x.s * y.c + y.s * z.c + z.s * x.c;
+    return iv(g.lo / lipschitz, g.hi / lipschitz);
+}
+
 // ---- the interpreter ----------------------------------------------------------------------------------------------
 
 // evaluation over a box (program_walk, rm_scene_program.h)
@@ -219,9 +324,13 @@ struct IntervalAlgebra {
     RM_HD Ival capsule(IVec3 p, vec3 a, vec3 b, double radius) const { return i_capsule(p, a, b, radius); }
     RM_HD Ival capped_torus(IVec3 p, double sc0, double sc1, double ra, double rb) const { return i_capped_torus(p, sc0, sc1, ra, rb); }
     RM_HD Ival cone(IVec3 p, double c, double s, double height) const { return i_cone(p, c, s, height); }
+    RM_HD Ival menger_cross(IVec3 p, double s, double s3) const { return i_menger_cross(p, s, s3); }
+    RM_HD Ival gyroid(IVec3 p, double freq, double lipschitz) const { return i_gyroid(p, freq, lipschitz); }
     RM_HD IVec3 translate(IVec3 p, double kx, double ky, double kz) const { return ivec3(p.x - kx, p.y - ky, p.z - kz); }
     RM_HD Ival repeat(Ival x, double spacing, bool pow2) const { return irepeat_axis(x, spacing, pow2); }
+    RM_HD Ival limited_repeat(Ival x, double spacing, double limit) const { return ilimited_repeat_axis(x, spacing, limit); }
     RM_HD Ival round(Ival a, double k) const { return a - k; }
+    RM_HD Ival scale(Ival a, double k) const { return i_scale(a, k); }
     RM_HD Ival abs(Ival a) const { return iabs_pw(a); }
     RM_HD Ival union_(Ival a, Ival b) const { return i_union(a, b); }
     RM_HD Ival subtract(Ival a, Ival b) const { return i_subtract(a, b); }

@@ -17,7 +17,7 @@ __global__ __launch_bounds__(kIntervalBlock) void interval_sdf_kernel(const void
                                                                      double* __restrict__ out_lo, double* __restrict__ out_hi)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const IVec3 box = ivec3(iv(lo[3 * i], hi[3 * i]), iv(lo[3 * i + 1], hi[3 * i + 1]), iv(lo[3 * i + 2], hi[3 * i + 2]));
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(kIntervalBlock) void interval_march_kernel(const vo
                                                                        double* __restrict__ normals)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const vec3 o = v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]);
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(kIntervalBlock) void interval_render_kernel(const v
                                                                         double* __restrict__ normal, int32_t* __restrict__ steps)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int py = row0 + (int)(i / (size_t)width), px = (int)(i % (size_t)width);

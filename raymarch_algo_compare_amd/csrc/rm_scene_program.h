@@ -33,8 +33,8 @@ constexpr int kProgMaxConst = kProgMaxArgs * kProgMaxOps;
 constexpr uint32_t kProgTranslated = 1u << 13;
 
 // The device image of a program (what a launch's scene_data points to).  code[i]: bits 0-5 opcode, 6-9 value slot,
-// 10-12 point slot, 13-15 axes of RM_SOP_REPEAT with a positive spacing, 16-31 offset of the constants in k[].  Two
-// flags reuse bits a word's opcode leaves free:
+// 10-12 point slot, 13-15 axes of RM_SOP_REPEAT / RM_SOP_LIMITED_REPEAT with a positive spacing, 16-31 offset of the
+// constants in k[].  Two flags reuse bits a word's opcode leaves free:
 //  * a primitive with bit 13 set is `translate, primitive, pop point` fused (its first three constants are the offset):
 //    the same arithmetic, p - offset then the primitive, without the trip through the point stack;
 //  * RM_SOP_REPEAT: bits 6-8 mark the axes whose spacing is a power of two in [2^-64, 2^64]; there py_mod_pow2 (the
@@ -53,7 +53,7 @@ struct ProgWord {
     RM_HD int pslot() const { return (int)((w >> 10) & 7u); }          // point slot saved to / restored from
     RM_HD int ko() const { return (int)(w >> 16); }                    // offset of the constants in k[]
     RM_HD bool translated() const { return (w & kProgTranslated) != 0; }           // a primitive fused with its translate
-    RM_HD bool axis(int a) const { return (w & (1u << (13 + a))) != 0; }           // RM_SOP_REPEAT: axis a is repeated
+    RM_HD bool axis(int a) const { return (w & (1u << (13 + a))) != 0; }           // RM_SOP_REPEAT, RM_SOP_LIMITED_REPEAT: axis a is repeated
     RM_HD bool pow2(int a) const { return (w & (1u << (6 + a))) != 0; }            // ... with a power-of-two spacing
 };
 
@@ -71,10 +71,16 @@ RM_HD int program_op_args(int op)
         case RM_SOP_CONE: return 3;
         case RM_SOP_SMOOTH_UNION: case RM_SOP_SMOOTH_SUBTRACT: case RM_SOP_SMOOTH_INTERSECT: return 1;
         case RM_SOP_TRANSLATE: case RM_SOP_REPEAT: return 3;
-        case RM_SOP_ROUND: case RM_SOP_ONION: return 1;
+        case RM_SOP_ROUND: case RM_SOP_ONION: case RM_SOP_SCALE: return 1;
+        case RM_SOP_LIMITED_REPEAT: return 6;
+        case RM_SOP_MENGER_CROSS: case RM_SOP_GYROID: return 2;
         default: return 0;
     }
 }
+
+// the three kinds of op the walks tell apart by their opcode (wave-uniform)
+RM_HD bool prog_is_transform(int op) { return (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) || op == RM_SOP_LIMITED_REPEAT; }
+RM_HD bool prog_is_primitive(int op) { return op <= RM_SOP_CONE || op >= RM_SOP_MENGER_CROSS; }
 
 // ---- scenes/primitives.py functions rm_scenes.h does not already hold ---------------------------------------------
 
@@ -127,6 +133,46 @@ RM_HD double repeat_axis_any(double x, double spacing, bool pow2)
     return m - spacing * 0.5;
 }
 
+// ---- the four ops beyond primitives.py (scenes/catalog.py) ------------------------------------------------------------
+
+// the cell index of RM_SOP_LIMITED_REPEAT, one axis with spacing c > 0 (Box Lattice, :584-588): non-decreasing in x
+RM_HD double limited_repeat_cell(double x, double c, double l) { return py_max(-l, py_min(l, rm_floor(x / c + 0.5))); }
+RM_HD double limited_repeat_axis(double x, double c, double l) { return x - c * limited_repeat_cell(x, c, l); }
+
+// one trip of the Menger loop (:221-237); s3 = s * 3.0 as the host multiplied it.  float.__mod__ by 2.0 is py_mod_pow2 for
+// every argument: the quotient a / 2 cannot overflow.
+RM_HD double menger_fold(double x, double s) { return rm_fabs(1.0 - 3.0 * rm_fabs(py_mod_pow2(x * s, 2.0) - 1.0)); }
+RM_HD double sd_menger_cross(vec3 p, double s, double s3)
+{
+    const double rx = menger_fold(p.x, s), ry = menger_fold(p.y, s), rz = menger_fold(p.z, s);
+    const double da = py_max(rx, ry);
+    const double db = py_max(ry, rz);
+    const double dc = py_max(rz, rx);
+    return (py_min(da, py_min(db, dc)) - 1.0) / s3;
+}
+
+// the gyroid sheet (:510-514): NaN where rm_sin / rm_cos are (|freq * p| >= 0x1.921fbp+26 or not finite)
+RM_HD double sd_gyroid(vec3 p, double freq, double lipschitz)
+{
+    // One axis per trip of a loop that stays a loop: rm_sincos is branch-free, every one of its conditions is a wave mask in a
+    // scalar register pair, and three copies side by side are what pushes the interpreter's kernels over their scalar
+    // registers.  (The catalogue's Gyroid, a kernel of its own, unrolls.)  Same operations on the same values.
+    // (the axes rotate through q0 and the results shift through s0..s2 / c0..c2: no select on the trip number, whose
+    // masks would be scalar register pairs again)
+    double q0 = p.x, q1 = p.y, q2 = p.z;
+    double sx = 0.0, cx = 0.0, sy = 0.0, cy = 0.0, sz = 0.0, cz = 0.0;
+#pragma unroll 1
+    for (int a = 0; a < 3; ++a) {
+        double s, c;
+        rm_sincos(freq * q0, &s, &c);
+        sx = sy; sy = sz; sz = s;
+        cx = cy; cy = cz; cz = c;
+        const double t = q0;
+        q0 = q1; q1 = q2; q2 = t;
+    }
+    return (sx * cy + sy * cz + sz * cx) / lipschitz;
+}
+
 // ---- the interpreter ----------------------------------------------------------------------------------------------
 
 // N register slots of a T (a record of doubles: double, vec3, Ival, IVec3, DIval), kept lane by lane.  Slot i
@@ -177,8 +223,8 @@ struct Slots {
 // The walk over a program image for the two sound evaluations of a program: over a box (IntervalAlgebra, rm_interval.h)
 // and over a box with the derivative along a ray (DualAlgebra, rm_segment.h).  (program_eval below keeps its own loop:
 // DESIGN.md section 3, "Interval oracle".)
-// An algebra names its Value and its Point (a record with members x, y, z) and provides the eight primitives, translate,
-// repeat of one coordinate, the two modifiers and the six combinators; it is an object because the dual one carries the
+// An algebra names its Value and its Point (a record with members x, y, z) and provides the ten primitives, translate,
+// repeat and limited repeat of one coordinate, the three modifiers and the six combinators; it is an object because the dual one carries the
 // ray's direction.  Src: nops(), word(i) (wave-uniform), k(i).
 template <class A, class Src>
 RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::Point p)
@@ -192,7 +238,7 @@ RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::P
         const ProgWord w{ src.word(pc) };
         const int slot = w.slot(), pslot = w.pslot(), op = w.op();
         int ko = w.ko();
-        if (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) {
+        if (prog_is_transform(op)) {
             if (op == RM_SOP_POP_POINT) {
                 p = saved.get(pslot, p);
             } else {
@@ -200,16 +246,20 @@ RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::P
                 const double kx = src.k(ko), ky = src.k(ko + 1), kz = src.k(ko + 2);
                 if (op == RM_SOP_TRANSLATE) {
                     p = alg.translate(p, kx, ky, kz);                                // :99-100
-                } else {                                                             // :102-108
+                } else if (op == RM_SOP_REPEAT) {                                    // :102-108
                     if (w.axis(0)) p.x = alg.repeat(p.x, kx, w.pow2(0));
                     if (w.axis(1)) p.y = alg.repeat(p.y, ky, w.pow2(1));
                     if (w.axis(2)) p.z = alg.repeat(p.z, kz, w.pow2(2));
+                } else {                                                             // RM_SOP_LIMITED_REPEAT
+                    if (w.axis(0)) p.x = alg.limited_repeat(p.x, kx, src.k(ko + 3));
+                    if (w.axis(1)) p.y = alg.limited_repeat(p.y, ky, src.k(ko + 4));
+                    if (w.axis(2)) p.z = alg.limited_repeat(p.z, kz, src.k(ko + 5));
                 }
             }
             continue;
         }
         V r;
-        if (op <= RM_SOP_CONE) {                                                     // primitives: push
+        if (prog_is_primitive(op)) {                                                 // primitives: push
             P q = p;
             if (w.translated()) {                                                    // fused op_translate (:99-100)
                 q = alg.translate(q, src.k(ko), src.k(ko + 1), src.k(ko + 2));
@@ -226,12 +276,15 @@ RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::P
                                     src.k(ko + 6));
                     break;
                 case RM_SOP_CAPPED_TORUS: r = alg.capped_torus(q, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
+                case RM_SOP_MENGER_CROSS: r = alg.menger_cross(q, src.k(ko), src.k(ko + 1)); break;
+                case RM_SOP_GYROID: r = alg.gyroid(q, src.k(ko), src.k(ko + 1)); break;
                 default: r = alg.cone(q, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
             }
         } else {
             const V a = vals.get(slot, vals.at(RM_SCENE_PROGRAM_MAX_VALUES - 1));
             if (op >= RM_SOP_ROUND) {                                                // distance modifiers
-                r = op == RM_SOP_ROUND ? alg.round(a, src.k(ko)) : alg.round(alg.abs(a), src.k(ko));   // :110-111, :113-114
+                if (op == RM_SOP_SCALE) r = alg.scale(a, src.k(ko));
+                else r = op == RM_SOP_ROUND ? alg.round(a, src.k(ko)) : alg.round(alg.abs(a), src.k(ko));   // :110-111, :113-114
             } else {                                                                 // combinators: d1 = a, d2 = b
                 const V b = vals.get(slot + 1, vals.at(RM_SCENE_PROGRAM_MAX_VALUES - 1));
                 switch (op) {
@@ -269,8 +322,10 @@ RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::P
         x##j = (i) == j ? q.x : x##j; y##j = (i) == j ? q.y : y##j; z##j = (i) == j ? q.z : z##j;                     \
     } while (0)
 
-// Src: nops(), word(i) (wave-uniform), k(i)
-template <class Src>
+// Src: nops(), word(i) (wave-uniform), k(i).  EXT: the four ops beyond primitives.py (RM_SOP_SCALE .. RM_SOP_GYROID) are
+// built in (SceneExtProgram below).  Without it every test on them is a compile-time constant and the walk is the one the
+// interpreter had before those ops existed -- the host never sends a program that holds one to such a kernel.
+template <bool EXT = true, class Src>
 RM_HD double program_eval(const Src& src, vec3 p)
 {
     double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3_ = 0.0, v4 = 0.0, v5 = 0.0, v6 = 0.0, v7 = 0.0;
@@ -280,7 +335,7 @@ RM_HD double program_eval(const Src& src, vec3 p)
     for (int pc = 0; pc < n; ++pc) {
         const ProgWord w{ src.word(pc) };
         const int slot = w.slot(), pslot = w.pslot(), ko = w.ko(), op = w.op();
-        if (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) {
+        if (EXT ? prog_is_transform(op) : (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT)) {
             if (op == RM_SOP_POP_POINT) {
                 vec3 r = v3(x3, y3, z3);
                 r = pslot == 2 ? v3(x2, y2, z2) : r;
@@ -292,16 +347,20 @@ RM_HD double program_eval(const Src& src, vec3 p)
                 const double kx = src.k(ko), ky = src.k(ko + 1), kz = src.k(ko + 2);
                 if (op == RM_SOP_TRANSLATE) {
                     p = p - v3(kx, ky, kz);                                          // :99-100
-                } else {                                                             // :102-108
+                } else if (!EXT || op == RM_SOP_REPEAT) {                            // :102-108
                     if (w.axis(0)) p.x = repeat_axis_any(p.x, kx, w.pow2(0));
                     if (w.axis(1)) p.y = repeat_axis_any(p.y, ky, w.pow2(1));
                     if (w.axis(2)) p.z = repeat_axis_any(p.z, kz, w.pow2(2));
+                } else {                                                             // RM_SOP_LIMITED_REPEAT
+                    if (w.axis(0)) p.x = limited_repeat_axis(p.x, kx, src.k(ko + 3));
+                    if (w.axis(1)) p.y = limited_repeat_axis(p.y, ky, src.k(ko + 4));
+                    if (w.axis(2)) p.z = limited_repeat_axis(p.z, kz, src.k(ko + 5));
                 }
             }
             continue;
         }
         double r;
-        if (op <= RM_SOP_CONE) {                                                     // primitives: push
+        if (EXT ? prog_is_primitive(op) : op <= RM_SOP_CONE) {                       // primitives: push
             vec3 p0 = p;
             int ko = w.ko();
             if (w.translated()) {                                               // fused op_translate (:99-100)
@@ -319,6 +378,16 @@ RM_HD double program_eval(const Src& src, vec3 p)
                                    src.k(ko + 6));
                     break;
                 case RM_SOP_CAPPED_TORUS: r = sd_capped_torus(p, src.k(ko), src.k(ko + 1), src.k(ko + 2), src.k(ko + 3)); break;
+                // The two labels below stay in the switch without EXT too, with the default's body: no such op arrives there,
+                // the compiler folds them into the default, and one switch serves both instantiations.
+                case RM_SOP_MENGER_CROSS:
+                    if constexpr (EXT) r = sd_menger_cross(p, src.k(ko), src.k(ko + 1));
+                    else r = sd_cone(p, src.k(ko), src.k(ko + 1), src.k(ko + 2));
+                    break;
+                case RM_SOP_GYROID:
+                    if constexpr (EXT) r = sd_gyroid(p, src.k(ko), src.k(ko + 1));
+                    else r = sd_cone(p, src.k(ko), src.k(ko + 1), src.k(ko + 2));
+                    break;
                 default: r = sd_cone(p, src.k(ko), src.k(ko + 1), src.k(ko + 2)); break;
             }
             p = p0;
@@ -326,7 +395,8 @@ RM_HD double program_eval(const Src& src, vec3 p)
             double a, b;
             RM_PV_GET(slot, a);
             if (op >= RM_SOP_ROUND) {                                                // distance modifiers
-                r = op == RM_SOP_ROUND ? a - src.k(ko) : rm_fabs(a) - src.k(ko);     // :110-111, :113-114
+                if (EXT && op == RM_SOP_SCALE) r = a * src.k(ko);
+                else r = op == RM_SOP_ROUND ? a - src.k(ko) : rm_fabs(a) - src.k(ko);     // :110-111, :113-114
             } else {                                                                 // combinators: d1 = a, d2 = b
                 RM_PV_GET(slot + 1, b);
                 switch (op) {
@@ -368,7 +438,12 @@ struct ProgSrc {
 };
 #endif
 
-struct SceneProgram {
+// The interpreter as a scene functor, in two instantiations: SceneProgram without the four ops beyond primitives.py and
+// without the sin / cos table in LDS -- the kernels of every program that holds none of those ops -- and SceneExtProgram with
+// both, chosen by the host for a program that holds one (program_has_ext).  DESIGN.md section 3, "Program extensions", has
+// the measurements that decided for two and for where the line runs.
+template <bool EXT>
+struct ProgramScene {
     static constexpr bool kLaunchData = true;
 #if defined(__HIP_DEVICE_COMPILE__)
     // prologue of a kernel (all threads of the workgroup; the barrier follows in rm_load_tables).  The bounds are
@@ -381,7 +456,7 @@ struct SceneProgram {
         for (int i = threadIdx.x; i < nk; i += blockDim.x) rm_s_prog_k[i] = img->k[i];
         if (threadIdx.x == 0) rm_s_prog_nops = n;
     }
-    static __device__ __forceinline__ double sdf(vec3 p) { return program_eval(ProgSrc{}, p); }
+    static __device__ __forceinline__ double sdf(vec3 p) { return program_eval<EXT>(ProgSrc{}, p); }
 #else
 #if defined(__HIPCC__)
     static __device__ void load(const void*) {}      // (hipcc's host pass; the device pass has the body above)
@@ -390,9 +465,23 @@ struct SceneProgram {
 #endif
 };
 
+struct SceneProgram : ProgramScene<false> {};
+struct SceneExtProgram : ProgramScene<true> {};
+// RM_SOP_GYROID reads the sin / cos table: the kernels that hold the op stage it next to the pow tables
+template <> struct SceneTables<SceneExtProgram> { static constexpr unsigned value = TB_POW | TB_SINCOS; };
+
+// (host code) does the image hold an op that needs SceneExtProgram's kernels?
+inline bool program_has_ext(const ProgramImage& img)
+{
+    for (int i = 0; i < img.nops; ++i)
+        if (ProgWord{ img.code[i] }.op() >= RM_SOP_SCALE) return true;
+    return false;
+}
+
 // (host code) Validates a program and writes its device image.  false with the reason in `why` for a malformed program: opcode out
 // of range, reserved field set, non-finite or (for unused entries) non-zero constant, smooth k == 0 (a division by zero
-// in the reference), value stack deeper than RM_SCENE_PROGRAM_MAX_VALUES or popped when empty, more than
+// in the reference), a scale factor, Menger scale or gyroid lipschitz that is not > 0, a Menger f[1] that is not f[0] * 3.0,
+// a negative limit of a limited repeat, value stack deeper than RM_SCENE_PROGRAM_MAX_VALUES or popped when empty, more than
 // RM_SCENE_PROGRAM_MAX_POINTS nested transforms or a pop without a transform, not exactly one value left, a transform
 // left open, length outside 1..RM_SCENE_PROGRAM_MAX_OPS.
 inline bool program_encode(const RmSceneOp* ops, int32_t nops, ProgramImage* img, char* why, size_t why_len)
@@ -421,21 +510,25 @@ inline bool program_encode(const RmSceneOp* ops, int32_t nops, ProgramImage* img
                 slot = (uint32_t)(vsp - 2);
                 --vsp;
                 break;
-            case RM_SOP_ROUND: case RM_SOP_ONION:
+            case RM_SOP_ROUND: case RM_SOP_ONION: case RM_SOP_SCALE:
+                if (o.op == RM_SOP_SCALE && !(o.f[0] > 0.0)) return snprintf(why, why_len, "op %d: scale factor must be > 0", i), false;
                 if (vsp < 1) return snprintf(why, why_len, "op %d: modifier needs a value, the stack is empty", i), false;
                 slot = (uint32_t)(vsp - 1);
                 break;
-            case RM_SOP_TRANSLATE: case RM_SOP_REPEAT:
+            case RM_SOP_TRANSLATE: case RM_SOP_REPEAT: case RM_SOP_LIMITED_REPEAT:
+                if (o.op == RM_SOP_LIMITED_REPEAT)
+                    for (int j = 3; j < 6; ++j)
+                        if (o.f[j] < 0.0) return snprintf(why, why_len, "op %d: limit f[%d] is negative", i, j), false;
                 if (psp >= RM_SCENE_PROGRAM_MAX_POINTS)
                     return snprintf(why, why_len, "op %d: more than %d nested transforms", i, RM_SCENE_PROGRAM_MAX_POINTS), false;
                 pslot = (uint32_t)psp++;
-                if (o.op == RM_SOP_REPEAT)
+                if (o.op != RM_SOP_TRANSLATE)
                     for (int j = 0; j < 3; ++j)
                         if (o.f[j] > 0.0) {
                             axes |= 1u << j;
                             int e = 0;
                             const double m = frexp(o.f[j], &e);
-                            if (m == 0.5 && e >= -63 && e <= 65) slot |= 1u << j;      // a power of two in [2^-64, 2^64]
+                            if (o.op == RM_SOP_REPEAT && m == 0.5 && e >= -63 && e <= 65) slot |= 1u << j;   // a power of two in [2^-64, 2^64]
                         }
                 break;
             case RM_SOP_POP_POINT:
@@ -443,6 +536,11 @@ inline bool program_encode(const RmSceneOp* ops, int32_t nops, ProgramImage* img
                 pslot = (uint32_t)--psp;
                 break;
             default:   // primitives
+                if (o.op == RM_SOP_MENGER_CROSS) {
+                    if (!(o.f[0] > 0.0)) return snprintf(why, why_len, "op %d: Menger scale must be > 0", i), false;
+                    if (o.f[1] != o.f[0] * 3.0) return snprintf(why, why_len, "op %d: f[1] must be the scale times 3.0", i), false;
+                }
+                if (o.op == RM_SOP_GYROID && !(o.f[1] > 0.0)) return snprintf(why, why_len, "op %d: gyroid lipschitz must be > 0", i), false;
                 if (vsp >= RM_SCENE_PROGRAM_MAX_VALUES)
                     return snprintf(why, why_len, "op %d: value stack deeper than %d", i, RM_SCENE_PROGRAM_MAX_VALUES), false;
                 slot = (uint32_t)vsp++;
@@ -456,7 +554,7 @@ inline bool program_encode(const RmSceneOp* ops, int32_t nops, ProgramImage* img
     int n = 0, nk = 0;
     for (int i = 0; i < nops; ++i) {
         const RmSceneOp& o = ops[i];
-        if (o.op == RM_SOP_TRANSLATE && i + 2 < nops && ops[i + 1].op <= RM_SOP_CONE && ops[i + 2].op == RM_SOP_POP_POINT) {
+        if (o.op == RM_SOP_TRANSLATE && i + 2 < nops && prog_is_primitive(ops[i + 1].op) && ops[i + 2].op == RM_SOP_POP_POINT) {
             img->code[n++] = word[i + 1] | kProgTranslated | (uint32_t)nk << 16;
             for (int j = 0; j < 3; ++j) img->k[nk++] = o.f[j];
             for (int j = 0; j < program_op_args(ops[i + 1].op); ++j) img->k[nk++] = ops[i + 1].f[j];

@@ -2,7 +2,8 @@
 // Instantiates render / march_rays kernels for every strategy and the sdf_eval kernel
 // of that scene, and exports their launchers through rm::scene_launchers_<id>().
 // With -DRM_SCENE_PROGRAM instead: the same kernels for the scene-program interpreter (rm_scene_program.h), exported
-// through rm::scene_launchers_program(); no single-launch pipeline and no team forms.
+// through rm::scene_launchers_program(); no single-launch pipeline and no team forms.  With -DRM_SCENE_PROGRAM_EXT as
+// well: the interpreter with the four ops beyond primitives.py (SceneExtProgram), exported through rm::scene_launchers_program_ext().
 #include "rm_kernels.h"
 #if defined(RM_SCENE_PROGRAM)
 #include "rm_scene_program.h"
@@ -16,7 +17,9 @@
 
 namespace rm {
 
-#if defined(RM_SCENE_PROGRAM)
+#if defined(RM_SCENE_PROGRAM_EXT)
+using SceneT = SceneExtProgram;
+#elif defined(RM_SCENE_PROGRAM)
 using SceneT = SceneProgram;
 #else
 template <int ID> struct SceneById;
@@ -185,7 +188,11 @@ static hipError_t march_rays_team(int strategy, const MarchCfg& cfg, const doubl
 
 #if defined(RM_SCENE_PROGRAM)
 static_assert(!kIter, "a scene program has no resumable evaluation");
+#if defined(RM_SCENE_PROGRAM_EXT)
+#define RM_LAUNCHERS_FN scene_launchers_program_ext
+#else
 #define RM_LAUNCHERS_FN scene_launchers_program
+#endif
 #else
 #define RM_CAT2(a, b) a##b
 #define RM_CAT(a, b) RM_CAT2(a, b)

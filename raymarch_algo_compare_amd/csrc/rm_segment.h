@@ -10,7 +10,7 @@
 //  * every other op: `val` is the interval extension of rm_interval.h itself (i_cylinder, i_capsule, ... are called, not
 //    restated), `der` is the chain rule through the pointwise formula.  DESIGN.md section 3, "Segment ceiling", gives the
 //    soundness argument of each rule.
-// A translated or repeated coordinate keeps d/dtau = rd_c, so the point is a box (IVec3) plus the constant direction and
+// A translated, repeated or limited-repeated coordinate keeps d/dtau = rd_c (wherever it is differentiable), so the point is a box (IVec3) plus the constant direction and
 // the four saved boxes need no derivative slots.  Rounding is to nearest, as in the reference.
 #pragma once
 
@@ -164,6 +164,40 @@ RM_HD DIval d_cone(DVec3 p, double c, double s, double height)
     return dv(i_cone(dvals(p), c, s, height), max_der(-d1, d2));
 }
 
+// RM_SOP_MENGER_CROSS: a is x * s up to jumps that |a| does not see, so d|a|/dtau follows from a's enclosure and the
+// exact slope s * rd_c; where the box may span a jump a's enclosure is [-1, 1], which spans 0, and abs_der gives the whole
+// of +-s |rd_c|.  The rest is abs, max and min: the decided branch's slope, else the hull.
+RM_HD DIval dmenger_fold(DIval x, double s)
+{
+    const double d = s * x.der.lo;                                       // x.der is the constant rd_c
+    const DIval b = dabs_pw(dv(imenger_a(x.val, s), iv(d, d)));
+    return dabs_pw(dv(iv(1.0 - 3.0 * b.val.hi, 1.0 - 3.0 * b.val.lo), -(b.der * 3.0)));
+}
+RM_HD DIval d_menger_cross(DVec3 p, double s, double s3)
+{
+    const DIval rx = dmenger_fold(p.x, s), ry = dmenger_fold(p.y, s), rz = dmenger_fold(p.z, s);
+    const DIval da = dv(i_intersect(rx.val, ry.val), max_der(rx, ry));
+    const DIval db = dv(i_intersect(ry.val, rz.val), max_der(ry, rz));
+    const DIval dc = dv(i_intersect(rz.val, rx.val), max_der(rz, rx));
+    const DIval dbc = dv(i_union(db.val, dc.val), min_der(db, dc));
+    const Ival der = min_der(da, dbc);
+    return dv(i_menger_cross(dvals(p), s, s3), iv(der.lo / s3, der.hi / s3));
+}
+
+// RM_SOP_GYROID: (sin q)' = cos q * q', (cos q)' = -sin q * q' with q' = freq * rd_c, by the same interval sin / cos; the
+// products and sums are DIval's, whose val half is the Ival operation i_gyroid performs.
+RM_HD DIval d_gyroid(DVec3 p, double freq, double lipschitz)
+{
+    const ISinCos3 sc = isincos3(dvals(p), freq);
+    const ISinCos x = sc.x, y = sc.y, z = sc.z;
+    const double qx = freq * p.x.der.lo, qy = freq * p.y.der.lo, qz = freq * p.z.der.lo;
+    const DIval sx = dv(x.s, x.c * qx), cx = dv(x.c, -(x.s * qx));
+    const DIval sy = dv(y.s, y.c * qy), cy = dv(y.c, -(y.s * qy));
+    const DIval sz = dv(z.s, z.c * qz), cz = dv(z.c, -(z.s * qz));
+    const DIval g = sx * cy + sy * cz + sz * cx;
+    return dv(iv(g.val.lo / lipschitz, g.val.hi / lipschitz), iv(g.der.lo / lipschitz, g.der.hi / lipschitz));
+}
+
 // ---- the interpreter ----------------------------------------------------------------------------------------------
 
 // evaluation over the box of a ray segment with direction rd (program_walk, rm_scene_program.h).  The point is the
@@ -180,7 +214,10 @@ struct DualAlgebra : IntervalAlgebra {
     RM_HD DIval capsule(IVec3 p, vec3 a, vec3 b, double radius) const { return d_capsule(dvec3(p, rd), a, b, radius); }
     RM_HD DIval capped_torus(IVec3 p, double sc0, double sc1, double ra, double rb) const { return d_capped_torus(dvec3(p, rd), sc0, sc1, ra, rb); }
     RM_HD DIval cone(IVec3 p, double c, double s, double height) const { return d_cone(dvec3(p, rd), c, s, height); }
+    RM_HD DIval menger_cross(IVec3 p, double s, double s3) const { return d_menger_cross(dvec3(p, rd), s, s3); }
+    RM_HD DIval gyroid(IVec3 p, double freq, double lipschitz) const { return d_gyroid(dvec3(p, rd), freq, lipschitz); }
     RM_HD DIval round(DIval a, double k) const { return a - k; }
+    RM_HD DIval scale(DIval a, double k) const { return dv(i_scale(a.val, k), i_scale(a.der, k)); }
     RM_HD DIval abs(DIval a) const { return dabs_pw(a); }
     RM_HD DIval union_(DIval a, DIval b) const { return dv(i_union(a.val, b.val), min_der(a, b)); }
     RM_HD DIval subtract(DIval a, DIval b) const { return dv(i_subtract(a.val, b.val), max_der(a, -b)); }

@@ -16,7 +16,7 @@ __global__ __launch_bounds__(kSegmentBlock) void segment_sdf_kernel(const void* 
                                                                    double* __restrict__ out)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double* s = segs + 8 * i;
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(kSegmentBlock) void segment_march_kernel(const void
                                                                      double* __restrict__ cursor)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const vec3 o = v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]);
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kSegmentBlock) void segment_render_kernel(const voi
                                                                       int32_t* __restrict__ iters, double* __restrict__ cursor)
 {
     SceneProgram::load(prog);
-    rm_load_tables<SceneProgram>();
+    rm_load_tables<SceneExtProgram>();      // the pow tables and, for RM_SOP_GYROID, sin / cos
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int py = row0 + (int)(i / (size_t)width), px = (int)(i % (size_t)width);

@@ -8,7 +8,12 @@ program (RmSceneOp[], include/rm_hip.h) that the device interpreter evaluates (c
 The builder's names and argument orders are the reference's, without the point argument: a point transform takes the
 subtree it applies to (`op_translate(offset, child)`, `op_repeat(spacing, child)`), a distance modifier the subtree it
 modifies (`op_round(child, radius)`, `op_onion(child, thickness)`).  `sd_cone`'s cos / sin of the angle are computed
-here by Python's math (the libm the reference calls), so the device never evaluates trigonometry.
+here by Python's math (the libm the reference calls).
+
+Four ops go beyond primitives.py, enough to write five more catalogue scenes as programs (catalogue_twins):
+`op_scale(child, factor)` multiplies a distance, `op_limited_repeat(spacing, limit, child)` is a finite lattice,
+`sd_menger_cross(scale)` is one trip of the Menger sponge's fold and `sd_gyroid(freq, lipschitz)` the gyroid sheet (the
+one op whose sin / cos the device evaluates, with the library's exact restatements of libm's).
 
 A registered scene is found by registry.get_scene_by_name and accepted by run_once, HipCollector, run_gpu_benchmark,
 GPURunner (by its id), the sweep and the _native entry points; get_all_scenes() / SCENES stay the 20 catalogue scenes.
@@ -34,6 +39,9 @@ OPCODES = {
     "op_translate": 14, "op_repeat": 15, "pop_point": 16,
     "op_round": 17, "op_onion": 18,
 }
+# the four ops that are not primitives.py functions (RM_SOP_SCALE ..)
+EXT_OPCODES = {"op_scale": 19, "op_limited_repeat": 20, "sd_menger_cross": 21, "sd_gyroid": 22}
+_ALL_OPCODES = {**OPCODES, **EXT_OPCODES}
 MAX_OPS, MAX_VALUES, MAX_POINTS = 256, 8, 4
 
 # op -> (parameters as (name, number of floats), children)
@@ -56,7 +64,12 @@ _SPEC: Dict[str, Tuple[Tuple[Tuple[str, int], ...], Tuple[str, ...]]] = {
     "op_repeat": ((("spacing", 3),), ("child",)),
     "op_round": ((("radius", 1),), ("child",)),
     "op_onion": ((("thickness", 1),), ("child",)),
+    "op_scale": ((("factor", 1),), ("child",)),
+    "op_limited_repeat": ((("spacing", 3), ("limit", 3)), ("child",)),
+    "sd_menger_cross": ((("scale", 1),), ()),
+    "sd_gyroid": ((("freq", 1), ("lipschitz", 1)), ()),
 }
+_POINT_TRANSFORMS = ("op_translate", "op_repeat", "op_limited_repeat")
 
 
 @dataclass(frozen=True)
@@ -181,6 +194,26 @@ def op_onion(child: Expr, thickness) -> Expr:
     return _make("op_onion", {"thickness": thickness}, (child,))
 
 
+def op_scale(child: Expr, factor) -> Expr:
+    """child * factor (factor > 0): a distance that is off by a known factor, e.g. Bad Lipschitz Sphere."""
+    return _make("op_scale", {"factor": factor}, (child,))
+
+
+def op_limited_repeat(spacing, limit, child: Expr) -> Expr:
+    """A finite lattice: per axis x - c * max(-l, min(l, floor(x / c + 0.5))); an axis with spacing 0 is untouched."""
+    return _make("op_limited_repeat", {"spacing": spacing, "limit": limit}, (child,))
+
+
+def sd_menger_cross(scale) -> Expr:
+    """One trip of the Menger sponge's loop (scenes/catalog.py:221-237) at fold scale `scale` (> 0)."""
+    return _make("sd_menger_cross", {"scale": scale}, ())
+
+
+def sd_gyroid(freq, lipschitz) -> Expr:
+    """(sin(q.x) cos(q.y) + sin(q.y) cos(q.z) + sin(q.z) cos(q.x)) / lipschitz with q = freq * p (lipschitz > 0)."""
+    return _make("sd_gyroid", {"freq": freq, "lipschitz": lipschitz}, ())
+
+
 # ---- the catalogue scenes expressible in primitives.py, restated -------------------------------------------------------
 # (csrc/rm_scenes.h, scenes/catalog.py; the built-in scene and its program give bit-identical frames)
 _CLOUD = [(0.4253, 1.3505, 0.9373, 0.4723), (-0.9343, -0.6794, 1.2701, 0.4257), (-1.6821, 1.0922, 1.0100, 0.3090),
@@ -222,6 +255,36 @@ def catalogue_expressions() -> Dict[int, Expr]:
     }
 
 
+_BUMPS = [(0.3841, 1.4500, 0.0000), (-0.4821, 1.3500, 0.4417), (0.0725, 1.2500, -0.8260), (0.5860, 1.1500, 0.7643),
+          (-1.0548, 1.0500, -0.1866), (0.9794, 0.9500, -0.6230), (-0.3209, 0.8500, 1.1935), (-0.5987, 0.7500, -1.1528),
+          (1.2698, 0.6500, 0.4637), (-1.2900, 0.5500, 0.5325), (0.6065, 0.4500, -1.2960), (0.4365, 0.3500, 1.3917),
+          (-1.2797, 0.2500, -0.7416), (1.4577, 0.1500, -0.3205), (-0.8622, 0.0500, 1.2264), (-0.1927, -0.0500, -1.4867),
+          (1.1412, -0.1500, 0.9618), (-1.4778, -0.2500, 0.0611), (1.0339, -0.3500, -1.0289), (-0.0661, -0.4500, 1.4294),
+          (-0.8941, -0.5500, -1.0715), (1.3398, -0.6500, 0.1803), (-1.0663, -0.7500, 0.7419), (0.2713, -0.8500, -1.2058),
+          (0.5771, -0.9500, 1.0072), (-1.0205, -1.0500, -0.3256), (0.8743, -1.1500, -0.4039), (-0.3201, -1.2500, 0.7649),
+          (-0.2213, -1.3500, -0.6152), (0.3400, -1.4500, 0.1787)]
+
+
+def catalogue_twins() -> Dict[int, Expr]:
+    """Scene id -> a program that is bit-identical, as a point function, to a catalogue scene the library holds no
+    interval form for: Menger (9), Bad Lipschitz Sphere (11), Bumpy Sphere (15), Gyroid (16), Box Lattice (18).
+    Registered (register_twin), such a twin gives its scene the interval oracle, the segment tracer and the affine
+    range.  Mandelbulb (10) has none: its estimator is no distance bound."""
+    menger = sd_box((1.0, 1.0, 1.0))
+    for s in (1.0, 3.0, 9.0):
+        menger = op_intersect(menger, sd_menger_cross(s))
+    bumpy = sd_sphere(1.4)
+    for c in _BUMPS:
+        bumpy = op_union(bumpy, op_translate(c, sd_sphere(0.18)))
+    return {
+        9: menger,
+        11: op_scale(sd_sphere(1.0), 2.0),
+        15: bumpy,
+        16: op_intersect(sd_gyroid(3.0, 3.0 * 2.0 * 3.0 ** 0.5), sd_sphere(2.2)),
+        18: op_limited_repeat((1.0, 1.0, 1.0), (2.0, 2.0, 2.0), sd_box((0.3, 0.3, 0.3))),
+    }
+
+
 # ---- JSON ----------------------------------------------------------------------------------------------------------
 
 def expr_from_json(d: dict) -> Expr:
@@ -258,6 +321,8 @@ def compile_ops(expr: Expr) -> List[Tuple[int, Tuple[float, ...]]]:
         if e.op == "sd_cone":     # cos / sin of the angle by the reference's libm (primitives.py:55-56)
             a = e.param("angle_rad")
             return (math.cos(a), math.sin(a), e.param("height"))
+        if e.op == "sd_menger_cross":     # `s *= 3.0` before the division (catalog.py:226, :236)
+            return (e.param("scale"), e.param("scale") * 3.0)
         vals: List[float] = []
         for _, v in e.params:
             vals.extend(v if isinstance(v, tuple) else (v,))
@@ -265,14 +330,14 @@ def compile_ops(expr: Expr) -> List[Tuple[int, Tuple[float, ...]]]:
 
     def emit(e: Expr) -> None:
         kids = _SPEC[e.op][1]
-        if kids == ("child",) and e.op in ("op_translate", "op_repeat"):
-            out.append((OPCODES[e.op], flat(e)))
+        if kids == ("child",) and e.op in _POINT_TRANSFORMS:
+            out.append((_ALL_OPCODES[e.op], flat(e)))
             emit(e.children[0])
             out.append((OPCODES["pop_point"], ()))
             return
         for c in e.children:
             emit(c)
-        out.append((OPCODES[e.op], flat(e)))
+        out.append((_ALL_OPCODES[e.op], flat(e)))
 
     emit(expr)
     return out
@@ -343,6 +408,36 @@ def unregister_scene(name: str) -> None:
         _native.scene_program_destroy(info.id)
 
 
+def twin_name(scene) -> str:
+    """The name a catalogue scene's twin is registered under."""
+    return f"{_catalogue_scene(scene).name} (program)"
+
+
+def _catalogue_scene(scene) -> SceneInfo:
+    if isinstance(scene, SceneInfo):
+        return scene
+    if isinstance(scene, str):
+        return registry.get_scene_by_name(scene)
+    return registry.SCENES[int(scene)]
+
+
+def register_twin(scene) -> SceneInfo:
+    """Register the twin (catalogue_twins) of a catalogue scene -- its id, name or record -- as "<name> (program)" with
+    the scene's Lipschitz bound and suggested camera; returns the record, the existing one if it is registered already.
+    KeyError for a scene without a twin."""
+    base = _catalogue_scene(scene)
+    twins = catalogue_twins()
+    if base.id not in twins:
+        raise KeyError(f"catalogue scene {base.name!r} has no twin program")
+    name = twin_name(base)
+    found = registry.find_program_scene(name)
+    if found is not None:
+        return found
+    return register_scene(name, twins[base.id], category=base.category,
+                          description=f"program twin of the catalogue scene {base.name}", lipschitz=base.lipschitz,
+                          camera_position=base.camera_position, camera_target=base.camera_target)
+
+
 def registered_scenes() -> List[SceneInfo]:
     with _reg_lock:
         return [r.info for r in _registered.values()]
@@ -404,4 +499,5 @@ __all__ = ["Expr", "sd_sphere", "sd_box", "sd_plane", "sd_cylinder", "sd_torus",
            "op_union", "op_subtract", "op_intersect", "op_smooth_union", "op_smooth_subtract", "op_smooth_intersect",
            "op_translate", "op_repeat", "op_round", "op_onion", "expr_from_json", "dumps", "loads", "compile_ops",
            "register_scene", "unregister_scene", "registered_scenes", "expression_of", "scene_entry", "save_scene_file",
-           "load_scene_file", "catalogue_expressions"]
+           "load_scene_file", "catalogue_expressions", "op_scale", "op_limited_repeat", "sd_menger_cross", "sd_gyroid",
+           "catalogue_twins", "register_twin", "twin_name"]

@@ -199,13 +199,27 @@ def ssim_columns(scene, kept: List, oracle_frames: Dict[str, Optional[Dict]]) ->
             row.update(cols)
 
 
-def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float) -> Dict[str, Optional[Dict]]:
-    """The oracle capture of every curated viewpoint of `scene` (None for each when it has no interval extension);
-    `oracle` is one of ORACLES (run_sweep has checked it)."""
+def sound_scene(scene, twins: bool = False):
+    """The scene the sound side evaluates for `scene`: the scene itself when it has an interval extension; with `twins`,
+    the registered program twin (scene_program.register_twin) of a catalogue scene that has none but has a twin; else
+    None."""
+    if interval_oracle.has_interval(scene):
+        return scene
+    if twins:
+        from . import scene_program
+        if scene.id in scene_program.catalogue_twins():
+            return scene_program.register_twin(scene)
+    return None
+
+
+def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float, twins: bool = False) -> Dict[str, Optional[Dict]]:
+    """The oracle capture of every curated viewpoint of `scene` (None for each when it has no interval extension and,
+    with `twins`, no program twin either); `oracle` is one of ORACLES (run_sweep has checked it)."""
     vps = viewpoints_for(scene)
-    if not interval_oracle.has_interval(scene):
+    sound = sound_scene(scene, twins)
+    if sound is None:
         return {vp.name: None for vp in vps}
-    return {vp.name: interval_oracle.interval_capture(scene, Camera(vp.position, vp.target, vp.up, 60.0, width, height), tol=tol)
+    return {vp.name: interval_oracle.interval_capture(sound, Camera(vp.position, vp.target, vp.up, 60.0, width, height), tol=tol)
             for vp in vps}
 
 
@@ -220,13 +234,20 @@ def ceiling_columns(frame: Optional[Dict], oracle: Optional[Dict]) -> Dict:
             "ceiling_iters_p95": c["iters_p95"]}
 
 
-def ceiling_columns_for(scene, width: int, height: int, oracle_frames: Dict[str, Optional[Dict]], tol: float) -> Dict[str, Dict]:
-    """ceiling_columns of every curated viewpoint of `scene` (oracle_frames: oracle_frames_for of the same scene and size)."""
+def ceiling_columns_for(scene, width: int, height: int, oracle_frames: Dict[str, Optional[Dict]], tol: float,
+                        twins: bool = False) -> Dict[str, Dict]:
+    """ceiling_columns of every curated viewpoint of `scene` (oracle_frames: oracle_frames_for of the same scene, size and
+    `twins`)."""
     out = {}
+    sound = sound_scene(scene, twins)
+    cfg = None
+    if sound is not None and sound is not scene:       # a twin: the tracer's clamp on K must admit the scene's own bound
+        from . import _native
+        cfg = _native.segment_config(tol=tol, l_global=max(1.0, float(scene.known_lipschitz_bound() or 1.0)))
     for vp in viewpoints_for(scene):
         truth = oracle_frames.get(vp.name)
         frame = None if truth is None else faithful_segment.faithful_capture(
-            scene, Camera(vp.position, vp.target, vp.up, 60.0, width, height), tol=tol)
+            sound, Camera(vp.position, vp.target, vp.up, 60.0, width, height), tol=tol, cfg=cfg)
         out[vp.name] = ceiling_columns(frame, truth)
     return out
 
@@ -236,14 +257,21 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
               epsilons: Sequence[float] = DEFAULT_EPSILONS, cap: int = 512, hit_threshold: float = 1e-4,
               out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False,
               oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL,
-              ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL, ssim: bool = False) -> List[Dict]:
+              ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL, ssim: bool = False,
+              oracle_twins: bool = False) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
     interval oracle's first hit of its viewpoint (ORACLE_FIELDS; one oracle frame per scene and viewpoint, tolerance
     `oracle_tol`).  ceiling="segment": every row also carries the sound segment tracer's result at its viewpoint
     (CEILING_FIELDS; hit tolerance `ceiling_tol`, scored against the interval oracle at `oracle_tol`).  ssim=True (only
-    with an oracle): every row also carries SSIM_FIELDS against the oracle capture of its viewpoint."""
+    with an oracle): every row also carries SSIM_FIELDS against the oracle capture of its viewpoint.  oracle_twins=True: a
+    catalogue scene without an interval extension but with a program twin (scene_program.catalogue_twins: Menger, Bad
+    Lipschitz Sphere, Bumpy Sphere, Gyroid, Box Lattice) is scored against its twin's oracle capture and ceiling frame; the
+    twin, the same point function bit for bit, stays registered.  Off, those scenes keep their empty cells.  A twin's
+    ceiling frame is traced with the tracer's clamp on K (RmSegmentConfig.l_global) raised to the scene's Lipschitz bound
+    (2 for Bad Lipschitz Sphere), a scene with its own interval form with the default clamp of 1: where the bound is above
+    1 the two kinds of ceiling row come from different tracer configs."""
     if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
         raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
     if ceiling is not None and ceiling not in CEILINGS:
@@ -257,9 +285,10 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     collector = HipCollector(MarchConfig(), device_id=device_id)
     rows: List[Dict] = []
     for scene in scenes:
-        truth = oracle_frames_for(scene, width, height, "interval", oracle_tol) if oracle is not None or ceiling is not None else None
+        truth = (oracle_frames_for(scene, width, height, "interval", oracle_tol, oracle_twins)
+                 if oracle is not None or ceiling is not None else None)
         ofr = truth if oracle is not None else None
-        ccols = ceiling_columns_for(scene, width, height, truth, ceiling_tol) if ceiling is not None else None
+        ccols = ceiling_columns_for(scene, width, height, truth, ceiling_tol, oracle_twins) if ceiling is not None else None
         kept: Optional[List] = [] if ssim else None
         for strat in strats:
             if strat.has_lipschitz:
@@ -316,13 +345,19 @@ def main(argv=None) -> int:
     ap.add_argument("--ceiling-tol", type=float, default=faithful_segment.DEFAULT_TOL, help="the ceiling tracer's hit tolerance")
     ap.add_argument("--ssim", action="store_true",
                     help="with --oracle: add the SSIM columns of every frame against the oracle capture (depth_ssim, normal_ssim, ...)")
+    ap.add_argument("--oracle-twins", action="store_true",
+                    help="with --oracle / --ceiling: score a catalogue scene that has no interval form against its program twin "
+                         "(Menger, Bad Lipschitz Sphere, Bumpy Sphere, Gyroid, Box Lattice); a twin's ceiling is traced with l_global = the "
+                         "scene's Lipschitz bound, not the default 1")
     a = ap.parse_args(argv)
     if a.ssim and a.oracle is None:
         ap.error("--ssim needs --oracle")
+    if a.oracle_twins and a.oracle is None and a.ceiling is None:
+        ap.error("--oracle-twins needs --oracle or --ceiling")
     rows = run_sweep([s for s in a.scenes.split(",") if s], [s for s in a.strategies.split(",") if s], a.mode, a.width, a.height,
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
                      a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol,
-                     ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim)
+                     ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim, oracle_twins=a.oracle_twins)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 

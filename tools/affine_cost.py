@@ -2,13 +2,13 @@
 """Per-frame cost of the affine range's march (rm_affine_render, RM_RANGE_AFFINE and RM_RANGE_MEET) on the GPU next to the
 interval oracle (rm_interval_render, without normals) of the same frame, in one process: kernel ms per frame (hipEvent
 timing, median of `--repeats` after `--warmup`) and the SDF segment evaluations of each march, for the 14 catalogue scenes
-with an interval extension, on each scene's default camera (its suggested camera, else (0, 0, 5) looking at the origin;
-fov 60), at the given sizes.  No time is gated: the comparison is against rm_interval_render of the same build and
+with an interval extension (with `--twins` also the five program twins, `--only-twins` those alone), on each scene's
+default camera (its suggested camera, else (0, 0, 5) looking at the origin; fov 60), at the given sizes.  No time is gated: the comparison is against rm_interval_render of the same build and
 scene.  A meet probe walks the scene's program twice, so fewer evaluations need not mean less time: that trade is what
 this tool measures.  Appends one JSON line per scene and size to `--out` and prints a markdown table (DESIGN.md section
 3, "Affine range").
 
-Usage:  python tools/affine_cost.py [--sizes 512x512,1920x1080] [--repeats 7] [--warmup 2] [--out profiles/affine/cost.jsonl]
+Usage:  python tools/affine_cost.py [--sizes 512x512,1920x1080] [--repeats 7] [--warmup 2] [--out profiles/affine/cost.jsonl] [--twins | --only-twins]
 """
 import argparse
 import json
@@ -21,7 +21,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
-from raymarch_algo_compare_amd import _native, registry  # noqa: E402
+from raymarch_algo_compare_amd import _native, registry, scene_program  # noqa: E402
 from raymarch_algo_compare_amd.camera import Camera  # noqa: E402
 
 
@@ -39,6 +39,10 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "affine", "cost.jsonl"))
     ap.add_argument("--label", default=None, help="what the library was built from (default: git's short HEAD)")
+    ap.add_argument("--twins", action="store_true",
+                    help="also the program twins of Menger, Bad Lipschitz Sphere, Bumpy Sphere, Gyroid and Box Lattice "
+                         "(scene_program.register_twin)")
+    ap.add_argument("--only-twins", action="store_true", help="the program twins alone")
     a = ap.parse_args()
     if a.repeats < 7:
         ap.error("--repeats must be at least 7")
@@ -49,9 +53,10 @@ def main() -> None:
     print("| scene | size | affine ms | meet ms | interval ms | affine evals | meet evals | interval evals | same hit map |")
     print("|---|---|---|---|---|---|---|---|---|")
     with open(a.out, "a", encoding="utf-8") as f:
-        for scene in registry.get_all_scenes():
-            if not _native.affine_supported(scene.id):
-                continue
+        scenes = [] if a.only_twins else [s for s in registry.get_all_scenes() if _native.affine_supported(s.id)]
+        if a.twins or a.only_twins:
+            scenes += [scene_program.register_twin(sid) for sid in sorted(scene_program.catalogue_twins())]
+        for scene in scenes:
             pos = scene.camera_position or (0.0, 0.0, 5.0)
             tgt = scene.camera_target or (0.0, 0.0, 0.0)
             for W, H in sizes:

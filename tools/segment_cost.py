@@ -2,13 +2,14 @@
 """Per-frame cost of the sound segment tracer (rm_segment_render) on the GPU next to the interval oracle
 (rm_interval_render) and the Standard sphere tracer (rm_render) of the same frame, in one process: kernel ms per frame
 (hipEvent timing, median of `--repeats` after `--warmup`) and the tracer's iters over the hit rays (median / p95 / max)
-for the 14 catalogue scenes with an interval extension, on each scene's default camera (its suggested camera, else
+for the 14 catalogue scenes with an interval extension (with `--twins` also the five program twins, `--only-twins` those
+alone), on each scene's default camera (its suggested camera, else
 (0, 0, 5) looking at the origin; fov 60), at the given sizes.  No time is gated: there is no earlier version of the
 tracer and the reference's NumPy loop is not a time to compare with.  Writes one JSON line per scene and size to `--out`
 and prints a markdown table ("Segment ceiling").  Only the two-pass evaluation (the point, then
 the segment) is built, so one form is timed.
 
-Usage:  python tools/segment_cost.py [--sizes 512x512,1920x1080] [--repeats 7] [--warmup 2] [--out profiles/segment/cost.jsonl]
+Usage:  python tools/segment_cost.py [--sizes 512x512,1920x1080] [--repeats 7] [--warmup 2] [--out profiles/segment/cost.jsonl] [--twins | --only-twins]
 """
 import argparse
 import json
@@ -21,7 +22,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
-from raymarch_algo_compare_amd import _native, registry  # noqa: E402
+from raymarch_algo_compare_amd import _native, registry, scene_program  # noqa: E402
 from raymarch_algo_compare_amd.camera import Camera  # noqa: E402
 from raymarch_algo_compare_amd import faithful_segment as fs  # noqa: E402
 
@@ -40,6 +41,10 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segment", "cost.jsonl"))
     ap.add_argument("--label", default=None, help="what the library was built from (default: git's short HEAD)")
+    ap.add_argument("--twins", action="store_true",
+                    help="also the program twins of Menger, Bad Lipschitz Sphere, Bumpy Sphere, Gyroid and Box Lattice "
+                         "(scene_program.register_twin)")
+    ap.add_argument("--only-twins", action="store_true", help="the program twins alone")
     a = ap.parse_args()
     if a.repeats < 7:
         ap.error("--repeats must be at least 7")
@@ -51,14 +56,17 @@ def main() -> None:
     print("| scene | size | segment ms | interval ms | Standard ms | iters median | p95 | max | budget used up | hit pixels |")
     print("|---|---|---|---|---|---|---|---|---|---|")
     with open(a.out, "w", encoding="utf-8") as f:
-        for scene in registry.get_all_scenes():
-            if not _native.segment_supported(scene.id):
-                continue
+        scenes = [] if a.only_twins else [s for s in registry.get_all_scenes() if _native.segment_supported(s.id)]
+        if a.twins or a.only_twins:
+            scenes += [scene_program.register_twin(sid) for sid in sorted(scene_program.catalogue_twins())]
+        for scene in scenes:
             pos = scene.camera_position or (0.0, 0.0, 5.0)
             tgt = scene.camera_target or (0.0, 0.0, 0.0)
             for W, H in sizes:
                 cam = Camera(pos, tgt, (0.0, 1.0, 0.0), 60.0, W, H).params14()
-                seg = _native.segment_render(scene.id, cam, W, H, warmup=a.warmup, repeats=a.repeats)
+                # the clamp on K admits the scene's own Lipschitz bound (2 for the Bad Lipschitz twin; 1 is the default)
+                scfg = _native.segment_config(l_global=max(1.0, float(scene.lipschitz or 1.0)))
+                seg = _native.segment_render(scene.id, cam, W, H, scfg, warmup=a.warmup, repeats=a.repeats)
                 ivl = _native.interval_render(scene.id, cam, W, H, warmup=a.warmup, repeats=a.repeats)
                 std = _native.render(_native.make_desc(scene.id, standard, cam, W, H), warmup=a.warmup, repeats=a.repeats)
                 hit = seg["hit"] > 0
