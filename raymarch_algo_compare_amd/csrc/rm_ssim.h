@@ -6,7 +6,9 @@
 // Images.  A capture's float32 maps become 8-bit images as the reference's data/capture_io.py makes them (_to_u8: NaN ->
 // 0, +inf -> 1, -inf -> 0, x * 255 in binary32, clamped to [0, 255], truncated):
 //   depth    1 - clamp((depth - lo) / max(hi - lo, 1e-6), 0, 1) on a hit, 0 on a miss ((lo, hi): the REFERENCE capture's
-//            depth range over its hits, (0, 1) without any; near is bright)
+//            depth range over its hits, (0, 1) without any; near is bright.  The range is NumPy's min / max: one NaN hit
+//            depth of the reference makes it (NaN, NaN), and then both depth images are 0 on every hit pixel; a +-inf
+//            hit depth is an ordinary bound)
 //   normal   n * 0.5 + 0.5 on a hit, 0 on a miss, per component
 //   colour   as it is
 // Seven channels: 0 depth, 1..3 normal, 4..6 colour.
@@ -68,17 +70,22 @@ RM_HD SsimDepthRange ssim_depth_range(double lo, double hi)
     return d;
 }
 
-// (min, max) of a capture's depth over its hits; (0, 1) without a hit
+// (min, max) of a capture's depth over its hits; (0, 1) without a hit.  As NumPy's min / max, a NaN on any hit makes
+// both NaN, wherever it sits (`d < a` alone would skip it unless it came first).  ssim_depth_range(NaN, NaN) keeps its
+// floor (`NaN > 1e-6` is false) and that does not matter: lo is NaN, so `depth - lo` is NaN on every hit pixel and the
+// depth image is 0 there whatever the range is.
 inline void ssim_depth_minmax(const float* depth, const uint8_t* hit, size_t n, double* lo, double* hi)
 {
-    bool any = false;
+    bool any = false, nan = false;
     float a = 0.0f, b = 0.0f;
     for (size_t i = 0; i < n; ++i) {
         if (!hit[i]) continue;
         const float d = depth[i];
+        if (d != d) nan = true;
         if (!any) { a = b = d; any = true; }
         else { a = d < a ? d : a; b = d > b ? d : b; }
     }
+    if (nan) a = b = __builtin_nanf("");
     *lo = any ? (double)a : 0.0;
     *hi = any ? (double)b : 1.0;
 }

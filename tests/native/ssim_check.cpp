@@ -3,7 +3,8 @@
 // restatement, with the reference's images and with the device in a container without a GPU.  Never loaded by the product.
 //
 // The loops below walk the image as rm_ssim.hip's workgroups do: tile by tile, the tile's 256 values folded by halves,
-// the tiles' partial sums added in index order.
+// the tiles' partial sums added in index order; the colour images' squared differences likewise, each tile adding the
+// pixels of its staged block that ssim_owns gives it.
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
@@ -39,14 +40,27 @@ double plane_sum(const uint8_t* x, const uint8_t* y, int W, int H)
     return ssim_sum_in_order(part.data(), tx * ty);
 }
 
-long long plane_ssd(const uint8_t* x, const uint8_t* y, size_t n)
+// sum of squared differences of the W x H planes x, y, walked as the device walks them: every tile goes over its staged
+// block (output pixels and halo) and adds the pixels that ssim_owns gives it; the tiles' sums are added in index order
+long long plane_ssd(const uint8_t* x, const uint8_t* y, int W, int H)
 {
-    long long s = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const int d = (int)x[i] - (int)y[i];
-        s += d * d;
+    const int tx = ssim_tiles_x(W), ty = ssim_tiles_y(H);
+    std::vector<long long> part((size_t)tx * ty);
+    for (int t = 0; t < tx * ty; ++t) {
+        const int tix = t % tx, tiy = t / tx, x0 = tix * kSsimTileW, y0 = tiy * kSsimTileH;
+        const bool last_x = tix == tx - 1, last_y = tiy == ty - 1;
+        long long s = 0;
+        for (int ly = 0; ly < kSsimStageH; ++ly)
+            for (int lx = 0; lx < kSsimStageW; ++lx) {
+                const int ix = x0 + lx, iy = y0 + ly;
+                if (ix >= W || iy >= H || !ssim_owns(lx, ly, last_x, last_y)) continue;
+                const size_t p = (size_t)iy * W + (size_t)ix;
+                const int d = (int)x[p] - (int)y[p];
+                s += d * d;
+            }
+        part[t] = s;
     }
-    return s;
+    return ssim_sum_in_order(part.data(), tx * ty);
 }
 
 void images(int W, int H, const float* depth, const float* normal, const float* color, const uint8_t* hit, SsimDepthRange r,
@@ -99,7 +113,7 @@ int rms_scores(int W, int H, const float* r_depth, const float* r_normal, const 
     for (int c = 0; c < kSsimChannels; ++c) {
         if ((c >= 1 && c < kSsimColor0 && !r_normal) || (c >= kSsimColor0 && !r_color)) continue;
         s_sum[c] = plane_sum(x.data() + c * n, y.data() + c * n, W, H);
-        if (c >= kSsimColor0) ssd[c - kSsimColor0] = plane_ssd(x.data() + c * n, y.data() + c * n, n);
+        if (c >= kSsimColor0) ssd[c - kSsimColor0] = plane_ssd(x.data() + c * n, y.data() + c * n, W, H);
     }
     ssim_combine(s_sum, ssd, W, H, r_normal != nullptr, r_color != nullptr, out);
     return 0;

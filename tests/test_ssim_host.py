@@ -8,8 +8,14 @@ float64, cropped by 3.  skimage is not installed, so NO SSIM value comes from th
 pins is the quantisation.  The bound between the host build and the oracle is 1e-9 absolute: the host's window sums are
 exact integers, the oracle's running means carry about 1e-11 of rounding on (co)variances of at most 65025 * 49 / 48, and
 the denominators are at least C1 * C2 ~ 380 -- a per-pixel error far below 1e-9, which a mean cannot exceed.
+
+Section 2b feeds the host build what decides whether the quantisation is right (tests/ssim_edge_cases.py: k/255 and its
+float32 neighbours, values outside [0, 1], NaN, +-inf, +-3.4e38, degenerate normals, non-finite hit depths, one hit, one
+depth), the strongest contrasts, and captures one pixel apart at every tile seam; tests/test_gpu_ssim.py gives the device
+the same inputs.
 """
 import ctypes
+import math
 import os
 import subprocess
 import sys
@@ -18,6 +24,7 @@ import numpy as np
 import pytest
 from scipy.ndimage import uniform_filter
 
+import ssim_edge_cases as E
 from conftest import GOLDEN, ROOT, build_native
 from raymarch_algo_compare_amd import _native, scoring, ssim
 
@@ -47,8 +54,9 @@ def oracle_image(x, y):
 
 def oracle_scores(method, reference):
     """the four scores of two capture dicts, through ssim.to_images"""
-    dr = ssim.depth_range(reference)
-    r, m = ssim.to_images(reference, dr), ssim.to_images(method, dr)
+    with np.errstate(invalid="ignore", over="ignore"):      # non-finite maps (ssim_edge_cases.py)
+        dr = ssim.depth_range(reference)
+        r, m = ssim.to_images(reference, dr), ssim.to_images(method, dr)
     out = [oracle_image(r["depth"], m["depth"]), None, None, None]
     if r["normal"] is not None and m["normal"] is not None:
         out[1] = oracle_image(r["normal"], m["normal"])
@@ -86,10 +94,12 @@ def _maps(c):
     return g("depth"), g("normal"), g("color"), np.ascontiguousarray(np.asarray(c["hit"]) != 0, np.uint8)
 
 
-def host_scores(lib, method, reference):
+def host_scores(lib, method, reference, hit_byte=1):
+    """rms_scores; hit_byte: what a hit is written as in the two hit maps"""
     H, W = np.shape(reference["hit"])
     rd, rn, rc, rh = _maps(reference)
     md, mn, mc, mh = _maps(method)
+    rh, mh = rh * np.uint8(hit_byte), mh * np.uint8(hit_byte)
     out = np.empty(4)
     assert lib.rms_scores(W, H, _f(rd), _f(rn), _f(rc), rh.ctypes.data_as(u8p), _f(md), _f(mn), _f(mc), mh.ctypes.data_as(u8p),
                           out.ctypes.data_as(dp)) == 0
@@ -158,7 +168,8 @@ def test_host_build_equals_the_float64_restatement(lib, W, H, ch):
 
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_constant_images_match_the_closed_form(lib, W, H):
-    for a, b in ((0, 255), (10, 200), (128, 129), (255, 254), (0, 1)):
+    assert E.CONSTANT_PAIRS == ((0, 255), (10, 200), (128, 129), (255, 254), (0, 1))
+    for a, b in E.CONSTANT_PAIRS:
         x, y = np.full((H, W), a, np.uint8), np.full((H, W), b, np.uint8)
         want = (2.0 * a * b + C1) / (a * a + b * b + C1)
         assert abs(host_image(lib, x, y) - want) <= 1e-12, (a, b)
@@ -191,33 +202,139 @@ def test_capture_scores_equal_the_restatement(lib, W, H):
 # ---- 2. the quantisation, against the reference's images ---------------------------------------------------------------------
 
 def golden_cases():
+    """(index, arrays) of the fixture's cases; c4 and later also carry own_drange and img_depth_own"""
     z = np.load(os.path.join(GOLDEN, "ssim_images.npz"))
     for i in range(int(z["ncases"][0])):
-        yield i, {k: z[f"c{i}_{k}"] for k in ("depth", "normal", "color", "hit", "drange", "img_depth", "img_normal", "img_color")}
+        keys = ["depth", "normal", "color", "hit", "drange", "img_depth", "img_normal", "img_color"]
+        keys += [k for k in ("own_drange", "img_depth_own") if f"c{i}_{k}" in z.files]
+        yield i, {k: z[f"c{i}_{k}"] for k in keys}
+
+
+def golden_capture(g):
+    return {"depth": g["depth"], "normal": g["normal"], "color": g["color"], "hit": g["hit"]}
+
+
+def same_range(a, b):
+    """two (lo, hi), a NaN equal to a NaN"""
+    return np.array_equal(np.asarray(a, np.float64), np.asarray(b, np.float64), equal_nan=True)
+
+
+def host_planes(lib, cap, lo, hi):
+    """the (7, H, W) planes of rms_images, untouched ones 0"""
+    H, W = np.shape(cap["hit"])
+    planes = np.zeros((7, H, W), np.uint8)
+    d, nrm, col, hit = _maps(cap)
+    lib.rms_images(W, H, _f(d), _f(nrm), _f(col), hit.ctypes.data_as(u8p), lo, hi, planes.ctypes.data_as(u8p))
+    return planes
+
+
+def host_depth_range(lib, cap):
+    H, W = np.shape(cap["hit"])
+    d, _, _, hit = _maps(cap)
+    lohi = np.empty(2)
+    lib.rms_depth_range(W, H, _f(d), hit.ctypes.data_as(u8p), lohi.ctypes.data_as(dp))
+    return tuple(lohi)
 
 
 def test_quantisation_equals_the_reference_images(lib):
-    n = 0
+    n = own = 0
     for i, g in golden_cases():
-        H, W = g["hit"].shape
-        cap = {"depth": g["depth"], "normal": g["normal"], "color": g["color"], "hit": g["hit"]}
-        lo, hi = (float(v) for v in g["drange"])
-        with np.errstate(invalid="ignore"):
-            img = ssim.to_images(cap, (lo, hi))
-        planes = np.empty((7, H, W), np.uint8)
-        d, nrm, col, hit = _maps(cap)
-        lib.rms_images(W, H, _f(d), _f(nrm), _f(col), hit.ctypes.data_as(u8p), lo, hi, planes.ctypes.data_as(u8p))
-        for key, sl in (("depth", planes[0]), ("normal", np.moveaxis(planes[1:4], 0, 2)), ("color", np.moveaxis(planes[4:7], 0, 2))):
-            assert img[key].dtype == np.uint8 and img[key].tobytes() == g["img_" + key].tobytes(), (i, key, "ssim.to_images")
-            assert sl.tobytes() == g["img_" + key].tobytes(), (i, key, "host build")
+        cap = golden_capture(g)
+        ranges = [("", tuple(float(v) for v in g["drange"]))]
+        if "own_drange" in g:      # the path rm_ssim_scores takes: the range of the capture's own hit depths
+            ranges.append(("_own", tuple(float(v) for v in g["own_drange"])))
+            own += 1
+        for suffix, (lo, hi) in ranges:
+            with np.errstate(invalid="ignore", over="ignore"):
+                img = ssim.to_images(cap, (lo, hi))
+            planes = host_planes(lib, cap, lo, hi)
+            for key, sl in (("depth", planes[0]), ("normal", np.moveaxis(planes[1:4], 0, 2)), ("color", np.moveaxis(planes[4:7], 0, 2))):
+                want = g["img_depth_own"] if (key, suffix) == ("depth", "_own") else g["img_" + key]
+                assert img[key].dtype == np.uint8 and img[key].tobytes() == want.tobytes(), (i, key, suffix, "ssim.to_images")
+                assert sl.tobytes() == want.tobytes(), (i, key, suffix, "host build")
         n += 1
-    assert n == 4
-    # the range of a capture's own depth, by both
+    assert n == 12 and own == 8
+    # the range of a capture's own depth, by both; a NaN on any hit makes it (nan, nan), as the reference's depth_range_of
+    nan_ranges = 0
     for i, g in golden_cases():
-        H, W = g["hit"].shape
-        lohi = np.empty(2)
-        lib.rms_depth_range(W, H, _f(np.ascontiguousarray(g["depth"])), np.ascontiguousarray(g["hit"]).ctypes.data_as(u8p), lohi.ctypes.data_as(dp))
-        assert tuple(lohi) == ssim.depth_range({"depth": g["depth"], "hit": g["hit"]}), i
+        cap = golden_capture(g)
+        got = host_depth_range(lib, cap)
+        assert same_range(got, ssim.depth_range(cap)), (i, got)
+        if "own_drange" in g:
+            assert same_range(got, g["own_drange"]), (i, got, g["own_drange"])
+            assert same_range(ssim.depth_range(cap), g["own_drange"]), i
+            nan_ranges += bool(np.isnan(g["own_drange"]).all())
+    assert nan_ranges == 2      # NaN at a late hit and at the first hit
+
+
+# ---- 2b. edge inputs (ssim_edge_cases.py) -----------------------------------------------------------------------------------
+
+def assert_scores_close(got, want, name):
+    for g, w in zip(got, want):
+        if w is None:
+            assert np.isnan(g), name
+        else:
+            assert abs(g - w) <= TOL, (name, g, w)      # a NaN score fails here
+
+
+@pytest.mark.parametrize("W,H", E.SHAPES)
+def test_edge_captures_equal_the_restatement(lib, W, H):
+    """Non-finite and edge-of-rounding maps: the host build's images equal ssim.to_images byte for byte and its scores the
+    restatement's.  The reference with a NaN depth on a late hit failed before ssim_depth_minmax propagated the NaN."""
+    for name, m, r in E.edge_pairs(W, H):
+        with np.errstate(invalid="ignore", over="ignore"):
+            dr = ssim.depth_range(r)
+            assert same_range(host_depth_range(lib, r), dr), name
+            for cap in (m, r):
+                img, planes = ssim.to_images(cap, dr), host_planes(lib, cap, dr[0], dr[1])
+                assert planes[0].tobytes() == img["depth"].tobytes(), (name, "depth")
+                if img["normal"] is not None:
+                    assert np.moveaxis(planes[1:4], 0, 2).tobytes() == img["normal"].tobytes(), (name, "normal")
+                if img["color"] is not None:
+                    assert np.moveaxis(planes[4:7], 0, 2).tobytes() == img["color"].tobytes(), (name, "color")
+        got, want = host_scores(lib, m, r), oracle_scores(m, r)
+        print(f"{W}x{H} {name}: range {dr} host {list(got)} oracle {want}")
+        assert_scores_close(got, want, name)
+        if want[3] is not None:
+            assert abs(got[3] - want[3]) <= np.spacing(want[3]), (name, got[3], want[3])
+
+
+def period_1_is_negative(name, scores):
+    return "period 1" not in name or (scores[0] < -0.9 and scores[1] < -0.9 and scores[2] < -0.9)
+
+
+@pytest.mark.parametrize("W,H", E.SHAPES)
+def test_contrast_pairs(lib, W, H):
+    for name, m, r, ab in E.contrast_pairs(W, H):
+        got, want = host_scores(lib, m, r), oracle_scores(m, r)
+        print(f"{W}x{H} {name}: host {list(got)} oracle {want}")
+        assert_scores_close(got, want, name)
+        for g, w in zip(got[:3], want[:3]):
+            assert (g < 0.0) == (w < 0.0), (name, g, w)
+        if ab is None:      # a checkerboard against its inverse; of period 7, a small image holds one field only
+            assert period_1_is_negative(name, got)
+        else:
+            a, b = ab
+            closed = (2.0 * a * b + C1) / (a * a + b * b + C1)
+            assert abs(got[1] - closed) <= 1e-12 and abs(got[2] - closed) <= 1e-12, (name, got, closed)
+            assert got[0] == 1.0 and got[3] == abs(a - b), (name, got)
+
+
+@pytest.mark.parametrize("W,H", E.SHAPES)
+def test_one_pixel_is_counted_exactly_once(lib, W, H):
+    """ssim_owns: wherever the one differing pixel lies, the colour RMSE is that of one squared difference"""
+    for name, m, r, d in E.one_hot_pairs(W, H):
+        got = host_scores(lib, m, r)
+        want = math.sqrt(d * d / (3 * W * H))
+        assert abs(got[3] - want) <= np.spacing(want), (name, got[3], want)
+        assert got[0] == 1.0 and got[1] == 1.0 and got[2] < 1.0, (name, got)
+
+
+def test_any_non_zero_hit_byte_is_a_hit(lib):
+    for name, m, r in E.edge_pairs(40, 33)[:4]:
+        one = host_scores(lib, m, r)
+        for byte in (2, 255):
+            assert host_scores(lib, m, r, hit_byte=byte).tobytes() == one.tobytes(), (name, byte)
 
 
 # ---- 3. the C ABI before the device -------------------------------------------------------------------------------------

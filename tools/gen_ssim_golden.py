@@ -8,7 +8,7 @@ by this project).  The SSIM arithmetic is checked against a float64 restatement 
 instead (tests/test_ssim_host.py); this fixture covers the one step that restatement cannot vouch for.
 
   ssim_images.npz   cases "c0" .. "c{n-1}" (n in "ncases"), prefix "c{k}_":
-                    depth  float32 (H, W)     beyond the range on both sides, NaN-free
+                    depth  float32 (H, W)     beyond the range on both sides, NaN-free (c0 .. c3)
                     normal float32 (H, W, 3)  unit-ish vectors; some components exactly +1 / -1 / 0
                     color  float32 (H, W, 3)  0, 1, the rounding edges k/255 -+ 1e-7, values outside [0, 1], some NaN / inf
                     hit    uint8   (H, W)     with misses
@@ -16,6 +16,20 @@ instead (tests/test_ssim_host.py); this fixture covers the one step that restate
                                               method's image uses its reference capture's range); c2: an all-miss
                                               capture with (0, 1); c3: a range below the 1e-6 floor
                     img_depth uint8 (H, W), img_normal, img_color uint8 (H, W, 3): the reference's images
+                    c4 and later (appended, so the random stream leaves c0 .. c3 as they were) are the plain case with
+                    what a degenerate normal or a broken frame puts into a capture, all 16 x 12 but c4:
+                      c4  badnormal   40 x 33; NaN, +inf, -inf (one component or all three) and all-zero normals, on hits
+                                      and on misses
+                      c5  nan_late    depth NaN on the 6th hit (row-major), NaN / +-inf on misses
+                      c6  nan_first   depth NaN on the first hit, NaN / +-inf on misses
+                      c7  posinf      depth +inf on two hits, NaN / +-inf on misses
+                      c8  neginf      depth -inf on two hits, NaN / +-inf on misses
+                      c9  huge        depth +3.4e38 and -3.4e38 on hits (their difference overflows binary32)
+                      c10 onehit      exactly one hit
+                      c11 equaldepth  every hit at depth 4.25, the misses' depths random
+                    and carry two more arrays:
+                    own_drange    float64 (2,)  the reference's depth_range_of(capture): NaN on a hit gives (nan, nan)
+                    img_depth_own uint8 (H, W)  depth_to_image with that range, the image a REFERENCE capture gets
 
 Usage:  python tools/gen_ssim_golden.py <path of the reference checkout>
 """
@@ -73,6 +87,38 @@ def make_case(rng: np.random.Generator, W: int, H: int, kind: str) -> dict:
     return {"depth": depth, "normal": normal, "color": color, "hit": hit, "drange": drange}
 
 
+SPECIAL = ("badnormal", "nan_late", "nan_first", "posinf", "neginf", "huge", "onehit", "equaldepth")
+
+
+def make_special(rng: np.random.Generator, W: int, H: int, kind: str) -> dict:
+    """the plain case with one kind of trouble put in; drange stays the plain case's"""
+    f32 = np.float32
+    c = make_case(rng, W, H, "plain")
+    depth, normal, hit = c["depth"], c["normal"], c["hit"]
+    if kind == "onehit":
+        hit[:] = False
+        hit[H // 2, W // 3] = True
+    hits, misses = np.flatnonzero(hit), np.flatnonzero(~hit)
+    flat = depth.reshape(-1)
+    if kind == "badnormal":
+        bad = np.array([[np.nan, np.nan, np.nan], [np.nan, 0.5, -0.5], [0.0, np.inf, 0.0], [-np.inf, 0.0, 1.0],
+                        [np.inf, np.inf, -np.inf], [0.0, 0.0, 0.0], [-0.0, -0.0, -0.0], [1.0, np.nan, -1.0]], f32)
+        nf = normal.reshape(-1, 3)
+        for idx in (hits, misses):                                   # every kind on hits and on misses
+            where = rng.choice(idx, 3 * len(bad), replace=False)
+            nf[where] = np.tile(bad, (3, 1))
+    elif kind == "equaldepth":
+        flat[hits] = f32(4.25)
+    else:
+        special = {"nan_late": [(5, np.nan)], "nan_first": [(0, np.nan)], "posinf": [(2, np.inf), (-1, np.inf)],
+                   "neginf": [(0, -np.inf), (7, -np.inf)], "huge": [(1, 3.4e38), (4, -3.4e38), (-2, 3.4e38)], "onehit": []}[kind]
+        for i, v in special:                                         # i: which hit, row-major
+            flat[hits[i]] = f32(v)
+        m = rng.choice(misses, 6, replace=False)                     # on a miss they must not matter
+        flat[m] = np.array([np.nan, np.inf, -np.inf, np.nan, 3.4e38, -3.4e38], f32)
+    return c
+
+
 def main(argv) -> int:
     if len(argv) != 2:
         print(__doc__.strip().splitlines()[-1], file=sys.stderr)
@@ -81,17 +127,26 @@ def main(argv) -> int:
     rng = np.random.default_rng(20240607)
     out = {}
     cases = [(16, 12, "plain"), (40, 33, "plain"), (16, 12, "allmiss"), (16, 12, "flat")]
+    cases += [(40, 33, "badnormal")] + [(16, 12, kind) for kind in SPECIAL[1:]]
     for i, (W, H, kind) in enumerate(cases):
-        c = make_case(rng, W, H, kind)
-        assert np.isfinite(c["depth"]).all()
+        if kind in SPECIAL:
+            c = make_special(rng, W, H, kind)
+        else:
+            c = make_case(rng, W, H, kind)
+            assert np.isfinite(c["depth"]).all()
         p = f"c{i}_"
         out[p + "depth"], out[p + "normal"], out[p + "color"] = c["depth"], c["normal"], c["color"]
         out[p + "hit"] = c["hit"].astype(np.uint8)
         out[p + "drange"] = np.array(c["drange"], np.float64)
-        with np.errstate(invalid="ignore"):
+        with np.errstate(invalid="ignore", over="ignore"):
             out[p + "img_depth"] = io.depth_to_image(c["depth"], c["hit"], c["drange"])
             out[p + "img_normal"] = io.normal_to_image(c["normal"], c["hit"])
             out[p + "img_color"] = io.color_to_image(c["color"])
+            if kind in SPECIAL:
+                own = io.depth_range_of(c)
+                out[p + "own_drange"] = np.array(own, np.float64)
+                out[p + "img_depth_own"] = io.depth_to_image(c["depth"], c["hit"], own)
+                assert out[p + "img_depth_own"].dtype == np.uint8
         for k in ("img_depth", "img_normal", "img_color"):
             assert out[p + k].dtype == np.uint8
         print(f"case {i} {W}x{H} {kind}: hits {int(c['hit'].sum())}, depth image values {len(np.unique(out[p + 'img_depth']))}, "
