@@ -679,6 +679,50 @@ typedef struct RmCaptureMaps {
 int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference, const RmCaptureMaps* methods,
                    int32_t nmethods, double* out, RmTiming* timing);
 
+/* ---- capture on the device: hit normals and shading (csrc/rm_capture.h) ------------------------------------------
+ * A capture is a march result plus, per pixel, the tetrahedron normal of the scene at the hit point (four SDF
+ * evaluations at p + 0.0005 * k_i) and the shaded colour of the reference's fragment shader (fixed key light, hemisphere
+ * ambient, gamma 0.4545; its sky gradient on a miss) -- the maps GPURunner.capture returns.  One kernel computes them in
+ * binary64 in a fixed, unfused order from the very camera ray the march kernels shoot and rounds each result to float
+ * once: the same inputs give the same bits on every run and on a host build of rm_capture.h.
+ *
+ * The float maps of the rows [row0, row0 + rows) of a frame, row-major HOST arrays of rows x width elements (geom x4,
+ * normal and color x3, interleaved).  hit is required, any other map may be NULL (not computed, not copied):
+ *   geom    [hit, iters / max_iterations, t / max_distance, final_sdf] (the divisions in binary64, then rounded)
+ *   normal  unit normal on a hit ((0, 0, 0) where the four samples are equal), (0, 0, 0) on a miss
+ *   depth   t on a hit, 0 on a miss
+ *   color   shaded colour on a hit, background on a miss
+ *   evals   SDF evaluations of the march (RmOutputs.evals), as float
+ *   hit     0 / 1 */
+typedef struct RmCaptureOutputs {
+    float* geom;
+    float* normal;
+    float* depth;
+    float* color;
+    float* evals;
+    uint8_t* hit;        /* required */
+} RmCaptureOutputs;
+/* Renders `desc` as rm_render_outputs does, then runs the capture kernel on the same stream over the march's device
+ * outputs and copies back only the requested maps: one synchronisation, no fp64 map crosses the bus.  hit, depth, evals
+ * and geom are the casts of what rm_render_outputs returns for the same desc.  Catalogue scenes and scene programs alike.
+ * desc->march.full must be 1 (final_sdf is part of geom) and the slice must not be band-cyclic: RM_E_BAD_ARG.  `timing`
+ * (optional) times march + capture kernels without the copies; a timed call returns the same bits.  desc, out and timing
+ * are checked before the device is touched. */
+int rm_capture(const RmFrameDesc* desc, const RmCaptureOutputs* out, RmStats* stats, RmTiming* timing);
+
+/* The shading pass alone, for frames that already exist on the host (batched sweep frames, segment-tracer frames,
+ * anything with a depth and a hit map): `nframes` frames of width x height pixels, frame-major, frame f seen by the
+ * camera cams[14 * f .. 14 * f + 14) (RmFrameDesc.cam layout), in ONE launch and one pair of copies.  Exactly one of `t`
+ * (fp64 ray parameters) and `depth` (fp32, widened to double) is non-NULL; it is read where hit != 0 only.  Writes normal
+ * and color (nframes x height x width x 3 floats each, both required).  A frame gets the same bits alone or in a batch,
+ * and rm_shade_frames(t = t_raw) gives rm_capture's normal and color bit for bit.
+ * Checked before the device is touched: RM_E_BAD_ARG for a NULL cams / hit / normal / color, both or neither of t and
+ * depth, nframes outside [1, 65535], a hit pixel whose depth is not finite or a camera field that is not (a host scan:
+ * such a value must not reach the kernel); RM_E_BAD_DIMS for a non-positive side or more than 2^31 - 1 pixels in all;
+ * RM_E_BAD_SCENE for an unknown or destroyed scene id. */
+int rm_shade_frames(int scene_id, int32_t width, int32_t height, int32_t nframes, const double* cams, const double* t,
+                    const float* depth, const uint8_t* hit, float* normal, float* color, RmTiming* timing);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,7 @@ EXPORTS = [
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
     "rm_affine_supported", "rm_affine_range_eval", "rm_affine_march_rays", "rm_affine_render",
-    "rm_ssim_scores",
+    "rm_ssim_scores", "rm_capture", "rm_shade_frames",
 ]
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
@@ -171,6 +171,13 @@ class RmCaptureMaps(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("color", ctypes.c_void_p), ("hit", ctypes.c_void_p)]
 
 
+class RmCaptureOutputs(ctypes.Structure):
+    """The host maps rm_capture writes (include/rm_hip.h): float32 geom / normal / depth / color / evals, uint8 hit; any but
+    hit may be NULL."""
+    _fields_ = [("geom", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("color", ctypes.c_void_p),
+                ("evals", ctypes.c_void_p), ("hit", ctypes.c_void_p)]
+
+
 class RmDeviceInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 128), ("arch", ctypes.c_char * 64),
                 ("device_id", ctypes.c_int32), ("compute_units", ctypes.c_int32),
@@ -268,6 +275,10 @@ def load() -> ctypes.CDLL:
                                        ctypes.POINTER(RmTiming)]
         L.rm_ssim_scores.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(RmCaptureMaps), ctypes.POINTER(RmCaptureMaps),
                                      ctypes.c_int32, dp, ctypes.POINTER(RmTiming)]
+        L.rm_capture.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmCaptureOutputs), ctypes.POINTER(RmStats),
+                                 ctypes.POINTER(RmTiming)]
+        L.rm_shade_frames.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, dp, vp, vp, vp, vp, vp,
+                                      ctypes.POINTER(RmTiming)]
         for name in EXPORTS:
             if name not in ("rm_shutdown", "rm_last_error", "rm_stats_device_bytes", "rm_default_strategy_params"):
                 getattr(L, name).restype = ctypes.c_int
@@ -703,3 +714,55 @@ def ssim_scores(width: int, height: int, reference: dict, methods, warmup=0, rep
     check(L.rm_ssim_scores(int(width), int(height), ctypes.byref(ref), marr, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                            _ref(tm)))
     return (out, timing_dict(tm)) if tm is not None else out
+
+
+CAPTURE_MAPS = {"geom": (4,), "normal": (3,), "depth": (), "color": (3,), "evals": ()}
+
+
+def capture(desc: RmFrameDesc, want=("geom", "normal", "depth", "color", "evals"), warmup=0, repeats=0) -> dict:
+    """rm_capture into fresh NumPy arrays: the float32 maps named in `want` (CAPTURE_MAPS) of the rows of `desc`, hit (u8),
+    stats (dict) and timing (dict or None).  `desc` must have been made with full=True."""
+    L = init()
+    shape = (int(desc.rows), int(desc.width))
+    unknown = [k for k in want if k not in CAPTURE_MAPS]
+    if unknown:
+        raise ValueError(f"unknown capture maps {unknown}")
+    out = {k: np.empty(shape + CAPTURE_MAPS[k], np.float32) for k in CAPTURE_MAPS if k in want}
+    out["hit"] = np.empty(shape, np.uint8)
+    o = RmCaptureOutputs(*[out[k].ctypes.data if k in out else None for k in ("geom", "normal", "depth", "color", "evals", "hit")])
+    st = RmStats()
+    tm = _timing(warmup, repeats)
+    check(L.rm_capture(ctypes.byref(desc), ctypes.byref(o), ctypes.byref(st), _ref(tm)))
+    out["stats"] = stats_dict(st)
+    out["timing"] = timing_dict(tm) if tm is not None else None
+    return out
+
+
+def shade_frames(scene_id: int, cams, hit, t=None, depth=None, warmup=0, repeats=0) -> dict:
+    """rm_shade_frames: normal and color (n, H, W, 3) float32 of the n frames `hit` (n, H, W; non-zero = hit) seen by the
+    cameras `cams` (n, 14), from their fp64 ray parameters `t` or their fp32 `depth` (exactly one; (n, H, W)).  One frame
+    may come without the leading axis; the result then has none either.  With repeats > 0 also `timing`."""
+    L = init()
+    hit = np.asarray(hit)
+    single = hit.ndim == 2
+    hit = np.ascontiguousarray((hit[None] if single else hit) != 0, np.uint8)
+    if hit.ndim != 3:
+        raise ValueError(f"hit has shape {hit.shape}, not (n, H, W)")
+    n, H, W = hit.shape
+    cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 14)
+    if len(cams) != n:
+        raise ValueError(f"{len(cams)} cameras for {n} frames")
+    if (t is None) == (depth is None):
+        raise ValueError("exactly one of t and depth must be given")
+    src = np.ascontiguousarray(t, np.float64) if t is not None else np.ascontiguousarray(depth, np.float32)
+    if src.size != hit.size:
+        raise ValueError(f"{'t' if t is not None else 'depth'} has shape {src.shape}, hit {hit.shape}")
+    normal, color = np.empty((n, H, W, 3), np.float32), np.empty((n, H, W, 3), np.float32)
+    tm = _timing(warmup, repeats)
+    check(L.rm_shade_frames(int(scene_id), W, H, n, cams.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                            _ptr(src) if t is not None else None, _ptr(src) if t is None else None, _ptr(hit), _ptr(normal),
+                            _ptr(color), _ref(tm)))
+    out = {"normal": normal[0] if single else normal, "color": color[0] if single else color}
+    if tm is not None:
+        out["timing"] = timing_dict(tm)
+    return out

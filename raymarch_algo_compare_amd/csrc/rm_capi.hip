@@ -199,6 +199,7 @@ struct State : Session {
     WsBuf ccost, corder;   // single-launch pipeline: the centre-out tile order of the frame shape `corder_key`
     WsBuf ssim_depth, ssim_normal, ssim_color, ssim_hit;   // rm_ssim_scores: the methods' maps, then the reference's
     WsBuf ssim_ref, ssim_part, ssim_ssd, ssim_out;         // its reference images, partial sums and scores
+    WsBuf cap_out[5], cap_cams;   // rm_capture / rm_shade_frames: geom, normal, depth, color, evals maps; the frames' cameras
 } g;
 
 std::mutex g_mu;
@@ -381,10 +382,10 @@ private:
 };
 
 // The staging of a call that takes host arrays and returns host arrays: inputs and outputs are declared with the
-// workspace buffer that carries them (every `ensure` happens here, before anything is enqueued), begin() reports an
-// allocation failure or enqueues the uploads, download() enqueues the copies back in declaration order and finish()
-// waits for them.  A NULL host output is an optional one the caller did not ask for: nothing is allocated or copied
-// and its device pointer is NULL.  Everything runs on the library's stream.
+// workspace buffer that carries them (every `ensure` happens here, before anything is enqueued; scratch() sizes a
+// buffer that is not copied), begin() reports an allocation failure or enqueues the uploads, download() enqueues the
+// copies back in declaration order and finish() waits for them.  A NULL host output is an optional one the caller did
+// not ask for: nothing is allocated or copied and its device pointer is NULL.  Everything runs on the library's stream.
 class Staged {
 public:
     explicit Staged(const Entry&) {}
@@ -397,6 +398,13 @@ public:
     T* out(Buf& b, T* host, size_t bytes, size_t slack = 0)
     {
         return host ? (T*)add(b, host, bytes, slack, false) : nullptr;
+    }
+    // a buffer the call's kernels hand to each other: sized here like every other one, never copied
+    template <class T>
+    T* scratch(Buf& b, size_t bytes, size_t slack = 0)
+    {
+        if (rc_ || (rc_ = b.ensure(bytes + slack))) return nullptr;
+        return (T*)b.p;
     }
     int begin()
     {
@@ -2211,6 +2219,102 @@ int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference
     HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)nmethods * 32, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return RM_OK;
+}
+
+// ---- capture on the device: hit normals and shading (rm_capture.h, capture_kernel) ------------------------------------
+
+int rm_capture(const RmFrameDesc* d, const RmCaptureOutputs* o, RmStats* stats, RmTiming* timing)
+{
+    if (!d || !o) return fail(RM_E_BAD_ARG, "desc or out is NULL");
+    if (!o->hit) return fail(RM_E_BAD_ARG, "hit is required");
+    if (!d->march.full) return fail(RM_E_BAD_ARG, "rm_capture requires march.full = 1 (final_sdf is part of geom)");
+    if (d->band_rows > 0 && d->band_stride > 1) return fail(RM_E_BAD_ARG, "rm_capture takes no band-cyclic slice");
+    int rc = check_desc(d);
+    if (rc || (timing && (rc = check_timing(timing)))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const size_t n = (size_t)d->rows * (size_t)d->width;
+    // the march's outputs stay in the workspace; only the float maps the caller asked for (and hit) are staged back
+    Staged st(e);
+    float* d_depth = st.scratch<float>(g.depth, n * 4, 16);
+    int32_t* d_iters = st.scratch<int32_t>(g.iters, n * 4, 16);
+    double* d_traw = st.scratch<double>(g.traw, n * 8, 16);
+    double* d_fs = st.scratch<double>(g.fs, n * 8, 16);
+    int32_t* d_evals = st.scratch<int32_t>(g.evals, n * 4, 16);
+    uint8_t* d_hit = st.out(g.hit, o->hit, n, 16);
+    rm::CaptureArgs c;
+    memset(&c, 0, sizeof c);
+    c.geom = st.out(g.cap_out[0], o->geom, n * 16);
+    c.normal = st.out(g.cap_out[1], o->normal, n * 12);
+    c.depth = st.out(g.cap_out[2], o->depth, n * 4);
+    c.color = st.out(g.cap_out[3], o->color, n * 12);
+    c.evals_f = st.out(g.cap_out[4], o->evals, n * 4);
+    if ((rc = st.begin())) return rc;
+    const rm::LaunchPlan p = plan_for(d);
+    rm::KernelArgs a;
+    if ((rc = make_args(d, p, d_depth, d_iters, d_hit, d_traw, d_fs, nullptr, (unsigned long long*)g.stats.p, &a))) return rc;
+    a.evals = d_evals;
+    c.cam = a.single.cam;
+    c.width = d->width; c.height = d->height; c.row0 = d->row0; c.rows = d->rows;
+    c.max_iterations = d->march.max_iterations; c.max_distance = d->march.max_distance;
+    c.hit = d_hit; c.t = a.t_raw; c.iters = a.iters; c.final_sdf = a.final_sdf; c.evals = a.evals;
+    c.scene_data = a.scene_data;
+    const rm::SceneLaunchers* const sc = launchers(d->scene_id);
+    rc = once_or_timed(e, timing, g.stream, [&] {
+        if (int rc1 = launch(d, p, a, g.stream)) return rc1;
+        HIP_TRY(sc->capture(c, 1, g.stream));
+        return (int)RM_OK;
+    });
+    if (rc || (rc = st.download())) return rc;
+    return read_stats(e, g.stats.p, g.stream, stats);
+}
+
+int rm_shade_frames(int scene_id, int32_t width, int32_t height, int32_t nframes, const double* cams, const double* t,
+                    const float* depth, const uint8_t* hit, float* normal, float* color, RmTiming* timing)
+{
+    if (!cams || !hit || !normal || !color) return fail(RM_E_BAD_ARG, "cams, hit, normal or color is NULL");
+    if (!t == !depth) return fail(RM_E_BAD_ARG, "exactly one of t and depth must be given");
+    if (nframes < 1 || nframes > 65535) return fail(RM_E_BAD_ARG, "nframes %d outside [1, 65535]", nframes);
+    if (width <= 0 || height <= 0) return fail(RM_E_BAD_DIMS, "bad frame shape %dx%d", width, height);
+    if ((long long)width * height * nframes > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "frames too large");
+    int rc = check_scene(scene_id);
+    if (rc || (timing && (rc = check_timing(timing)))) return rc;
+    const size_t npix = (size_t)width * (size_t)height, n = npix * (size_t)nframes;
+    for (size_t i = 0; i < n; ++i) {      // the libm restatements are unclaimed for NaN arguments
+        if (!hit[i]) continue;
+        const double v = t ? t[i] : (double)depth[i];
+        if (!(v - v == 0.0))
+            return fail(RM_E_BAD_ARG, "frame %zu, pixel %zu: the depth of a hit is not finite", i / npix, i % npix);
+    }
+    for (size_t i = 0; i < (size_t)nframes * 14; ++i)
+        if (!(cams[i] - cams[i] == 0.0)) return fail(RM_E_BAD_ARG, "camera %zu: field %zu is not finite", i / 14, i % 14);
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const void* data = nullptr;
+    if ((rc = scene_data(scene_id, &data))) return rc;
+    Staged st(e);
+    rm::CaptureArgs c;
+    memset(&c, 0, sizeof c);
+    static_assert(sizeof(rm::CameraParams) == 14 * sizeof(double), "cams is an array of CameraParams");
+    c.cams = (const rm::CameraParams*)st.in(g.cap_cams, cams, (size_t)nframes * sizeof(rm::CameraParams));
+    if (t) c.t = st.in(g.in[0], t, n * 8);
+    else c.depth_in = st.in(g.in[0], depth, n * 4);
+    c.hit = st.in(g.in[1], hit, n);
+    c.normal = st.out(g.cap_out[1], normal, n * 12);
+    c.color = st.out(g.cap_out[3], color, n * 12);
+    if ((rc = st.begin())) return rc;
+    c.width = width; c.height = height; c.row0 = 0; c.rows = height;
+    c.max_iterations = 1; c.max_distance = 1.0;
+    c.scene_data = data;
+    const rm::SceneLaunchers* const sc = launchers(scene_id);
+    rc = once_or_timed(e, timing, g.stream, [&] {
+        HIP_TRY(sc->capture(c, nframes, g.stream));
+        return (int)RM_OK;
+    });
+    if (rc) return rc;
+    return st.finish();
 }
 
 }  // extern "C"

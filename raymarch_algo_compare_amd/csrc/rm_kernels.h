@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "rm_camera.h"
+#include "rm_capture.h"
 #include "rm_scenes.h"
 #include "rm_shape.h"
 #include "rm_strategies.h"
@@ -1170,6 +1171,63 @@ __global__ __launch_bounds__(64 * kTeam) void resume_team_kernel(const KernelArg
     if (a.keep_busy > 0 && threadIdx.x == 0) __hip_atomic_fetch_add(&a.stats[12 + level], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- capture: hit normals and shading of marched frames (rm_capture.h) -----------------------------------------------------
+//
+// A second kernel on the stream of the march, never fused into the march kernels: one pixel per lane over the rows
+// [row0, row0 + rows) of `nframes` frames of one shape (grid y = frame; rm_capture: one frame, its camera in the
+// arguments; rm_shade_frames: a device array of cameras).  Reads what the march left on the device (hit, fp64 t or
+// fp32 depth; for rm_capture also iters, final_sdf, evals) and writes the float maps with plain vector stores; an output
+// pointer that is NULL is skipped.  All arrays are frame-major, rows x width elements per frame.
+struct CaptureArgs {
+    CameraParams cam;             // the camera of a one-frame launch
+    const CameraParams* cams;     // device array [gridDim.y], or nullptr: `cam`
+    int32_t width, height, row0, rows;
+    int32_t max_iterations;       // geom only
+    double max_distance;          // geom only
+    const uint8_t* hit;
+    const double* t;              // the parameter of every ray (fp64), or nullptr:
+    const float* depth_in;        // fp32 depth, widened
+    const int32_t* iters;         // geom only
+    const double* final_sdf;      // geom only
+    const int32_t* evals;         // evals_f only
+    float* geom;                  // x4
+    float* normal;                // x3
+    float* depth;
+    float* color;                 // x3
+    float* evals_f;
+    const void* scene_data;       // KernelArgs.scene_data
+};
+
+// camera_ray's length() and the gamma need the pow tables whatever the scene's own SDF reads
+template <class Scene> struct CaptureTables {};
+template <class Scene> struct SceneTables<CaptureTables<Scene>> { static constexpr unsigned value = SceneTables<Scene>::value | TB_POW; };
+
+template <class Scene>
+__global__ __launch_bounds__(256) void capture_kernel(CaptureArgs a)
+{
+    rm_load_scene_data<Scene>(a.scene_data);
+    rm_load_tables<CaptureTables<Scene>>();      // all 256 threads, ends with the barrier: no pixel test before this line
+    const size_t n = (size_t)a.rows * (size_t)a.width;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t gi = (size_t)blockIdx.y * n + i;
+    const int row = (int)(i / (size_t)a.width), px = (int)(i - (size_t)row * (size_t)a.width);
+    const bool hit = a.hit[gi] != 0;
+    double t = 0.0;
+    if (hit || a.geom) t = a.t ? a.t[gi] : (double)a.depth_in[gi];
+    if (a.normal || a.color) {
+        float nrm[3], col[3];
+        capture_shade<Scene>(a.cams ? a.cams[blockIdx.y] : a.cam, a.width, a.height, px, a.row0 + row, hit, t, nrm, col);
+        if (a.normal) { a.normal[3 * gi] = nrm[0]; a.normal[3 * gi + 1] = nrm[1]; a.normal[3 * gi + 2] = nrm[2]; }
+        if (a.color) { a.color[3 * gi] = col[0]; a.color[3 * gi + 1] = col[1]; a.color[3 * gi + 2] = col[2]; }
+    }
+    float geom[4];
+    capture_geom(hit, t, a.iters ? a.iters[gi] : 0, a.final_sdf ? a.final_sdf[gi] : 0.0, a.evals ? a.evals[gi] : 0,
+                 a.max_iterations, a.max_distance, a.geom ? geom : nullptr, a.depth ? &a.depth[gi] : nullptr,
+                 a.evals_f ? &a.evals_f[gi] : nullptr);
+    if (a.geom) *reinterpret_cast<float4*>(a.geom + 4 * gi) = make_float4(geom[0], geom[1], geom[2], geom[3]);
+}
+
 // Per-scene launch table, filled by rm_scene_tu.hip (one translation unit per scene).
 struct SceneLaunchers {
     hipError_t (*render)(int strategy, const KernelArgs& a, int grid, hipStream_t s);                    // 64x4 tiles
@@ -1187,6 +1245,8 @@ struct SceneLaunchers {
     // nullptr: no team form.  busy: a zeroed device word -> `fillers` more workgroups keep the chip busy until the teams are through
     hipError_t (*march_rays_team)(int strategy, const MarchCfg& cfg, const double* o, const double* d, size_t n,
                                   uint8_t* hit, double* t, int32_t* iters, double* fs, unsigned long long* busy, int fillers, hipStream_t s);
+    // capture_kernel over `nframes` frames (1..65535) of a.rows x a.width pixels each
+    hipError_t (*capture)(const CaptureArgs& a, int nframes, hipStream_t s);
 };
 
 }  // namespace rm

@@ -1,6 +1,6 @@
 // rm_scene_tu.hip -- one translation unit per scene (compile with -DRM_SCENE_ID=<0..19>).
-// Instantiates render / march_rays kernels for every strategy and the sdf_eval kernel
-// of that scene, and exports their launchers through rm::scene_launchers_<id>().
+// Instantiates render / march_rays kernels for every strategy and the sdf_eval and capture
+// kernels of that scene, and exports their launchers through rm::scene_launchers_<id>().
 // With -DRM_SCENE_PROGRAM instead: the same kernels for the scene-program interpreter (rm_scene_program.h), exported
 // through rm::scene_launchers_program(); no single-launch pipeline and no team forms.  With -DRM_SCENE_PROGRAM_EXT as
 // well: the interpreter with the four ops beyond primitives.py (SceneExtProgram), exported through rm::scene_launchers_program_ext().
@@ -186,6 +186,15 @@ static hipError_t march_rays_team(int strategy, const MarchCfg& cfg, const doubl
     });
 }
 
+static hipError_t capture(const CaptureArgs& a, int nframes, hipStream_t s)
+{
+    const size_t n = (size_t)a.rows * (size_t)a.width;
+    if (n == 0) return hipSuccess;
+    if (nframes < 1 || nframes > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(capture_kernel<SceneT>, dim3((unsigned)((n + 255) / 256), (unsigned)nframes), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 #if defined(RM_SCENE_PROGRAM)
 static_assert(!kIter, "a scene program has no resumable evaluation");
 #if defined(RM_SCENE_PROGRAM_EXT)
@@ -202,7 +211,7 @@ static_assert(!kIter, "a scene program has no resumable evaluation");
 const SceneLaunchers* RM_LAUNCHERS_FN()
 {
     static const SceneLaunchers l = { render, resume, kIter ? resume_team : nullptr, RM_PIPELINE_FNS, kIter,
-                                      entry_bytes, occupancy, sdf_eval, march_rays, kIter ? march_rays_team : nullptr };
+                                      entry_bytes, occupancy, sdf_eval, march_rays, kIter ? march_rays_team : nullptr, capture };
     return &l;
 }
 

@@ -147,7 +147,7 @@ class GPURunner:
                 raise KeyError(f"unknown shader parameter {k!r}")
         return out
 
-    def _frame(self, scene_id, strategy, render_cfg, march_cfg, lipschitz, timed, want_evals, params=None):
+    def _frame(self, scene_id, strategy, render_cfg, march_cfg, lipschitz, timed, want_evals, params=None, device_capture=False):
         if get_scene_by_id(scene_id) is None:
             raise ValueError(f"scene id {scene_id} is neither a catalogue scene nor a registered scene")
         cam = Camera(render_cfg.camera_position, render_cfg.camera_target, render_cfg.camera_up,
@@ -161,6 +161,8 @@ class GPURunner:
         desc = _native.make_desc(int(scene_id), strategy.id, cam.params14(), cam.width, cam.height, 0, None,
                                  march_cfg.max_iterations, march_cfg.hit_threshold, march_cfg.max_distance, lip, True,
                                  params=prm)
+        if device_capture:
+            return cam, _native.capture(desc)
         out = _native.render(desc, want_t_raw=True, want_final_sdf=True, repeats=1 if timed else 0, want_evals=want_evals)
         return cam, out
 
@@ -181,11 +183,22 @@ class GPURunner:
         return self._geom(out, march_cfg), out["timing"]["ms_median"] * 1e-3
 
     def capture(self, scene_id: int, strategy_id: int, render_cfg: RenderConfig, march_cfg: MarchConfig,
-                lipschitz: float = 1.0, params: dict | None = None, *, strategy_key: str | None = None) -> dict:
+                lipschitz: float = 1.0, params: dict | None = None, *, strategy_key: str | None = None,
+                device: bool = False) -> dict:
         """-> geom (H,W,4), normal (H,W,3), depth (H,W), color (H,W,3), evals (H,W), hit (H,W) bool -- the capture
         targets of main.glsl:79-110: tetrahedron normals from four SDF evaluations (rm_sdf_eval) at the hit point,
         the shader's fixed key light + hemisphere ambient + gamma, its background on misses, and the number of SDF
-        evaluations the march itself performed."""
+        evaluations the march itself performed.
+
+        device=True: the same dict from rm_capture -- normals and shading by the capture kernel, at the hit point of
+        the very ray the march shot, in a fixed order of operations (csrc/rm_capture.h); only float maps come back.
+        hit, depth, evals and geom are the same bits either way; normal and color agree to a float ulp (the host path
+        below takes its ray from ray_directions and its dot product and gamma from NumPy)."""
+        if device:
+            _, out = self._frame(scene_id, self._strategy(strategy_id, strategy_key), render_cfg, march_cfg, lipschitz, False,
+                                 True, params, device_capture=True)
+            return {"geom": out["geom"], "normal": out["normal"], "depth": out["depth"], "color": out["color"],
+                    "evals": out["evals"], "hit": out["hit"] > 0}
         cam, out = self._frame(scene_id, self._strategy(strategy_id, strategy_key), render_cfg, march_cfg, lipschitz, False, True, params)
         h, w = out["iters"].shape
         hit = out["hit"] > 0

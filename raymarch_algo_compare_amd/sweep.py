@@ -173,9 +173,21 @@ def oracle_columns(frame: Dict, oracle: Optional[Dict]) -> Dict:
             "oracle_depth_mae": d["mae"], "oracle_depth_rmse": d["rmse"], "oracle_depth_p95": d["p95"]}
 
 
-def ssim_columns(scene, kept: List, oracle_frames: Dict[str, Optional[Dict]]) -> None:
+def device_normal_maps(scene, items: List) -> List[np.ndarray]:
+    """The (H, W, 3) float32 normal maps of the kept rows `items` of one viewpoint, all from ONE rm_shade_frames call (the
+    capture kernel, csrc/rm_capture.h: the hit point on the very ray the frame marched, from the frame's fp32 depth)."""
+    from . import _native
+    cams = np.stack([cam.params14() for _, _, cam, _, _ in items])
+    hit = np.stack([np.asarray(h, dtype=bool) for _, _, _, h, _ in items])
+    depth = np.stack([np.asarray(d, dtype=np.float32) for _, _, _, _, d in items])
+    return list(_native.shade_frames(scene.id, cams, hit, depth=depth)["normal"])
+
+
+def ssim_columns(scene, kept: List, oracle_frames: Dict[str, Optional[Dict]], device_normals: bool = False) -> None:
     """Adds the SSIM_FIELDS columns to the kept rows of one scene (sweep_cell's `keep`): all rows of a viewpoint -- every
-    strategy, parameter combo and level -- against that viewpoint's oracle capture in ONE rm_ssim_scores call."""
+    strategy, parameter combo and level -- against that viewpoint's oracle capture in ONE rm_ssim_scores call.
+    `device_normals`: the rows' normals come from one rm_shade_frames call per viewpoint (device_normal_maps) instead of one
+    hit_normals round trip per row."""
     from . import ssim
     from .runner import hit_normals, ray_directions
     by_vp: Dict[str, List] = {}
@@ -186,6 +198,12 @@ def ssim_columns(scene, kept: List, oracle_frames: Dict[str, Optional[Dict]]) ->
         if truth is None:
             for row, *_ in items:
                 row.update(dict.fromkeys(SSIM_FIELDS))
+            continue
+        if device_normals:
+            methods = [{"hit": np.asarray(hit, dtype=bool), "depth": depth, "normal": normal}
+                       for (_, _, _, hit, depth), normal in zip(items, device_normal_maps(scene, items))]
+            for (row, *_), cols in zip(items, ssim.ssim_scores_batch(methods, truth)):
+                row.update(cols)
             continue
         rd = ray_directions(items[0][2])
         methods = []
@@ -258,7 +276,7 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
               out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False,
               oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL,
               ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL, ssim: bool = False,
-              oracle_twins: bool = False) -> List[Dict]:
+              oracle_twins: bool = False, device_capture: bool = False) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
@@ -271,13 +289,16 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     twin, the same point function bit for bit, stays registered.  Off, those scenes keep their empty cells.  A twin's
     ceiling frame is traced with the tracer's clamp on K (RmSegmentConfig.l_global) raised to the scene's Lipschitz bound
     (2 for Bad Lipschitz Sphere), a scene with its own interval form with the default clamp of 1: where the bound is above
-    1 the two kinds of ceiling row come from different tracer configs."""
+    1 the two kinds of ceiling row come from different tracer configs.  device_capture=True (with ssim): the frames' normals
+    come from the capture kernel, one rm_shade_frames call per viewpoint (ssim_columns); off, the output is unchanged."""
     if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
         raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
     if ceiling is not None and ceiling not in CEILINGS:
         raise ValueError(f"unknown ceiling {ceiling!r}: one of {CEILINGS}")
     if ssim and oracle is None:
         raise ValueError("ssim needs an oracle to score against: pass oracle=")
+    if device_capture and not ssim:
+        raise ValueError("device_capture computes the normals of the ssim columns: pass ssim=True")
     scenes = registry.get_all_scenes() if not scene_names else [_need(registry.get_scene_by_name(n), "scene", n) for n in scene_names]
     strats = ([registry.get_strategy_by_name(k) for k in registry.list_strategies()] if not strategy_names
               else [_need(registry.get_shader_strategy(n) or registry.get_strategy_by_name(n), "strategy", n) for n in strategy_names])
@@ -299,7 +320,7 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
                 print(f"{scene.name:24s} {strat.short_name:24s} {len(cell):3d} frames  "
                       f"{sum(r['ms_per_frame'] for r in cell):8.2f} ms", file=sys.stderr)
         if kept:
-            ssim_columns(scene, kept, ofr)
+            ssim_columns(scene, kept, ofr, device_normals=device_capture)
     if out_path:
         write_rows(rows, out_path)
     return rows
@@ -345,6 +366,9 @@ def main(argv=None) -> int:
     ap.add_argument("--ceiling-tol", type=float, default=faithful_segment.DEFAULT_TOL, help="the ceiling tracer's hit tolerance")
     ap.add_argument("--ssim", action="store_true",
                     help="with --oracle: add the SSIM columns of every frame against the oracle capture (depth_ssim, normal_ssim, ...)")
+    ap.add_argument("--device-capture", action="store_true",
+                    help="with --ssim: the frames' normals from the capture kernel, one rm_shade_frames call per viewpoint, instead "
+                         "of one host round trip per row")
     ap.add_argument("--oracle-twins", action="store_true",
                     help="with --oracle / --ceiling: score a catalogue scene that has no interval form against its program twin "
                          "(Menger, Bad Lipschitz Sphere, Bumpy Sphere, Gyroid, Box Lattice); a twin's ceiling is traced with l_global = the "
@@ -352,12 +376,15 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.ssim and a.oracle is None:
         ap.error("--ssim needs --oracle")
+    if a.device_capture and not a.ssim:
+        ap.error("--device-capture needs --ssim")
     if a.oracle_twins and a.oracle is None and a.ceiling is None:
         ap.error("--oracle-twins needs --oracle or --ceiling")
     rows = run_sweep([s for s in a.scenes.split(",") if s], [s for s in a.strategies.split(",") if s], a.mode, a.width, a.height,
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
                      a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol,
-                     ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim, oracle_twins=a.oracle_twins)
+                     ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim, oracle_twins=a.oracle_twins,
+                     device_capture=a.device_capture)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 
