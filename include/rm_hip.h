@@ -679,6 +679,48 @@ typedef struct RmCaptureMaps {
 int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference, const RmCaptureMaps* methods,
                    int32_t nmethods, double* out, RmTiming* timing);
 
+/* ---- hit-mask, depth and normal scoring of captures (csrc/rm_score.h) ---------------------------------------------
+ * The primary and secondary tiers of the reference's metrics/scoring.py and its calibration residual
+ * (gpu/oracle_calibration.py), for `nmethods` captures against one reference in one call; csrc/rm_score.h states every
+ * definition in full.
+ *
+ * The maps of one width x height capture, row-major HOST arrays: depth (W*H), normal (W*H*3, interleaved), hit (W*H
+ * bytes, non-zero = hit).  depth and normal hold doubles when fp64 != 0, floats otherwise (widened on read, which is
+ * exact).  depth and hit are required; normal may be NULL in the reference and in every method alike (the two normal
+ * outputs are then NaN), NULL on one side only is RM_E_BAD_ARG. */
+typedef struct RmScoreMaps {
+    const void* depth;
+    const void* normal;
+    const uint8_t* hit;
+    int32_t fp64;
+} RmScoreMaps;
+/* One method's result.  With m the method's hit mask and r the reference's:
+ *   n_method_hit |m|, n_reference_hit |r|, n_co_hit |m & r|, n_union |m | r|; n_co_hit_core and n_union_core count the
+ *   same pixels outside the reference's silhouette band (the pixels within L1 distance band_k of a pixel whose hit flag
+ *   differs from an in-image 4-neighbour's: scoring.silhouette_band); n_nan_depth / n_nan_angle count the co-hit pixels
+ *   whose depth gap / normal angle is NaN.  Rates (IoU, false hit, false miss) are left to the caller: integer divisions
+ *   of these counts.
+ *   Over the co-hit pixels, gap = depth - reference depth: depth_mae = mean |gap|, depth_rmse = sqrt(mean gap^2),
+ *   depth_signed = mean gap, depth_p95 and depth_med = np.percentile(|gap|, 95) and np.median(|gap|), exact order
+ *   statistics under NumPy's interpolation rules; normal_mean_deg and normal_p95_deg likewise of the angle between the
+ *   normals in degrees (cosine clamped to [-1, 1], a NaN kept).  All NaN when n_co_hit = 0; a NaN in a sample makes its
+ *   percentile and median NaN. */
+typedef struct RmScoreResult {
+    int64_t n_method_hit, n_reference_hit, n_co_hit, n_union, n_co_hit_core, n_union_core, n_nan_depth, n_nan_angle;
+    double depth_mae, depth_rmse, depth_signed, depth_p95, depth_med, normal_mean_deg, normal_p95_deg;
+} RmScoreResult;
+/* Scores methods[0 .. nmethods) against `reference`; out: nmethods results.  band_k in [0, 8] is the half width of the
+ * silhouette band, made once from the reference; a negative band_k means no band (the core counts equal the full
+ * counts).  There is no minimum side: 1 x 1 is valid.  Counts are integer sums, every floating-point sum has a fixed
+ * order (32 x 8 tiles folded by halves, added in tile order) and the order statistics are exact selections, so the same
+ * inputs give the same bits on every run, a method scores the same alone or in a batch, and a host build of
+ * csrc/rm_score.h reproduces the result bit for bit.  `timing` (optional) times the kernels without the copies; a timed
+ * call returns the same bits.  Checked before the device is touched: RM_E_BAD_ARG for a NULL argument, a NULL depth or
+ * hit map, a one-sided NULL normal, nmethods outside [1, 65535] or band_k above 8; RM_E_BAD_DIMS for a non-positive side
+ * or more than 2^31 - 1 pixels. */
+int rm_score_captures(int32_t width, int32_t height, int32_t band_k, const RmScoreMaps* reference, const RmScoreMaps* methods,
+                      int32_t nmethods, RmScoreResult* out, RmTiming* timing);
+
 /* ---- capture on the device: hit normals and shading (csrc/rm_capture.h) ------------------------------------------
  * A capture is a march result plus, per pixel, the tetrahedron normal of the scene at the hit point (four SDF
  * evaluations at p + 0.0005 * k_i) and the shaded colour of the reference's fragment shader (fixed key light, hemisphere

@@ -36,7 +36,7 @@ EXPORTS = [
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
     "rm_affine_supported", "rm_affine_range_eval", "rm_affine_march_rays", "rm_affine_render",
-    "rm_ssim_scores", "rm_capture", "rm_shade_frames",
+    "rm_ssim_scores", "rm_capture", "rm_shade_frames", "rm_score_captures",
 ]
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
@@ -171,6 +171,20 @@ class RmCaptureMaps(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("color", ctypes.c_void_p), ("hit", ctypes.c_void_p)]
 
 
+class RmScoreMaps(ctypes.Structure):
+    """The host maps of one capture as rm_score_captures reads them (include/rm_hip.h): depth and normal hold float64 when
+    fp64 != 0, float32 otherwise; uint8 hit; normal may be NULL."""
+    _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("hit", ctypes.c_void_p), ("fp64", ctypes.c_int32)]
+
+
+class RmScoreResult(ctypes.Structure):
+    """One method's counts, depth error and normal angle against the reference (include/rm_hip.h)."""
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_method_hit", "n_reference_hit", "n_co_hit", "n_union", "n_co_hit_core",
+                                              "n_union_core", "n_nan_depth", "n_nan_angle")] + \
+               [(k, ctypes.c_double) for k in ("depth_mae", "depth_rmse", "depth_signed", "depth_p95", "depth_med",
+                                               "normal_mean_deg", "normal_p95_deg")]
+
+
 class RmCaptureOutputs(ctypes.Structure):
     """The host maps rm_capture writes (include/rm_hip.h): float32 geom / normal / depth / color / evals, uint8 hit; any but
     hit may be NULL."""
@@ -275,6 +289,8 @@ def load() -> ctypes.CDLL:
                                        ctypes.POINTER(RmTiming)]
         L.rm_ssim_scores.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(RmCaptureMaps), ctypes.POINTER(RmCaptureMaps),
                                      ctypes.c_int32, dp, ctypes.POINTER(RmTiming)]
+        L.rm_score_captures.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(RmScoreMaps),
+                                        ctypes.POINTER(RmScoreMaps), ctypes.c_int32, ctypes.POINTER(RmScoreResult), ctypes.POINTER(RmTiming)]
         L.rm_capture.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmCaptureOutputs), ctypes.POINTER(RmStats),
                                  ctypes.POINTER(RmTiming)]
         L.rm_shade_frames.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, dp, vp, vp, vp, vp, vp,
@@ -713,6 +729,42 @@ def ssim_scores(width: int, height: int, reference: dict, methods, warmup=0, rep
     tm = _timing(warmup, repeats)
     check(L.rm_ssim_scores(int(width), int(height), ctypes.byref(ref), marr, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                            _ref(tm)))
+    return (out, timing_dict(tm)) if tm is not None else out
+
+
+def score_maps(capture: dict, width: int, height: int):
+    """(RmScoreMaps, the arrays it points into) of a capture dict.  depth and normal stay float32 when both are (the
+    flag fp64 = 0) and are float64 otherwise; a uint8 hit map is passed as it is (non-zero = hit), any other as `!= 0`; a
+    missing or None normal is NULL."""
+    shape = (int(height), int(width))
+    depth, normal, hit = np.asarray(capture["depth"]), capture.get("normal"), np.asarray(capture["hit"])
+    normal = None if normal is None else np.asarray(normal)
+    single = depth.dtype == np.float32 and (normal is None or normal.dtype == np.float32)
+    dtype = np.float32 if single else np.float64
+    keep = [np.ascontiguousarray(depth, dtype), None if normal is None else np.ascontiguousarray(normal, dtype),
+            np.ascontiguousarray(hit if hit.dtype == np.uint8 else hit != 0, np.uint8)]
+    for a, key, tail in zip(keep, ("depth", "normal", "hit"), ((), (3,), ())):
+        if a is not None and a.shape != shape + tail:
+            raise ValueError(f"{key} has shape {a.shape}, not {shape + tail}")
+    return RmScoreMaps(keep[0].ctypes.data, None if normal is None else keep[1].ctypes.data, keep[2].ctypes.data, int(not single)), keep
+
+
+def score_captures(width: int, height: int, reference: dict, methods, band_k=2, warmup=0, repeats=0):
+    """rm_score_captures: one dict of RmScoreResult's fields (int counts, float statistics) per capture dict of `methods`
+    against `reference`; band_k < 0: no silhouette band.  With repeats > 0 also the kernels' timing dict."""
+    L = init()
+    n = len(methods)
+    keep = []
+    ref, k = score_maps(reference, width, height)
+    keep.append(k)
+    marr = (RmScoreMaps * max(n, 1))()
+    for i, c in enumerate(methods):
+        marr[i], k = score_maps(c, width, height)
+        keep.append(k)
+    res = (RmScoreResult * max(n, 1))()
+    tm = _timing(warmup, repeats)
+    check(L.rm_score_captures(int(width), int(height), int(band_k), ctypes.byref(ref), marr, n, res, _ref(tm)))
+    out = [{name: getattr(res[i], name) for name, _ in RmScoreResult._fields_} for i in range(n)]
     return (out, timing_dict(tm)) if tm is not None else out
 
 

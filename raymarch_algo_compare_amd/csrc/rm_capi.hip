@@ -29,6 +29,7 @@
 #include "rm_interval_catalogue.h"
 #include "rm_segment.h"
 #include "rm_affine.h"
+#include "rm_score.h"
 #include "rm_ssim.h"
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
@@ -75,6 +76,8 @@ hipError_t launch_affine_render(const void* prog, int mode, const IntervalParams
                                 int row0, int rows, double* depth, uint8_t* hit, int32_t* steps, hipStream_t s);
 // rm_ssim.hip
 hipError_t launch_ssim(const SsimLaunch& a, hipStream_t s);
+// rm_score.hip
+hipError_t launch_score(const ScoreLaunch& a, hipStream_t s);
 
 static const SceneLaunchers* scene(int id)
 {
@@ -199,6 +202,8 @@ struct State : Session {
     WsBuf ccost, corder;   // single-launch pipeline: the centre-out tile order of the frame shape `corder_key`
     WsBuf ssim_depth, ssim_normal, ssim_color, ssim_hit;   // rm_ssim_scores: the methods' maps, then the reference's
     WsBuf ssim_ref, ssim_part, ssim_ssd, ssim_out;         // its reference images, partial sums and scores
+    WsBuf score_depth, score_normal, score_hit, score_caps;   // rm_score_captures: the methods' maps, then the reference's
+    WsBuf score_band, score_keys, score_small, score_part;    // its band, sample keys, counts / selections / results, partial sums
     WsBuf cap_out[5], cap_cams;   // rm_capture / rm_shade_frames: geom, normal, depth, color, evals maps; the frames' cameras
 } g;
 
@@ -2217,6 +2222,86 @@ int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference
     });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)nmethods * 32, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RM_OK;
+}
+
+// ---- hit-mask, depth and normal scoring of captures (rm_score.h, rm_score.hip) --------------------------------------
+
+static_assert(sizeof(RmScoreResult) == sizeof(rm::ScoreResult) && offsetof(RmScoreResult, depth_mae) == offsetof(rm::ScoreResult, depth_mae) &&
+              offsetof(RmScoreResult, normal_p95_deg) == offsetof(rm::ScoreResult, normal_p95_deg), "rm::ScoreResult is RmScoreResult");
+
+namespace {
+
+int score_check_maps(const RmScoreMaps& c, const RmScoreMaps& ref, const char* who, int index)
+{
+    if (!c.depth || !c.hit) return fail(RM_E_BAD_ARG, "%s %d: depth and hit are required", who, index);
+    if (!c.normal != !ref.normal) return fail(RM_E_BAD_ARG, "%s %d: normal is NULL on one side only", who, index);
+    return RM_OK;
+}
+
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+}  // namespace
+
+int rm_score_captures(int32_t width, int32_t height, int32_t band_k, const RmScoreMaps* reference, const RmScoreMaps* methods,
+                      int32_t nmethods, RmScoreResult* out, RmTiming* timing)
+{
+    if (!reference || !methods || !out) return fail(RM_E_BAD_ARG, "reference, methods or out is NULL");
+    if (nmethods <= 0 || nmethods > rm::kScoreMaxMethods)
+        return fail(RM_E_BAD_ARG, "nmethods %d outside [1, %d]", nmethods, rm::kScoreMaxMethods);
+    if (band_k > rm::kScoreMaxBand) return fail(RM_E_BAD_ARG, "band_k %d above %d", band_k, rm::kScoreMaxBand);
+    if (width <= 0 || height <= 0) return fail(RM_E_BAD_DIMS, "a %dx%d image has no pixel", width, height);
+    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
+    int rc = score_check_maps(*reference, *reference, "reference", 0);
+    for (int m = 0; !rc && m < nmethods; ++m) rc = score_check_maps(methods[m], *reference, "method", m);
+    if (rc || (timing && (rc = check_timing(timing)))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const size_t npix = (size_t)width * (size_t)height, nm = (size_t)nmethods, caps = nm + 1;   // the reference is capture `nmethods`
+    const size_t ntiles = (size_t)rm::score_tiles_x(width) * (size_t)rm::score_tiles_y(height);
+    const bool has_normal = reference->normal != nullptr;
+    // one small buffer: counts, selections, histograms, least keys above, results
+    const size_t o_counts = 0, o_sel = align256(o_counts + nm * rm::kScoreCounts * 8);
+    const size_t o_hist = align256(o_sel + nm * rm::kScoreSelects * sizeof(rm::ScoreSelect));
+    const size_t o_above = align256(o_hist + nm * rm::kScoreSelects * 256 * 4);
+    const size_t o_out = align256(o_above + nm * rm::kScoreSelects * 8), small = o_out + nm * sizeof(rm::ScoreResult);
+    // every capture has a slot of W*H doubles (and 3 W*H for the normals), whichever type it holds
+    if ((rc = g.score_depth.ensure(caps * npix * 8)) || (rc = g.score_hit.ensure(caps * npix)) ||
+        (has_normal && (rc = g.score_normal.ensure(caps * npix * 24))) || (rc = g.score_caps.ensure(caps * sizeof(rm::ScoreMaps))) ||
+        (band_k >= 0 && (rc = g.score_band.ensure(npix))) || (rc = g.score_keys.ensure(nm * (has_normal ? 2 : 1) * npix * 8)) ||
+        (rc = g.score_small.ensure(small)) || (rc = g.score_part.ensure(nm * rm::kScoreSums * ntiles * 8)))
+        return rc;
+    std::vector<rm::ScoreMaps> table(caps);
+    for (size_t m = 0; m < caps; ++m) {
+        const RmScoreMaps& c = m < nm ? methods[m] : *reference;
+        const size_t elem = c.fp64 ? 8 : 4;
+        rm::ScoreMaps& d = table[m];
+        d.depth = (char*)g.score_depth.p + m * npix * 8;
+        d.normal = has_normal ? (char*)g.score_normal.p + m * npix * 24 : nullptr;
+        d.hit = (uint8_t*)g.score_hit.p + m * npix;
+        d.fp64 = c.fp64 != 0;
+        HIP_TRY(hipMemcpyAsync((void*)d.depth, c.depth, npix * elem, hipMemcpyHostToDevice, g.stream));
+        HIP_TRY(hipMemcpyAsync((void*)d.hit, c.hit, npix, hipMemcpyHostToDevice, g.stream));
+        if (has_normal) HIP_TRY(hipMemcpyAsync((void*)d.normal, c.normal, npix * 3 * elem, hipMemcpyHostToDevice, g.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(g.score_caps.p, table.data(), caps * sizeof(rm::ScoreMaps), hipMemcpyHostToDevice, g.stream));
+    rm::ScoreLaunch a;
+    a.width = width; a.height = height; a.nmethods = nmethods; a.has_normal = has_normal; a.band_k = band_k < 0 ? -1 : band_k;
+    a.caps = (const rm::ScoreMaps*)g.score_caps.p;
+    a.band = (uint8_t*)g.score_band.p;
+    a.keys = (uint64_t*)g.score_keys.p;
+    char* sm = (char*)g.score_small.p;
+    a.counts = (unsigned long long*)(sm + o_counts); a.sel = (rm::ScoreSelect*)(sm + o_sel); a.hist = (uint32_t*)(sm + o_hist);
+    a.above = (unsigned long long*)(sm + o_above); a.out = (rm::ScoreResult*)(sm + o_out);
+    a.part = (double*)g.score_part.p;
+    rc = once_or_timed(e, timing, g.stream, [&] {
+        HIP_TRY(rm::launch_score(a, g.stream));
+        return (int)RM_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, a.out, nm * sizeof(rm::ScoreResult), hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return RM_OK;
 }

@@ -113,12 +113,14 @@ def finest_index(mode: str, levels) -> int:
 
 def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, width: int, height: int, grid: bool = False,
                oracle_frames: Optional[Dict[str, Optional[Dict]]] = None,
-               ceiling_cols: Optional[Dict[str, Dict]] = None, keep: Optional[List] = None) -> List[Dict]:
+               ceiling_cols: Optional[Dict[str, Dict]] = None, keep: Optional[List] = None,
+               defer_oracle: bool = False) -> List[Dict]:
     """All viewpoints x parameter combos x levels of one (scene, strategy) in one batched launch -> one row per
     frame.  `grid` brute-forces the strategy's tunable parameters (reference sweep.py:181,222-223).  `oracle_frames`
     (viewpoint name -> oracle capture, None without one) adds the ORACLE_FIELDS columns, `ceiling_cols` (viewpoint name ->
     CEILING_FIELDS values) those.  `keep` (a list) receives (row, viewpoint name, camera, hit map, depth map) of every row,
-    for ssim_columns."""
+    for ssim_columns and device_oracle_columns.  `defer_oracle`: the ORACLE_FIELDS cells are left empty here, for
+    device_oracle_columns to fill."""
     from .runner import GPURunner
     vps = viewpoints_for(scene)
     combos = param_combos(strategy.key) if grid else [{}]
@@ -155,7 +157,8 @@ def sweep_cell(collector: HipCollector, scene, strategy, mode: str, levels, widt
             "ms_per_frame": float(st.kernel_ms),
         })
         if oracle_frames is not None:
-            rows[-1].update(oracle_columns({"hit": st.hit_map, "depth": st.depth_map}, oracle_frames.get(vp.name)))
+            rows[-1].update(oracle_columns({"hit": st.hit_map, "depth": st.depth_map},
+                                           None if defer_oracle else oracle_frames.get(vp.name)))
         if ceiling_cols is not None:
             rows[-1].update(ceiling_cols[vp.name])
         if keep is not None:
@@ -171,6 +174,25 @@ def oracle_columns(frame: Dict, oracle: Optional[Dict]) -> Dict:
     d = scoring._depth_metrics(frame, oracle)
     return {"oracle_iou": h["iou"], "oracle_false_hit": h["false_hit_rate"], "oracle_false_miss": h["false_miss_rate"],
             "oracle_depth_mae": d["mae"], "oracle_depth_rmse": d["rmse"], "oracle_depth_p95": d["p95"]}
+
+
+def device_oracle_columns(kept: List, oracle_frames: Dict[str, Optional[Dict]]) -> None:
+    """Fills the ORACLE_FIELDS columns of the kept rows of one scene (sweep_cell's `keep`, with defer_oracle) on the device:
+    all rows of a viewpoint -- every strategy, parameter combo and level -- against that viewpoint's oracle capture in ONE
+    rm_score_captures call (score_device.py).  Rows of a viewpoint without an oracle capture keep their empty cells."""
+    from . import score_device
+    by_vp: Dict[str, List] = {}
+    for item in kept:
+        by_vp.setdefault(item[1], []).append(item)
+    for name, items in by_vp.items():
+        truth = oracle_frames.get(name)
+        if truth is None:
+            continue
+        methods = [{"hit": hit, "depth": depth} for _, _, _, hit, depth in items]
+        for (row, *_), rep in zip(items, score_device.score_capture_batch(methods, {"hit": truth["hit"], "depth": truth["depth"]})):
+            h, d = rep["hit"], rep["depth"]
+            row.update({"oracle_iou": h["iou"], "oracle_false_hit": h["false_hit_rate"], "oracle_false_miss": h["false_miss_rate"],
+                        "oracle_depth_mae": d["mae"], "oracle_depth_rmse": d["rmse"], "oracle_depth_p95": d["p95"]})
 
 
 def device_normal_maps(scene, items: List) -> List[np.ndarray]:
@@ -241,19 +263,23 @@ def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float, t
             for vp in vps}
 
 
-def ceiling_columns(frame: Optional[Dict], oracle: Optional[Dict]) -> Dict:
+def ceiling_columns(frame: Optional[Dict], oracle: Optional[Dict], device_score: bool = False) -> Dict:
     """CEILING_FIELDS of one faithful_capture frame against the oracle capture of its viewpoint; None (empty cells) without
-    them."""
+    them.  `device_score`: the residual comes from the device (score_device.residual_batch)."""
     if frame is None or oracle is None:
         return {k: None for k in CEILING_FIELDS}
-    res = scoring.residual(frame["hit"], frame["depth"], oracle["hit"], oracle["depth"], scoring.silhouette_band(oracle["hit"], k=2))
+    if device_score:
+        from . import score_device
+        res = score_device.residual_batch([{"hit": frame["hit"], "depth": frame["depth"]}], oracle, k=2)[0]
+    else:
+        res = scoring.residual(frame["hit"], frame["depth"], oracle["hit"], oracle["depth"], scoring.silhouette_band(oracle["hit"], k=2))
     c = faithful_segment.cost(frame)
     return {"ceiling_iou": res["iou"], "ceiling_depth_med": res["depth_med"], "ceiling_iters_median": c["iters_median"],
             "ceiling_iters_p95": c["iters_p95"]}
 
 
 def ceiling_columns_for(scene, width: int, height: int, oracle_frames: Dict[str, Optional[Dict]], tol: float,
-                        twins: bool = False) -> Dict[str, Dict]:
+                        twins: bool = False, device_score: bool = False) -> Dict[str, Dict]:
     """ceiling_columns of every curated viewpoint of `scene` (oracle_frames: oracle_frames_for of the same scene, size and
     `twins`)."""
     out = {}
@@ -266,7 +292,7 @@ def ceiling_columns_for(scene, width: int, height: int, oracle_frames: Dict[str,
         truth = oracle_frames.get(vp.name)
         frame = None if truth is None else faithful_segment.faithful_capture(
             sound, Camera(vp.position, vp.target, vp.up, 60.0, width, height), tol=tol, cfg=cfg)
-        out[vp.name] = ceiling_columns(frame, truth)
+        out[vp.name] = ceiling_columns(frame, truth, device_score)
     return out
 
 
@@ -276,7 +302,7 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
               out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False,
               oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL,
               ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL, ssim: bool = False,
-              oracle_twins: bool = False, device_capture: bool = False) -> List[Dict]:
+              oracle_twins: bool = False, device_capture: bool = False, device_score: bool = False) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
@@ -290,7 +316,11 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     ceiling frame is traced with the tracer's clamp on K (RmSegmentConfig.l_global) raised to the scene's Lipschitz bound
     (2 for Bad Lipschitz Sphere), a scene with its own interval form with the default clamp of 1: where the bound is above
     1 the two kinds of ceiling row come from different tracer configs.  device_capture=True (with ssim): the frames' normals
-    come from the capture kernel, one rm_shade_frames call per viewpoint (ssim_columns); off, the output is unchanged."""
+    come from the capture kernel, one rm_shade_frames call per viewpoint (ssim_columns); off, the output is unchanged.
+    device_score=True (only with an oracle): ORACLE_FIELDS, and the residual behind CEILING_FIELDS when a ceiling is asked
+    for, come from the device -- one rm_score_captures call per viewpoint over all of its rows (device_oracle_columns); the
+    count-derived and percentile columns equal the host's, the means differ by summation order only.  Off, the output is
+    unchanged."""
     if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
         raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
     if ceiling is not None and ceiling not in CEILINGS:
@@ -299,6 +329,8 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
         raise ValueError("ssim needs an oracle to score against: pass oracle=")
     if device_capture and not ssim:
         raise ValueError("device_capture computes the normals of the ssim columns: pass ssim=True")
+    if device_score and oracle is None:
+        raise ValueError("device_score scores against an oracle: pass oracle=")
     scenes = registry.get_all_scenes() if not scene_names else [_need(registry.get_scene_by_name(n), "scene", n) for n in scene_names]
     strats = ([registry.get_strategy_by_name(k) for k in registry.list_strategies()] if not strategy_names
               else [_need(registry.get_shader_strategy(n) or registry.get_strategy_by_name(n), "strategy", n) for n in strategy_names])
@@ -309,17 +341,20 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
         truth = (oracle_frames_for(scene, width, height, "interval", oracle_tol, oracle_twins)
                  if oracle is not None or ceiling is not None else None)
         ofr = truth if oracle is not None else None
-        ccols = ceiling_columns_for(scene, width, height, truth, ceiling_tol, oracle_twins) if ceiling is not None else None
-        kept: Optional[List] = [] if ssim else None
+        ccols = (ceiling_columns_for(scene, width, height, truth, ceiling_tol, oracle_twins, device_score)
+                 if ceiling is not None else None)
+        kept: Optional[List] = [] if ssim or device_score else None
         for strat in strats:
             if strat.has_lipschitz:
                 strat.lipschitz = scene.known_lipschitz_bound() or 1.0      # run_once wiring (reference main.py:58-61)
-            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid, ofr, ccols, kept)
+            cell = sweep_cell(collector, scene, strat, mode, levels, width, height, grid, ofr, ccols, kept, device_score)
             rows.extend(cell)
             if verbose:
                 print(f"{scene.name:24s} {strat.short_name:24s} {len(cell):3d} frames  "
                       f"{sum(r['ms_per_frame'] for r in cell):8.2f} ms", file=sys.stderr)
-        if kept:
+        if kept and device_score:
+            device_oracle_columns(kept, ofr)
+        if kept and ssim:
             ssim_columns(scene, kept, ofr, device_normals=device_capture)
     if out_path:
         write_rows(rows, out_path)
@@ -369,6 +404,9 @@ def main(argv=None) -> int:
     ap.add_argument("--device-capture", action="store_true",
                     help="with --ssim: the frames' normals from the capture kernel, one rm_shade_frames call per viewpoint, instead "
                          "of one host round trip per row")
+    ap.add_argument("--device-score", action="store_true",
+                    help="with --oracle: the oracle_* columns (and the residual behind the ceiling_* columns) from the device, one "
+                         "rm_score_captures call per viewpoint, instead of NumPy per row")
     ap.add_argument("--oracle-twins", action="store_true",
                     help="with --oracle / --ceiling: score a catalogue scene that has no interval form against its program twin "
                          "(Menger, Bad Lipschitz Sphere, Bumpy Sphere, Gyroid, Box Lattice); a twin's ceiling is traced with l_global = the "
@@ -378,13 +416,15 @@ def main(argv=None) -> int:
         ap.error("--ssim needs --oracle")
     if a.device_capture and not a.ssim:
         ap.error("--device-capture needs --ssim")
+    if a.device_score and a.oracle is None:
+        ap.error("--device-score needs --oracle")
     if a.oracle_twins and a.oracle is None and a.ceiling is None:
         ap.error("--oracle-twins needs --oracle or --ceiling")
     rows = run_sweep([s for s in a.scenes.split(",") if s], [s for s in a.strategies.split(",") if s], a.mode, a.width, a.height,
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
                      a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol,
                      ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim, oracle_twins=a.oracle_twins,
-                     device_capture=a.device_capture)
+                     device_capture=a.device_capture, device_score=a.device_score)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 
