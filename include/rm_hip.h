@@ -19,7 +19,12 @@
  * the other copy corrupts the runtime (round 2's SIGABRT).  While two copies are mapped, only streams made by
  * rm_stream_create are accepted (anything else: RM_E_BAD_ARG, the handle is not touched); with one copy mapped every
  * hipStream_t of the process is that runtime's and is accepted (e.g. a torch stream when torch was imported first).
- * Hosts without a HIP binding of their own take streams from rm_stream_create.
+ * Hosts without a HIP binding of their own take streams from rm_stream_create; rm_shutdown destroys those that are left.
+ * One stream of the library's own per session: a single-launch frame in its split form (RmFrameDesc.pipeline_form) runs
+ * its team kernel on an internal stream next to the producer kernel on the caller's.  The internal stream starts after
+ * what the caller's stream held when the frame was enqueued and the caller's stream continues after it, so events the
+ * caller records around a frame cover both kernels and nothing else of the caller's is reordered.  It is created by the
+ * first such frame and destroyed by rm_shutdown.
  * Scene programs: the registry of programs has a lock of its own; create / destroy may be called from any thread.
  * Destroying a program while a frame that renders it is still in flight on a stream is the caller's error (the
  * frame reads the program's device copy until it ends): synchronise the stream first.
@@ -206,7 +211,14 @@ typedef struct RmFrameDesc {
      * 1-8 % faster from two of the Mandelbulb's three curated cameras and writes half as much again to HBM).  Results are identical. */
     int32_t early_handover;
     int32_t early_trips;
-    int32_t reserved1;
+    /* How the single launch (pipeline = 2) is performed.  0 = library's choice, 1 = fused: one kernel whose workgroups are
+     * producers or teams, 2 = split: the producers and the teams are two kernels that run side by side, the producers on the
+     * caller's stream and the teams on a stream of the library's own (each kernel gets a register allocation of its own;
+     * the caller's stream continues when both have ended), 3 = the two kernels one after the other on the caller's stream
+     * (for tests: what a device that does not run them side by side makes of form 2).  Forms 2 and 3 exist for the default
+     * schedule -- scenes with a team form, queue_first = 0 / 3, no late teams -- and are refused elsewhere (RM_E_BAD_ARG);
+     * ignored by frames that are not single launches.  Results are identical in every form. */
+    int32_t pipeline_form;
 } RmFrameDesc;
 
 /* Frame reduce computed in-kernel (the integer part of RayMarchStats.compute, core/types.py:77-137). */

@@ -187,6 +187,11 @@ struct Session {
     hipEvent_t frame_ev = nullptr;                   // end of the latest frame, on `frame_stream` (frames share one workspace)
     hipStream_t frame_stream = nullptr;
     bool frame_ev_valid = false;
+    // The split single launch (rm_pipeline.h): the team kernel runs on a stream of the library's own, next to the producer
+    // kernel on the caller's.  Created by the first split frame; split_ev[0] = "the frame's set-up is enqueued" (the side
+    // stream waits for it), split_ev[1] = "the team kernel has ended" (the caller's stream waits for it).
+    hipStream_t team_stream = nullptr;
+    hipEvent_t split_ev[2] = { nullptr, nullptr };
 };
 
 // The library's state: the session and the grow-only device workspace.  Only buffers are declared here (anything else
@@ -467,6 +472,7 @@ int check_desc(const RmFrameDesc* d)
     if (d->resume_mode < 0 || d->resume_mode > 3) return fail(RM_E_BAD_ARG, "resume_mode must be 0..3");
     if (d->resume_grid < 0) return fail(RM_E_BAD_ARG, "negative resume_grid");
     if (d->pipeline < 0 || d->pipeline > 2) return fail(RM_E_BAD_ARG, "pipeline must be 0, 1 or 2");
+    if (d->pipeline_form < 0 || d->pipeline_form > 3) return fail(RM_E_BAD_ARG, "pipeline_form must be 0 .. 3");
     if (d->team_grid < 0 || d->queue_first < 0 || d->queue_first > 3 || d->team_steal < 0 || d->team_steal > 2 ||
         d->queue_refill_min < 0 || d->queue_refill_min > 64 || d->queue_retry < 0 || d->team_retry < 0 || d->age_priority < 0)
         return fail(RM_E_BAD_ARG, "bad single-launch tuning field");
@@ -690,6 +696,43 @@ int launch(const RmFrameDesc* d, const rm::LaunchPlan& p, const rm::KernelArgs& 
     return RM_OK;
 }
 
+// How the single launch of plan `p` is performed (RmFrameDesc.pipeline_form): 1 = the fused pipeline_kernel, 2 = producers
+// and teams as two kernels side by side, 3 = the two kernels one after the other on the caller's stream (tests).
+// The split form covers the default schedule -- detach mode, every team resident from the start -- where a producer never
+// waits for a team; any other knob set keeps the fused kernel.  Library's choice (0): kSplitByDefault, and only where
+// each of the two kernels reaches at least the workgroups per compute unit the plan's grid counts on, so that together
+// they occupy no more than the fused grid does.
+// Measured (parent, fused default and split default alternating three times on one MI355X, DESIGN.md section 3 "Split single
+// launch"): bench.py 270.5-272.5 Mrays/s with the fused kernel, 278.0-278.7 split.
+#ifndef RM_SPLIT_BY_DEFAULT
+#define RM_SPLIT_BY_DEFAULT 1      // (-DRM_SPLIT_BY_DEFAULT=0: the other default, for a same-box A/B of two libraries)
+#endif
+constexpr bool kSplitByDefault = RM_SPLIT_BY_DEFAULT != 0;
+int single_launch_form(const RmFrameDesc* d, const rm::LaunchPlan& p, const rm::KernelArgs& a, const rm::SceneLaunchers* sc, int* form)
+{
+    *form = 1;
+    if (d->pipeline_form == 1) return RM_OK;
+    const bool covered = sc->pipeline_teams && sc->pipeline_producers && p.team_wgs > 0 && p.suspend_after2 > 0 && p.q0_detach != 0 &&
+                         p.early_exit_wgs == 0 && p.late_team_first == p.pipeline_grid;
+    if (d->pipeline_form >= 2) {
+        if (!covered)
+            return fail(RM_E_BAD_ARG, "pipeline_form %d: the split form exists for single launches with teams in detach mode without late teams", d->pipeline_form);
+        *form = d->pipeline_form;
+        return RM_OK;
+    }
+    if (!kSplitByDefault || !covered || a.frames) return RM_OK;
+    // Skipping-Spheres and Adaptive-Hybrid keep the fused kernel: same alternation at 1920x1080, fused / split 8.91 / 8.99-9.00 ms
+    // and 4.61 / 4.68-4.76 (few of their rays reach the teams; the other nine of the registry gain or stay within the spread)
+    if (d->strategy_id == 7 || d->strategy_id == 9) return RM_OK;
+    int fused = 0, producers = 0, teams = 0;
+    if (sc->occupancy_pipeline(d->strategy_id, a.interleave, 0, &fused) != hipSuccess ||
+        sc->occupancy_split(d->strategy_id, a.tile_h, a.interleave, 0, &producers, &teams) != hipSuccess)
+        return RM_OK;
+    const int per_cu = rm::grid_per_cu(fused);
+    if (producers >= per_cu && teams >= per_cu) *form = 2;
+    return RM_OK;
+}
+
 // Performs the plan `p` (rm_launch_plan.h) of one launch: workspace, caches and enqueues in the order it dictates.
 int launch_frame(const RmFrameDesc* d, const rm::LaunchPlan& p, rm::KernelArgs a, hipStream_t s)
 {
@@ -804,7 +847,33 @@ int launch_frame(const RmFrameDesc* d, const rm::LaunchPlan& p, rm::KernelArgs a
             g.trace_pix = npix;
         }
         if (a.tile_cost) HIP_TRY(hipMemsetAsync(a.tile_cost, 0, (size_t)ntiles * 4, s));   // resumed rays may report before the tile flush
-        HIP_TRY(sc->pipeline(d->strategy_id, a, p.pipeline_grid, s));
+        int form = 1;
+        if (int rcf = single_launch_form(d, p, a, sc, &form)) return rcf;
+        if (form == 1) {
+            HIP_TRY(sc->pipeline(d->strategy_id, a, p.pipeline_grid, s));
+        } else {
+            // PRODUCERS FIRST: they never wait for a team, so whatever the device makes of the two kernels -- side by side, or
+            // the teams only once the producers have left -- the frame is correct and ends.  A team that starts before any
+            // producer polls (bounded) until the producer waves have reported their exit.
+            const int producer_wgs = p.pipeline_grid - p.team_wgs;
+            hipStream_t ts = s;
+            if (form == 2) {
+                if (!g.team_stream) {
+                    HIP_TRY(hipStreamCreateWithFlags(&g.team_stream, hipStreamNonBlocking));
+                    for (auto& e : g.split_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                }
+                ts = g.team_stream;
+                HIP_TRY(hipEventRecord(g.split_ev[0], s));            // control block, queues and statistics are reset
+                HIP_TRY(hipStreamWaitEvent(ts, g.split_ev[0], 0));
+            }
+            HIP_TRY(sc->pipeline_producers(d->strategy_id, a, producer_wgs, s));
+            HIP_TRY(sc->pipeline_teams(d->strategy_id, a, p.team_wgs, ts));
+            if (form == 2) {
+                // the caller's stream goes on when both kernels have ended: its events and the statistics fold cover the teams
+                HIP_TRY(hipEventRecord(g.split_ev[1], ts));
+                HIP_TRY(hipStreamWaitEvent(s, g.split_ev[1], 0));
+            }
+        }
         if (pt) HIP_TRY(hipEventRecord(g.pev[++g.pass_count], s));
         g.last_was_pipeline = true;
         g.last_stats = a.stats;
@@ -1145,6 +1214,17 @@ void rm_shutdown(void)
     if (!g.ready) return;
     (void)hipSetDevice(g.device);
     (void)hipStreamSynchronize(g.stream);
+    if (g.team_stream) {
+        (void)hipStreamSynchronize(g.team_stream);
+        for (auto& e : g.split_ev) (void)hipEventDestroy(e);
+        (void)hipStreamDestroy(g.team_stream);
+    }
+    // streams handed out by rm_stream_create belong to this session: run them dry, destroy and forget them
+    for (void* s : g_own_streams) {
+        (void)hipStreamSynchronize((hipStream_t)s);
+        (void)hipStreamDestroy((hipStream_t)s);
+    }
+    g_own_streams.clear();
     g_seen_streams.clear();
     release_all(g_workspace_bufs);
     if (g.frame_ev_valid) (void)hipEventDestroy(g.frame_ev);

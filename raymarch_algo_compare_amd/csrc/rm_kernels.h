@@ -1247,6 +1247,12 @@ struct SceneLaunchers {
                                   uint8_t* hit, double* t, int32_t* iters, double* fs, unsigned long long* busy, int fillers, hipStream_t s);
     // capture_kernel over `nframes` frames (1..65535) of a.rows x a.width pixels each
     hipError_t (*capture)(const CaptureArgs& a, int nframes, hipStream_t s);
+    // The split form of the single launch (rm_pipeline.h; nullptr: the scene has no team form): the producer workgroups of
+    // the plan and its team workgroups as two kernels that take the same arguments, and the workgroups per compute unit
+    // each of them reaches.
+    hipError_t (*pipeline_producers)(int strategy, const KernelArgs& a, int grid, hipStream_t s);
+    hipError_t (*pipeline_teams)(int strategy, const KernelArgs& a, int grid, hipStream_t s);
+    hipError_t (*occupancy_split)(int strategy, int tile_h, int interleave, int batch, int* producers_per_cu, int* teams_per_cu);
 };
 
 }  // namespace rm

@@ -281,16 +281,183 @@ __device__ __forceinline__ bool early_handover(const KernelArgs&, const NoEval&,
 template <class Scene, class E>
 __device__ __forceinline__ bool early_handover(const KernelArgs&, const E&, long) { return false; }
 
-template <class Scene, class Strat, int TILE_H, bool INTERLEAVE, bool BATCH>
-__global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const KernelArgs a)
+// THE TEAM ROLE: what one wave (part 0 .. 2) of a team does from the moment its workgroup's mailbox `L` is zeroed until no
+// ray can arrive any more -- the queue-1 pop protocol, the shared trips, the result stores, marks, trace, histogram flush and
+// the kCTeamDone report.  Written once: the fused pipeline_kernel runs it in its team workgroups, pipeline_team_kernel
+// (below) is nothing else.  The three waves of the team are the only live waves of their workgroup, so the hardware
+// barrier synchronises them.
+// The launch's arguments come in twice.  `a` is read where every evaluation looks (the refill knobs, the trace switch) and
+// at entry; `ar` everywhere else -- the pop, the finished ray, the exit -- which a wave reaches once in hundreds of
+// evaluations.  The fused kernel passes its kernel arguments for both.  pipeline_team_kernel passes a copy in LDS as `ar`:
+// left in the kernel arguments, the camera, the output pointers and the queue fields are fetched at entry and sit in scalar
+// registers through every trip loop (36 of them against 17 in march_rays_team_kernel), and the loops rebuild their
+// 64-bit constants on every trip for want of registers.
+template <class Scene, class Strat, bool BATCH>
+__device__ __forceinline__ void pipe_team_role(const KernelArgs& a, const KernelArgs& ar, PipeTeamLds& L, const int part, const int lane)
+{
+    WaveAcc acc;
+    // a team carries the frame's critical chains: its waves win the issue arbitration on the SIMDs they share
+    if (a.team_prio >= 3) __builtin_amdgcn_s_setprio(3);
+    else if (a.team_prio == 2) __builtin_amdgcn_s_setprio(2);
+    else if (a.team_prio == 1) __builtin_amdgcn_s_setprio(1);
+    bool active = false;
+    uint32_t my_gi = 0;
+    uint32_t my_push = 0;                 // when this ray entered the queue (ticks since launch; tuning marks)
+    uint32_t my_pop = 0, nev_pop = 0;     // development trace: when it left the queue, evaluations it had then
+    int nev = 0;
+    vec3 origin = v3(0.0, 0.0, 0.0), dir = v3(0.0, 0.0, 0.0);
+    MarchCfg lane_cfg = a.single.cfg;
+    if constexpr (!BATCH) pin_cfg(lane_cfg);
+    const MarchCfg& cfg = lane_cfg;
+    Strat s;
+    typename Scene::Eval ev;
+    int turn = 0;
+    int since_try = 0;                    // evaluations since the last look at the queues
+    unsigned long long idle_since = 0;    // device clock when the team last had work (part 0, lane 0)
+
+    for (;;) {
+        const unsigned long long idle = __ballot(!active);
+        const int nidle = __popcll(idle);
+        // same decision in every wave of the team (identical state)
+        const bool look = nidle == 64 || (nidle >= a.refill_min && since_try >= a.team_retry);
+        if (look) {
+            since_try = 0;
+            if (part == 0) {
+                // part 0 claims AND waits for the publication of the claimed entries: one wave decides which lanes
+                // take a ray (a wait that runs into its bound drops the entry), the others follow its mask -- three
+                // waves polling on their own could disagree and leave the team's lock-step
+                unsigned int base = 0, done = 0;
+                int q = 1, cnt = 0;
+                if (lane == 0) {
+                    cnt = q_claim_lane0(ar, 1, nidle, base);
+                    if (cnt == 0 && ar.team_steal) { q = 0; cnt = q_claim_lane0(ar, 0, nidle, base); }
+                    if (cnt == 0 && nidle == 64) {
+                        // nothing anywhere: finished once no producer can push any more (one load per idle poll) and
+                        // both queues are handed out (looked at only then)
+                        const unsigned long long ex = ld_relaxed(ctl(ar, kCProdExited));      // read BEFORE the queue counters
+                        if (ex >= (unsigned long long)ar.producer_waves && q_available(ar, 1) <= 0 && q_available(ar, 0) <= 0) done = 1;
+                        const unsigned long long now = realtime();
+                        if (idle_since == 0) idle_since = now;
+                        if (!done && now - idle_since > kMaxTeamWaitTicks) { atomicMax(&ar.stats[kWError], 2ull); done = 1; }
+                    } else if (cnt > 0) {
+                        idle_since = 0;
+                        if (ar.marks && q == 1) atomicMax(&ar.stats[kWMarkPop], realtime());
+                    }
+                }
+                cnt = __builtin_amdgcn_readfirstlane(cnt);
+                q = __builtin_amdgcn_readfirstlane(q);
+                base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+                unsigned long long okm = 0;
+                if (cnt > 0) {
+                    const int rank = rank_in_mask(idle);
+                    const bool want = !active && rank < cnt;
+                    const bool got = q_wait_ready<Strat>(ar, q, want, base + (unsigned int)rank);
+                    okm = __ballot(want && got);
+                }
+                if (lane == 0) {
+                    L.base = base; L.count = (unsigned int)cnt; L.queue = (unsigned int)q; L.done = done;
+                    L.ok_lo = (unsigned int)okm; L.ok_hi = (unsigned int)(okm >> 32);
+                }
+            }
+            __syncthreads();
+            const unsigned int base = L.base, cnt = L.count, q = L.queue, done = L.done;
+            const unsigned long long okm = ((unsigned long long)L.ok_hi << 32) | (unsigned long long)L.ok_lo;
+            __syncthreads();              // the mailbox may be rewritten on the next look
+            if (done) break;
+            if (cnt > 0) {
+                if (part != 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // part 0 acquired in q_wait_ready
+                const int rank = rank_in_mask(idle);
+                const bool mine = ((okm >> lane) & 1ull) != 0;
+                if (mine) {
+                    const QEntry<Strat>* const e = (const QEntry<Strat>*)ar.queue[q] + (base + (unsigned int)rank);
+                    my_gi = e->gi;
+                    nev = (int)e->nev;
+                    s = e->s;
+                    my_push = e->pad;
+                    if (ar.trace) { my_pop = (uint32_t)(realtime() - ~ld_relaxed(&ar.stats[kWMarkStart])); nev_pop = (uint32_t)nev; }
+                    uint32_t frame; int x, gy;
+                    element_pixel(ar, my_gi, frame, x, gy);
+                    if constexpr (BATCH) {
+                        const FrameParams& fp = ar.frames[frame];
+                        camera_ray(fp.cam, ar.width, ar.height, x, gy, origin, dir);   // recomputed: same bits
+                        lane_cfg = fp.cfg;
+                        lane_cfg.full = ar.full;
+                    } else {
+                        camera_ray(ar.single.cam, ar.width, ar.height, x, gy, origin, dir);
+                    }
+                    active = true;
+                }
+            } else if (nidle == 64) {
+                // back off: one lane of one wave per team polls, a few microseconds apart (the pick-up delay is
+                // nothing against the hundreds of evaluations a parked ray has ahead of it)
+                __builtin_amdgcn_s_sleep(127);
+                __builtin_amdgcn_s_sleep(127);
+                continue;
+            }
+        }
+        if (!__any(active)) continue;
+
+        // ---- one whole SDF evaluation for every live ray, trips shared by the team -------------------
+        ++since_try;
+        bool ready = true;
+        if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
+        team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, L.xch, turn); });
+        const int live = a.trace ? __popcll(__ballot(active)) : 0;
+        if (active) {
+            ++nev;
+            if (s.step(Scene::value(ev), cfg)) {
+                active = false;
+                if (part == 0) {
+                    store_direct(ar, my_gi, s.res, nev, acc, L.hist);
+                    if (ar.trace) {
+                        const uint32_t k = atomicAdd(&ar.trace[0], 1u);
+                        if (k < ar.trace_cap) {
+                            uint32_t* const r = ar.trace + 8 + 8 * (size_t)k;
+                            r[0] = my_gi; r[1] = (uint32_t)s.res.iters; r[2] = my_push; r[3] = my_pop;
+                            r[4] = (uint32_t)(realtime() - ~ld_relaxed(&ar.stats[kWMarkStart]));
+                            r[5] = nev_pop; r[6] = (uint32_t)nev; r[7] = (uint32_t)blockIdx.x | ((uint32_t)live << 16);
+                        }
+                    }
+                    if (ar.marks && s.res.iters >= kLongRay) {        // tuning marks of the frame's longest rays
+                        const unsigned long long now = realtime() - ~ld_relaxed(&ar.stats[kWMarkStart]);
+                        atomicMax(&ar.stats[kWLongPushMax], (unsigned long long)my_push);
+                        atomicMax(&ar.stats[kWLongPushMin], ~(unsigned long long)my_push);
+                        atomicMax(&ar.stats[kWLongTeamMax], now - my_push);
+                        atomicMax(&ar.stats[kWLongTeamMin], ~(now - my_push));
+                    }
+                }
+            }
+        }
+    }
+    unsigned long long* const spart = stats_part(ar.stats);
+    if (part == 0) acc.flush(spart);
+    __syncthreads();                      // part 0's histogram updates are in LDS
+    for (int b = part * 64 + lane; b < kHistBins; b += 64 * kTeam) {
+        const unsigned int c = L.hist[b];
+        if (c) atomicAdd(&spart[kStatsHead + b], (unsigned long long)c);
+    }
+    if (part == 0 && lane == 0) __hip_atomic_fetch_add(ctl(ar, kCTeamDone), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The body of pipeline_kernel (fused: TEAM_ROLE = the scene has a team form) and of pipeline_producer_kernel (the SPLIT form,
+// TEAM_ROLE = false: every workgroup is a producer, workgroup 0 holds producer wave 0, and the teams are a kernel of their
+// own -- pipeline_team_kernel -- enqueued next to this one and fed through the same queue and control block).
+// The launch's arguments come in twice, as in pipe_team_role.  `ka` is what a wave reads once at entry into values it keeps
+// (the tile count, the park budgets); `a` is read everywhere else.  The fused kernel passes its kernel arguments for both.
+// The SPLIT form passes a copy in LDS as `a`, runs in detach mode only and never leaves early: read from the kernel
+// arguments, some sixty fields sit in scalar registers through the march loop, their spills take four vector registers as
+// lanes, and the interleaved Mandelbulb march at the 256-register cap then spills 2 ... 4 vector registers to scratch.
+template <class Scene, class Strat, int TILE_H, bool INTERLEAVE, bool BATCH, bool TEAM_ROLE, bool SPLIT>
+__device__ __forceinline__ void pipeline_body(const KernelArgs& ka, const KernelArgs& a)
 {
     static_assert(!INTERLEAVE || SceneIterative<Scene>::value, "INTERLEAVE needs Scene::Eval");
     constexpr bool TEAMS = SceneIterative<Scene>::value;      // the scene has a team form (trip_part / trip_join)
+    static_assert(TEAMS || !TEAM_ROLE, "team workgroups need a team form");
     constexpr int TILE_PIX = kTileW * TILE_H;
     using Entry = QEntry<Strat>;
     using PLds = PipeProducerLds<TILE_PIX>;
     // a workgroup has one role: producer staging and team block overlap
-    constexpr size_t kRoleBytes = sizeof(PLds) > sizeof(PipeTeamLds) ? sizeof(PLds) : sizeof(PipeTeamLds);
+    constexpr size_t kRoleBytes = (!TEAM_ROLE || sizeof(PLds) > sizeof(PipeTeamLds)) ? sizeof(PLds) : sizeof(PipeTeamLds);
     __shared__ __attribute__((aligned(16))) unsigned char s_role[kRoleBytes];
     __shared__ unsigned int s_hist[kHistBins];
     __shared__ unsigned int s_leave;          // an early-exit producer workgroup has decided to leave
@@ -308,8 +475,8 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     // grid is larger than what is resident at once, the dispatcher starts a late team when an early-exit producer
     // workgroup has left (below) -- or, at the latest, when producers finish; a team that finds nothing simply ends.
     // A producer never waits for a team (detach mode), so no co-residency is assumed.
-    const bool late_team = TEAMS && (int)blockIdx.x >= a.late_team_first;
-    const bool team_wg = TEAMS && ((int)blockIdx.x < a.team_wgs || late_team);      // workgroup-uniform
+    const bool late_team = TEAM_ROLE && (int)blockIdx.x >= a.late_team_first;
+    const bool team_wg = TEAM_ROLE && ((int)blockIdx.x < a.team_wgs || late_team);      // workgroup-uniform
     if (late_team && threadIdx.x == 0) __hip_atomic_fetch_add(ctl(a, kCLateStarted), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // wave roles in a team workgroup: 0..2 = part of the team, -1 = leave, -2 = producer
     constexpr int kRole[8] = { 0, 1, 2, -1, -1, -1, -1, -1 };
@@ -322,156 +489,15 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
         __syncthreads();                     // the last workgroup-wide barrier of a team workgroup
     }
 
-    if constexpr (TEAMS) {
+    if constexpr (TEAM_ROLE) {
     if (team_wg && wave_role == -1) return;     // the wave that would share a SIMD with a team's critical wave
     if (team_role) {
         // =================================== TEAM ====================================================
-        // a team carries the frame's critical chains: its waves win the issue arbitration on the SIMDs they share
-        if (a.team_prio >= 3) __builtin_amdgcn_s_setprio(3);
-        else if (a.team_prio == 2) __builtin_amdgcn_s_setprio(2);
-        else if (a.team_prio == 1) __builtin_amdgcn_s_setprio(1);
         // (team is 0 and part is wave_role; spelt as the division the code generator was tuned with -- the plain forms
         // allocate a few more VGPRs)
         const int team = wave_role / kTeam;
-        PipeTeamLds& L = reinterpret_cast<PipeTeamLds*>(s_role)[team];
         const int part = wave_role % kTeam;
-        bool active = false;
-        uint32_t my_gi = 0;
-        uint32_t my_push = 0;                 // when this ray entered the queue (ticks since launch; tuning marks)
-        uint32_t my_pop = 0, nev_pop = 0;     // development trace: when it left the queue, evaluations it had then
-        int nev = 0;
-        vec3 origin = v3(0.0, 0.0, 0.0), dir = v3(0.0, 0.0, 0.0);
-        MarchCfg lane_cfg = a.single.cfg;
-        if constexpr (!BATCH) pin_cfg(lane_cfg);
-        const MarchCfg& cfg = lane_cfg;
-        Strat s;
-        typename Scene::Eval ev;
-        int turn = 0;
-        int since_try = 0;                    // evaluations since the last look at the queues
-        unsigned long long idle_since = 0;    // device clock when the team last had work (part 0, lane 0)
-
-        for (;;) {
-            const unsigned long long idle = __ballot(!active);
-            const int nidle = __popcll(idle);
-            // same decision in every wave of the team (identical state)
-            const bool look = nidle == 64 || (nidle >= a.refill_min && since_try >= a.team_retry);
-            if (look) {
-                since_try = 0;
-                if (part == 0) {
-                    // part 0 claims AND waits for the publication of the claimed entries: one wave decides which lanes
-                    // take a ray (a wait that runs into its bound drops the entry), the others follow its mask -- three
-                    // waves polling on their own could disagree and leave the team's lock-step
-                    unsigned int base = 0, done = 0;
-                    int q = 1, cnt = 0;
-                    if (lane == 0) {
-                        cnt = q_claim_lane0(a, 1, nidle, base);
-                        if (cnt == 0 && a.team_steal) { q = 0; cnt = q_claim_lane0(a, 0, nidle, base); }
-                        if (cnt == 0 && nidle == 64) {
-                            // nothing anywhere: finished once no producer can push any more (one load per idle poll) and
-                            // both queues are handed out (looked at only then)
-                            const unsigned long long ex = ld_relaxed(ctl(a, kCProdExited));      // read BEFORE the queue counters
-                            if (ex >= (unsigned long long)a.producer_waves && q_available(a, 1) <= 0 && q_available(a, 0) <= 0) done = 1;
-                            const unsigned long long now = realtime();
-                            if (idle_since == 0) idle_since = now;
-                            if (!done && now - idle_since > kMaxTeamWaitTicks) { atomicMax(&a.stats[kWError], 2ull); done = 1; }
-                        } else if (cnt > 0) {
-                            idle_since = 0;
-                            if (a.marks && q == 1) atomicMax(&a.stats[kWMarkPop], realtime());
-                        }
-                    }
-                    cnt = __builtin_amdgcn_readfirstlane(cnt);
-                    q = __builtin_amdgcn_readfirstlane(q);
-                    base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
-                    unsigned long long okm = 0;
-                    if (cnt > 0) {
-                        const int rank = rank_in_mask(idle);
-                        const bool want = !active && rank < cnt;
-                        const bool got = q_wait_ready<Strat>(a, q, want, base + (unsigned int)rank);
-                        okm = __ballot(want && got);
-                    }
-                    if (lane == 0) {
-                        L.base = base; L.count = (unsigned int)cnt; L.queue = (unsigned int)q; L.done = done;
-                        L.ok_lo = (unsigned int)okm; L.ok_hi = (unsigned int)(okm >> 32);
-                    }
-                }
-                __syncthreads();
-                const unsigned int base = L.base, cnt = L.count, q = L.queue, done = L.done;
-                const unsigned long long okm = ((unsigned long long)L.ok_hi << 32) | (unsigned long long)L.ok_lo;
-                __syncthreads();              // the mailbox may be rewritten on the next look
-                if (done) break;
-                if (cnt > 0) {
-                    if (part != 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // part 0 acquired in q_wait_ready
-                    const int rank = rank_in_mask(idle);
-                    const bool mine = ((okm >> lane) & 1ull) != 0;
-                    if (mine) {
-                        const Entry* const e = (const Entry*)a.queue[q] + (base + (unsigned int)rank);
-                        my_gi = e->gi;
-                        nev = (int)e->nev;
-                        s = e->s;
-                        my_push = e->pad;
-                        if (a.trace) { my_pop = (uint32_t)(realtime() - ~ld_relaxed(&a.stats[kWMarkStart])); nev_pop = (uint32_t)nev; }
-                        uint32_t frame; int x, gy;
-                        element_pixel(a, my_gi, frame, x, gy);
-                        if constexpr (BATCH) {
-                            const FrameParams& fp = a.frames[frame];
-                            camera_ray(fp.cam, a.width, a.height, x, gy, origin, dir);   // recomputed: same bits
-                            lane_cfg = fp.cfg;
-                            lane_cfg.full = a.full;
-                        } else {
-                            camera_ray(a.single.cam, a.width, a.height, x, gy, origin, dir);
-                        }
-                        active = true;
-                    }
-                } else if (nidle == 64) {
-                    // back off: one lane of one wave per team polls, a few microseconds apart (the pick-up delay is
-                    // nothing against the hundreds of evaluations a parked ray has ahead of it)
-                    __builtin_amdgcn_s_sleep(127);
-                    __builtin_amdgcn_s_sleep(127);
-                    continue;
-                }
-            }
-            if (!__any(active)) continue;
-
-            // ---- one whole SDF evaluation for every live ray, trips shared by the team -------------------
-            ++since_try;
-            bool ready = true;
-            if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-            team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, L.xch, turn); });
-            const int live = a.trace ? __popcll(__ballot(active)) : 0;
-            if (active) {
-                ++nev;
-                if (s.step(Scene::value(ev), cfg)) {
-                    active = false;
-                    if (part == 0) {
-                        store_direct(a, my_gi, s.res, nev, acc, L.hist);
-                        if (a.trace) {
-                            const uint32_t k = atomicAdd(&a.trace[0], 1u);
-                            if (k < a.trace_cap) {
-                                uint32_t* const r = a.trace + 8 + 8 * (size_t)k;
-                                r[0] = my_gi; r[1] = (uint32_t)s.res.iters; r[2] = my_push; r[3] = my_pop;
-                                r[4] = (uint32_t)(realtime() - ~ld_relaxed(&a.stats[kWMarkStart]));
-                                r[5] = nev_pop; r[6] = (uint32_t)nev; r[7] = (uint32_t)blockIdx.x | ((uint32_t)live << 16);
-                            }
-                        }
-                        if (a.marks && s.res.iters >= kLongRay) {        // tuning marks of the frame's longest rays
-                            const unsigned long long now = realtime() - ~ld_relaxed(&a.stats[kWMarkStart]);
-                            atomicMax(&a.stats[kWLongPushMax], (unsigned long long)my_push);
-                            atomicMax(&a.stats[kWLongPushMin], ~(unsigned long long)my_push);
-                            atomicMax(&a.stats[kWLongTeamMax], now - my_push);
-                            atomicMax(&a.stats[kWLongTeamMin], ~(now - my_push));
-                        }
-                    }
-                }
-            }
-        }
-        unsigned long long* const spart = stats_part(a.stats);
-        if (part == 0) acc.flush(spart);
-        __syncthreads();                      // part 0's histogram updates are in LDS
-        for (int b = part * 64 + lane; b < kHistBins; b += 64 * kTeam) {
-            const unsigned int c = L.hist[b];
-            if (c) atomicAdd(&spart[kStatsHead + b], (unsigned long long)c);
-        }
-        if (part == 0 && lane == 0) __hip_atomic_fetch_add(ctl(a, kCTeamDone), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pipe_team_role<Scene, Strat, BATCH>(a, a, reinterpret_cast<PipeTeamLds*>(s_role)[team], part, lane);
         return;
     }
     }
@@ -480,19 +506,20 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     PLds& L = *reinterpret_cast<PLds*>(s_role);
     float (*const s_depth)[TILE_PIX] = L.depth[wave];
     uint32_t (*const s_ih)[TILE_PIX] = L.ih[wave];
-    const int ntiles = a.tiles_per_frame * a.nframes;
+    const int ntiles = ka.tiles_per_frame * ka.nframes;
     // this wave's index among the launch's producer waves (its first tile)
-    const int team_wgs = TEAMS ? a.team_wgs : 0;
-    const int pwave = ((int)blockIdx.x - team_wgs) * kPipeWaves + wave;
-    const int park0 = a.suspend_after;                                   // fresh rays -> queue 0
-    const int park1 = (TEAMS && a.team_wgs > 0) ? a.suspend_after2 : 0;  // resumed rays -> queue 1 (teams)
+    const int team_wgs = TEAM_ROLE ? a.team_wgs : 0;
+    int pwave = ((int)blockIdx.x - team_wgs) * kPipeWaves + wave;
+    if constexpr (SPLIT) pwave = __builtin_amdgcn_readfirstlane(pwave);  // wave-uniform: kept in a scalar register
+    const int park0 = ka.suspend_after;                                  // fresh rays -> queue 0
+    const int park1 = (TEAMS && ka.team_wgs > 0) ? ka.suspend_after2 : 0;  // resumed rays -> queue 1 (teams)
     const bool queues = park0 > 0;
     // detach: a fresh ray that reaches park0 trips is not parked in queue 0 -- its pixel is struck from the tile
     // (the tile flushes without it, the slot is free for the next tile) and it marches on in its lane as a
     // "resumed" ray.  No queue traffic at all below park1; queue 0 stays empty.
-    const bool detach = a.q0_detach != 0;
+    const bool detach = SPLIT || a.q0_detach != 0;
     // this workgroup may leave early to make room for a late team (wave 0 looks at the backlog, the others follow its flag)
-    const bool may_leave = TEAMS && detach && park1 > 0 && ((int)blockIdx.x - team_wgs) < a.early_exit_wgs;
+    const bool may_leave = !SPLIT && TEAMS && detach && park1 > 0 && ((int)blockIdx.x - team_wgs) < a.early_exit_wgs;
     bool leaving = false;                         // wave-uniform: no new tiles, detached rays go to queue 1 at once
 
     int slot_tile[kSlots], slot_out[kSlots];
@@ -866,6 +893,41 @@ __global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const Kern
     }
     // a finished producer workgroup keeps its compute unit's lanes busy until the teams are through (KEEP BUSY, rm_kernels.h)
     if (TEAMS && a.keep_busy > 0 && !team_wg && a.team_wgs > 0) keep_busy_until(ctl(a, kCTeamDone), (unsigned long long)a.team_wgs, a.keep_busy);
+}
+
+template <class Scene, class Strat, int TILE_H, bool INTERLEAVE, bool BATCH>
+__global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_kernel(const KernelArgs a)
+{
+    pipeline_body<Scene, Strat, TILE_H, INTERLEAVE, BATCH, SceneIterative<Scene>::value, false>(a, a);
+}
+
+// THE SPLIT FORM of the single launch: the same frame as two kernels side by side.  The fused kernel's register allocation
+// serves two roles -- about 60 KernelArgs fields and the producer's state are live into the team path, which rebuilds 64-bit
+// constants in scalar registers on every trip and moves spilled scalars through lanes.  Here the
+// producers (grid = the plan's producer workgroups, 4 waves each) and the teams (grid = team_wgs, 3 waves each) are
+// compiled and allocated on their own.  Scope: detach mode without late teams -- a producer never waits for a team, so the
+// frame is correct and ends whether the two kernels run side by side or one after the other (producers are enqueued first;
+// a team that starts before any producer waits in its bounded idle poll).
+template <class Scene, class Strat, int TILE_H, bool INTERLEAVE, bool BATCH>
+__global__ __launch_bounds__(64 * kPipeWaves, 2) void pipeline_producer_kernel(const KernelArgs a)
+{
+    __shared__ KernelArgs s_args;             // what the producers read after entry; published by pipeline_body's first barrier
+    if (threadIdx.x == 0) s_args = a;
+    pipeline_body<Scene, Strat, TILE_H, INTERLEAVE, BATCH, false, true>(a, s_args);
+}
+
+template <class Scene, class Strat, bool BATCH>
+__global__ __launch_bounds__(64 * kTeam) void pipeline_team_kernel(const KernelArgs a)
+{
+    __shared__ PipeTeamLds T;
+    __shared__ KernelArgs s_args;             // what the rare paths read (pipe_team_role); published by the barriers below
+    if (threadIdx.x == 0) s_args = a;
+    for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) T.hist[b] = 0u;
+    if (threadIdx.x == 0) { T.base = T.count = T.queue = T.done = 0u; T.ok_lo = T.ok_hi = 0u; }
+    rm_load_tables<Scene>();
+    __syncthreads();
+    if (a.marks && threadIdx.x == 0) atomicMax(&a.stats[kWMarkStart], ~realtime());
+    pipe_team_role<Scene, Strat, BATCH>(a, s_args, T, (int)(threadIdx.x >> 6), lane_id());
 }
 
 }  // namespace rm

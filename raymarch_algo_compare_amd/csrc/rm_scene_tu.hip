@@ -123,6 +123,7 @@ static hipError_t resume_team(int strategy, int level, const KernelArgs& a, int 
 
 #if defined(RM_SCENE_PROGRAM)
 #define RM_PIPELINE_FNS nullptr, nullptr
+#define RM_SPLIT_FNS nullptr, nullptr, nullptr
 #else
 #define RM_PIPELINE_FNS pipeline, occupancy_pipeline
 // One-row tiles (TILE_H = 1) are built for the scenes with a team form only: there a frame ends with its longest
@@ -150,6 +151,49 @@ static hipError_t occupancy_pipeline(int strategy, int interleave, int batch, in
     // the TILE_H = 4 instantiation is asked about for one-row launches too: the grids the launch plan computes rest on it
     return blocks_per_cu(pipeline_fn(strategy, 4, interleave, batch), 64 * kPipeWaves, blocks);
 }
+
+// The split form of the single launch (rm_pipeline.h): producers and teams as two kernels.  Scenes with a team form only;
+// the team kernel does not depend on the tile height or on the producers' evaluation mode.
+static FrameKernel pipeline_producer_fn(int strategy, int tile_h, int interleave, int batch)
+{
+    return with_strategy(strategy, FrameKernel(), [&](auto t) -> FrameKernel {
+        using S = typename decltype(t)::type;
+        if constexpr (kIter) {
+            if (tile_h == 1)
+                return with_mode(interleave, batch, [](auto il, auto b) -> FrameKernel { return pipeline_producer_kernel<SceneT, S, 1, il(), b()>; });
+            if (tile_h == 4)
+                return with_mode(interleave, batch, [](auto il, auto b) -> FrameKernel { return pipeline_producer_kernel<SceneT, S, 4, il(), b()>; });
+        }
+        return nullptr;
+    });
+}
+
+static FrameKernel pipeline_team_fn(int strategy, int batch)
+{
+    return with_strategy(strategy, FrameKernel(), [&](auto t) -> FrameKernel {
+        using S = typename decltype(t)::type;
+        if constexpr (kIter) return batch ? pipeline_team_kernel<SceneT, S, true> : pipeline_team_kernel<SceneT, S, false>;
+        return nullptr;
+    });
+}
+
+static hipError_t pipeline_producers(int strategy, const KernelArgs& a, int grid, hipStream_t s)
+{
+    return launch(pipeline_producer_fn(strategy, a.tile_h, a.interleave, a.frames != nullptr), grid, 64 * kPipeWaves, s, a);
+}
+
+static hipError_t pipeline_teams(int strategy, const KernelArgs& a, int grid, hipStream_t s)
+{
+    return launch(pipeline_team_fn(strategy, a.frames != nullptr), grid, 64 * kTeam, s, a);
+}
+
+// workgroups per compute unit of each of the two kernels (the launch's own instantiations)
+static hipError_t occupancy_split(int strategy, int tile_h, int interleave, int batch, int* producers, int* teams)
+{
+    const hipError_t e = blocks_per_cu(pipeline_producer_fn(strategy, tile_h, interleave, batch), 64 * kPipeWaves, producers);
+    return e != hipSuccess ? e : blocks_per_cu(pipeline_team_fn(strategy, batch), 64 * kTeam, teams);
+}
+#define RM_SPLIT_FNS (kIter ? pipeline_producers : nullptr), (kIter ? pipeline_teams : nullptr), (kIter ? occupancy_split : nullptr)
 #endif
 
 static int entry_bytes(int strategy)
@@ -211,7 +255,8 @@ static_assert(!kIter, "a scene program has no resumable evaluation");
 const SceneLaunchers* RM_LAUNCHERS_FN()
 {
     static const SceneLaunchers l = { render, resume, kIter ? resume_team : nullptr, RM_PIPELINE_FNS, kIter,
-                                      entry_bytes, occupancy, sdf_eval, march_rays, kIter ? march_rays_team : nullptr, capture };
+                                      entry_bytes, occupancy, sdf_eval, march_rays, kIter ? march_rays_team : nullptr, capture,
+                                      RM_SPLIT_FNS };
     return &l;
 }
 

@@ -11,7 +11,10 @@ is a runtime value.
 Input: the assembly the build keeps next to each object with KEEP_ASM=1 (after the rm_peephole.py pass), e.g.
 
   make -C raymarch_algo_compare_amd/csrc DEV=1 DEVSCENES=10 KEEP_ASM=1
-  python tools/team_loop_isa.py raymarch_algo_compare_amd/_build_dev/scene_10.s            # the bench kernel
+  python tools/team_loop_isa.py raymarch_algo_compare_amd/_build_dev/scene_10.s            # the team kernel of the split
+                                                                                           # single launch, the fused bench
+                                                                                           # kernel and march_rays_team_kernel,
+                                                                                           # then the three side by side
   python tools/team_loop_isa.py scene_10.s --kernel march_rays_team_kernel --kernel resume_team_kernel
   python tools/team_loop_isa.py scene_10.s --json
 """
@@ -23,6 +26,9 @@ import re
 import sys
 
 BENCH_KERNEL = "_ZN2rm15pipeline_kernelINS_15SceneMandelbulbENS_13StratStandardELi4ELb1ELb0EEEvNS_10KernelArgsE"
+TEAM_KERNEL = "_ZN2rm20pipeline_team_kernelINS_15SceneMandelbulbENS_13StratStandardELb0EEEvNS_10KernelArgsE"
+ALONE_KERNEL = "_ZN2rm22march_rays_team_kernelINS_15SceneMandelbulbENS_13StratStandardEEE"      # (a prefix: its arguments follow)
+DEFAULT_KERNELS = [TEAM_KERNEL, BENCH_KERNEL, ALONE_KERNEL]
 XCH_WRITE = re.compile(r"^\s*ds_write2st64_b64\b.*?(?:offset0:(\d+))?\s+offset1:(\d+)")
 LITERAL = re.compile(r"^\s*s_mov_b32\s+s\d+,\s*(0x[0-9a-fA-F]+|-?\d+)\s*$")
 
@@ -162,12 +168,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("asm", help="assembly of a scene object (KEEP_ASM=1 build)")
     ap.add_argument("--kernel", action="append", default=None,
-                    help="mangled name or a substring of it (repeatable); default: the bench kernel")
+                    help="mangled name or a substring of it (repeatable); default: the split single launch's team kernel, the "
+                         "fused bench kernel and march_rays_team_kernel")
     ap.add_argument("--json", action="store_true", help="one JSON object instead of the table")
     args = ap.parse_args(argv)
     lines = open(args.asm).read().splitlines()
     funcs = functions(lines)
-    wanted = args.kernel or [BENCH_KERNEL]
+    wanted = args.kernel or DEFAULT_KERNELS
     report = {}
     for w in wanted:
         for name, (a, b) in funcs.items():
@@ -189,6 +196,17 @@ def main(argv=None):
         for L in r["loops"]:
             part = "?" if L["part"] is None else L["part"]
             print(f"  {L['header']:<13} {part:>4} " + " ".join(f"{L[c]:>8}" for c in cols))
+    if len(report) > 1:
+        # side by side, per part: static / scalar / literal s_mov of one pass of each kernel's loop
+        short = {name: re.sub(r"^_ZN2rm\d+(\w+?)INS_.*$", r"\1", name) for name in report}
+        parts = sorted({L["part"] for r in report.values() for L in r["loops"] if L["part"] is not None})
+        print("\nstatic / scalar / literal s_mov per pass   " + "   ".join(f"{short[n]:>24}" for n in report))
+        for p in parts:
+            cells = []
+            for n, r in report.items():
+                Ls = [L for L in r["loops"] if L["part"] == p]
+                cells.append(" + ".join(f"{L['static']} / {L['scalar']} / {L['literal_s_mov']}" for L in Ls) or "-")
+            print(f"  part {p:<35} " + "   ".join(f"{c:>24}" for c in cells))
 
 
 if __name__ == "__main__":
