@@ -918,7 +918,8 @@ constexpr int kTeam = 3;
 
 // Exchange buffer of a team: [trip parity][value 0..5][lane]; double-buffered so one barrier per trip
 // suffices (a wave can only overwrite a buffer after every wave has passed the barrier that follows
-// the reads of its previous use).
+// the reads of its previous use).  A trip without an exchange (team_trips THE SHORT LAST TRIP) touches neither buffer
+// nor `turn`: the exchanges that remain keep alternating, which is all the argument needs.
 struct TeamXch {
     double v[2][2 * kTeam][64];
 };
@@ -952,27 +953,56 @@ struct ScenePartLoops : std::false_type {};
 template <class Scene>
 struct ScenePartLoops<Scene, decltype((void)Scene::kPartLoops)> : std::integral_constant<bool, Scene::kPartLoops> {};
 
-// The trips of one evaluation of every live ray (ready: the lane's value is ready).  `trip(part, go)` is team_trip
-// bound to the team's exchange and barrier.  With per-part loops the part is dispatched
+// Scene::kLastTrip / Scene::trip_last: the trip with that index only finishes the evaluation from values every wave
+// already holds (rm_scenes.h THE SHORT LAST TRIP).  Scenes without the hook compile to what they were.
+template <class Scene, class = void>
+struct SceneShortLastTrip : std::false_type {};
+template <class Scene>
+struct SceneShortLastTrip<Scene, decltype((void)Scene::kLastTrip)> : std::true_type {};
+
+// The trips of one evaluation of every live ray (ready: the lane's value is ready; `ev` as Scene::begin left it).
+// `trip(part, go)` is team_trip bound to the team's exchange and barrier.  With per-part loops the part is dispatched
 // once, outside the trip loop, on a wave-uniform scalar: each wave's loop holds only its own part's chain, with no
 // branch on the part per trip.
-template <int P, class Trip>
+// THE SHORT LAST TRIP: every caller begins the evaluation of ALL its live lanes right before the call (no lane comes in
+// with an evaluation under way) and the lanes trip in lock-step until they drop out, so the trip index of every lane
+// that is not ready is the loop's own count `n` -- one wave-uniform number, the same in the three waves.  The part loops
+// therefore stop before trip Scene::kLastTrip, and the lanes still not ready then take Scene::trip_last once, behind
+// the loops, in each wave for itself (the same bits in all three: giving it to one wave would cost the exchange and
+// barrier it saves): no exchange, no barrier, `turn` stays.  The exchanges that do happen still alternate between the
+// two halves of TeamXch, so its one-barrier argument holds.
+template <class Scene, int P, class Trip>
 __device__ __forceinline__ void team_trips_part(bool& ready, const Trip& trip)
 {
-    while (__any(!ready)) {
-        const bool fin = trip(std::integral_constant<int, P>(), !ready);
-        if (!ready) ready = fin;
+    if constexpr (SceneShortLastTrip<Scene>::value) {
+#pragma unroll 1      // the count is bounded: keep the loop a loop
+        for (int n = 0; n < Scene::kLastTrip && __any(!ready); ++n) {
+            const bool fin = trip(std::integral_constant<int, P>(), !ready);
+            if (!ready) ready = fin;
+        }
+    } else {
+        while (__any(!ready)) {
+            const bool fin = trip(std::integral_constant<int, P>(), !ready);
+            if (!ready) ready = fin;
+        }
     }
 }
 template <class Scene, class Trip>
-__device__ __forceinline__ void team_trips(int part, bool& ready, const Trip& trip)
+__device__ __forceinline__ void team_trips(int part, bool& ready, typename Scene::Eval& ev, const Trip& trip)
 {
     if constexpr (ScenePartLoops<Scene>::value) {
         part = __builtin_amdgcn_readfirstlane(part);
-        if (part == 0) team_trips_part<0>(ready, trip);
-        else if (part == 1) team_trips_part<1>(ready, trip);
-        else team_trips_part<2>(ready, trip);
+        if (part == 0) team_trips_part<Scene, 0>(ready, trip);
+        else if (part == 1) team_trips_part<Scene, 1>(ready, trip);
+        else team_trips_part<Scene, 2>(ready, trip);
+        if constexpr (SceneShortLastTrip<Scene>::value) {
+            if (__any(!ready)) {                  // only lanes entering trip Scene::kLastTrip are left
+                if (!ready) Scene::trip_last(ev);
+                ready = true;
+            }
+        }
     } else {
+        static_assert(!SceneShortLastTrip<Scene>::value, "the short last trip is built into the per-part loops only");
         while (__any(!ready)) {
             const bool fin = trip(part, !ready);
             if (!ready) ready = fin;
@@ -1012,7 +1042,7 @@ __global__ __launch_bounds__(64 * kTeam) void march_rays_team_kernel(MarchCfg cf
     while (__any(!done)) {
         bool ready = true;
         if (!done) ready = Scene::begin(ev, o + d * s.te);
-        team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
+        team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
         if (!done) done = s.step(Scene::value(ev), cfg);
     }
     if (have && part == 0) {
@@ -1111,7 +1141,7 @@ __global__ __launch_bounds__(64 * kTeam) void resume_team_kernel(const KernelArg
         // ---- one whole SDF evaluation for every live ray, trips shared by the team -------------------
         bool ready = true;
         if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-        team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
+        team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
         bool park = false;
         if (active) {
             ++nev;

@@ -401,7 +401,7 @@ __device__ __forceinline__ void pipe_team_role(const KernelArgs& a, const Kernel
         ++since_try;
         bool ready = true;
         if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-        team_trips<Scene>(part, ready, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, L.xch, turn); });
+        team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, L.xch, turn); });
         const int live = a.trace ? __popcll(__ballot(active)) : 0;
         if (active) {
             ++nev;

@@ -186,6 +186,24 @@ struct SceneMandelbulb {                                                        
         e.r = length_a(e.z);
         return e.r > 4.0;
     }
+    // THE SHORT LAST TRIP.  The trip entered with i == kLastTrip ends the loop whatever it computes, and value() reads
+    // only r (measured at the top of that trip) and dr: the new z -- the division, acos, atan2, both sincos, r ** 8, the
+    // three products and `+ p` -- is never read (:276-293).  None of those calls can raise in the reference (the acos
+    // argument is clamped, r <= 4), so leaving them out changes no bit of any result.  trip_last is what remains:
+    // the dr update, same expression and operation order as in trip() (rm_pow(x, y) has the bits of rm_pow2's first
+    // result, rm_math_pow.h).  e.i still ends at 8 (eval_trips feeds the producers' early hand-over); e.z is left
+    // STALE on purpose -- nothing reads it after an evaluation has ended: value() does not, begin() overwrites it.
+    // Taken where the lanes that are still looping share one trip index: sdf() below (lanes enter together) and the
+    // team loops (rm_kernels.h team_trips).  trip() itself stays a full pass for the interleaved producer turn, where
+    // the lanes of a wave sit at different trips.
+    static constexpr int kLastTrip = 7;
+    static RM_HD void trip_last(Eval& e)
+    {
+        const double power = 8.0;
+        const double r7 = rm_pow(e.r, power - 1.0);
+        e.dr = r7 * power * e.dr + 1.0;
+        e.i = kLastTrip + 1;
+    }
     // ---- the trip split by function, for a TEAM of wavefronts (rm_kernels.h) ----------------------
     // The three transcendental chains of a trip are independent of one another:
     //   part 0:  sin, cos of 8 * acos(clamp(z.z / max(r, 1e-12)))            (:277, :286-290)
@@ -237,7 +255,13 @@ struct SceneMandelbulb {                                                        
     {
         Eval e;
         bool done = begin(e, p);
-        while (!done) done = trip(e);
+        // every lane starts at trip 0 and a lane only ever leaves the loop, so the lanes still looping share the trip
+        // index: the test for the short last trip is uniform among them
+#pragma unroll 1
+        for (int i = 0; !done; ++i) {
+            if (i == kLastTrip) { trip_last(e); break; }
+            done = trip(e);
+        }
         return value(e);
     }
 };

@@ -124,11 +124,83 @@ def team_loops(lines, a, b):
     for lo, hi, loop, _ in blocks:
         if loop in inner_headers:
             loops.setdefault(loop, []).append((lo, hi))
-    out = []
-    for h, ranges in loops.items():
-        if any(re.match(r"^\s*s_barrier\b", lines[k]) for lo, hi in ranges for k in range(lo, hi + 1)):
-            out.append((h, ranges))
+    def has_barrier(ranges):
+        return any(re.match(r"^\s*s_barrier\b", lines[k]) for lo, hi in ranges for k in range(lo, hi + 1))
+
+    out = [(h, ranges) for h, ranges in loops.items() if has_barrier(ranges)]
+    out += two_entry_loops(lines, [blk for blk in blocks if blk[2] not in inner_headers], has_barrier)
     return sorted(out, key=lambda t: t[1][0][0])
+
+
+BRANCH = re.compile(r"^\s*s_(c?branch\w*)\s+\.LBB(\d+_\d+)\b")
+
+
+def two_entry_loops(lines, blocks, has_barrier):
+    """Trip loops the compiler does not annotate: a loop whose count sits in its test (the short last trip, rm_kernels.h
+    team_trips) comes out with two entries, and the loop comments name natural loops only.  Found from the branches
+    themselves: among the blocks that share their innermost annotated loop, that loop's header aside, every cycle (a
+    strongly connected component of more than one block, or a block that branches to itself) that holds an s_barrier.
+    Named after its first block in layout order."""
+    label = {}
+    for k, (lo, hi, loop, _) in enumerate(blocks):
+        m = BLOCK.match(lines[lo])
+        if m.group(1):
+            label[m.group(1)] = k
+    succ = {k: set() for k in range(len(blocks))}
+    for k, (lo, hi, loop, _) in enumerate(blocks):
+        falls = True
+        for i in range(lo, hi + 1):
+            ins = lines[i].split(";", 1)[0]
+            m = BRANCH.match(ins)
+            if m:
+                t = label.get(m.group(2))
+                if t is not None and blocks[t][2] == loop and loop is not None and m.group(2) != loop:
+                    succ[k].add(t)
+                falls = m.group(1) != "branch"
+            elif re.match(r"^\s*(s_endpgm|s_setpc_b64)\b", ins):
+                falls = False
+            elif ins.strip() and not ins.strip().endswith(":") and not ins.strip().startswith("."):
+                falls = True
+        if falls and k + 1 < len(blocks) and blocks[k + 1][2] == loop and loop is not None and blocks[k + 1][0] == hi + 1:
+            m = BLOCK.match(lines[blocks[k + 1][0]])
+            if m.group(1) != loop:
+                succ[k].add(k + 1)
+    # Tarjan, iterative
+    index, low, on, stack, comps, n = {}, {}, set(), [], [], [0]
+    for root in succ:
+        if root in index:
+            continue
+        work = [(root, iter(sorted(succ[root])))]
+        index[root] = low[root] = n[0]; n[0] += 1; stack.append(root); on.add(root)
+        while work:
+            v, it = work[-1]
+            for w in it:
+                if w not in index:
+                    index[w] = low[w] = n[0]; n[0] += 1; stack.append(w); on.add(w)
+                    work.append((w, iter(sorted(succ[w]))))
+                    break
+                if w in on:
+                    low[v] = min(low[v], index[w])
+            else:
+                work.pop()
+                if work:
+                    low[work[-1][0]] = min(low[work[-1][0]], low[v])
+                if low[v] == index[v]:
+                    comp = []
+                    while True:
+                        w = stack.pop(); on.discard(w); comp.append(w)
+                        if w == v:
+                            break
+                    comps.append(sorted(comp))
+    out = []
+    for comp in comps:
+        if len(comp) == 1 and comp[0] not in succ[comp[0]]:
+            continue
+        ranges = [(blocks[k][0], blocks[k][1]) for k in comp]
+        if has_barrier(ranges):
+            m = BLOCK.match(lines[ranges[0][0]])
+            out.append((m.group(1) or f"line{ranges[0][0]}", ranges))
+    return out
 
 
 def resources(lines, name):
