@@ -45,6 +45,22 @@ RM_MATH_HD double rm_fnma(double a, double b, double c) { return rm_fma(-a, b, c
 // instruction it issues costs 8 cycles of the frame's critical chain whether its result is selected or not.
 // With U a band is evaluated only if some live lane of the wave selects it (one ballot per band); the selected
 // value is computed by the same instructions either way, so results are bit-identical.
+//
+// The same ballots carry the selects (rm_acos_team, rm_atan2_team, rm_sincos_team: what the templates run with U).
+// There the select that brings a band's or a special operand's value in sits inside that band's guarded block, the
+// rescaling of atan2 sits with the ladder of special operands it belongs to, and the widest band is the value the
+// others are selected into.  A wave whose live lanes agree -- a ray marching alone in its team is the frame's
+// critical case -- runs its band and no select, compare or rescaling of the others.  "Every live lane selects this"
+// needs no ballot of its own: it is "no live lane needs any of the rest".  A guarded block holds arithmetic as well
+// as its selects: a block of selects alone comes back from the compiler as selects on (ballot & lane predicate),
+// which costs more than it saves (the range 1 fold of sincos is left alone for that reason).  Every branch is
+// wave-uniform.  The team forms are functions of their own, and the dense forms below keep their text, because
+// the compiler's schedule follows the order of the statements: the dense kernels must compile to what they were
+// (tools/kernel_isa_diff.py).  That is also why the dense bodies still spell rm_band_needed<U> and rm_do_sin<U>: with
+// U the templates return from their first statement, U never reaches those lines, and there they are always true.
+// The team forms restate the arithmetic, so they are held to libm and to the dense forms on their own: on the host,
+// where every block runs, by tests/test_math_exact_team.py (tests/test_math_exact.py holds the dense forms only); on
+// the device by tests/test_gpu_math_exact.py and tests/test_gpu_uniform_paths.py.
 template <bool U>
 RM_MATH_HD bool rm_band_needed(bool lane_selects)
 {
@@ -114,6 +130,80 @@ RM_MATH_HD double rm_do_cos(double a, double da)
     return cs + cor;
 }
 
+// do_sin for a team wave: the table form is the value, the Taylor form and its select run only for a wave that
+// holds a lane below 0.126
+RM_MATH_HD double rm_do_sin_team(double a, double da)
+{
+    typedef SinCosK K;
+    const double aa = rm_fabs(a);
+    const double dx = (a <= 0.0) ? -da : da;
+    const double u = K::big + aa;
+    const double x = aa - (u - K::big);
+    const int k = rm_sincos_row(u);
+    const double sn = tab_sincos(k, 0), ssn = tab_sincos(k, 1), cs = tab_sincos(k, 2), ccs = tab_sincos(k, 3);
+    const double xx = x * x;
+    const double s = x + rm_fma(x * xx, rm_fma(xx, K::sn5, K::sn3), dx);
+    const double c = rm_fma(x, dx, xx * rm_fma(xx, rm_fma(xx, K::cs6, K::cs4), K::cs2));
+    const double cor = rm_fma(s, cs, rm_fnma(c, sn, rm_fma(s, ccs, ssn)));
+    double res = __builtin_copysign(sn + cor, a);
+    if (rm_band_needed<true>(aa < 0.126)) {
+        const double taylor = rm_taylor_sin(a, da);                    // uses dx before the sign flip, as s_sin.c does
+        res = (aa < 0.126) ? taylor : res;
+    }
+    return res;
+}
+
+// rm_sincos for a team wave (the ranges and the routing are those of rm_sincos below).  Range 2's inputs to do_sin /
+// do_cos, its outputs, and the arguments below 2^-26 or beyond the claimed range are served by selects; here those
+// run only in a wave that holds such a lane (two ballots, one for the inputs and one for the outputs), and a wave of
+// range 1 and 3 arguments goes straight through.
+RM_MATH_HD void rm_sincos_team(double x, double* sin_out, double* cos_out)
+{
+    typedef SinCosK K;
+    const uint32_t k = (uint32_t)(rm_asuint64(x) >> 32) & 0x7fffffffu;
+    const double ax = rm_fabs(x);
+    const bool r1 = k < 0x3feb6000u;
+    const bool r2 = !r1 & (k < 0x400368fdu);
+    const bool any_r2 = rm_band_needed<true>(r2);
+    const bool any_edge = rm_band_needed<true>(r2 | (k - 0x3e500000u >= 0x419921fbu - 0x3e500000u));
+    const double t = rm_fma(x, K::hpinv, K::toint);
+    const double xn = r1 ? 0.0 : (t - K::toint);
+    const uint32_t n = r1 ? 0u : (uint32_t)rm_asuint64(t);
+    const double y = rm_fnma(xn, K::mp2, rm_fnma(xn, K::mp1, x));
+    const double t2 = rm_fnma(xn, K::pp3, y);
+    double db = rm_fnma(K::pp3, xn, y - t2);
+    const double b = rm_fnma(xn, K::pp4, t2);
+    db = db + rm_fnma(xn, K::pp4, t2 - b);
+
+    double aS = b, daS = db, aC = b, daC = db;
+    if (any_r2) {
+        const double tt = K::hp0 - ax;
+        const double a2 = tt + K::hp1;
+        const double da2 = (tt - a2) + K::hp1;
+        aS = r2 ? a2 : b, daS = r2 ? da2 : db, aC = r2 ? tt : b, daC = r2 ? K::hp1 : db;
+    }
+    const double dS = rm_do_sin_team(aS, daS);
+    const double dC = rm_do_cos(aC, daC);
+
+    const uint32_t m = n + 1u;
+    double s = (n & 1u) ? dC : dS;
+    s = (n & 2u) ? -s : s;
+    double c = (m & 1u) ? dC : dS;
+    c = (m & 2u) ? -c : c;
+    if (any_edge) {
+        const double s2 = __builtin_copysign(dC, x);
+        s = r2 ? s2 : s, c = r2 ? dS : c;
+        s = (k < 0x3e500000u) ? x : s;                      // |x| < 2^-26
+        c = (k < 0x3e400000u) ? 1.0 : c;                    // |x| < 2^-27
+        const double bad = __builtin_nan("");                // inf / nan -> nan; __branred range unclaimed
+        const bool huge = k >= 0x419921fbu;
+        s = huge ? bad : s;
+        c = huge ? bad : c;
+    }
+    *sin_out = s;
+    *cos_out = c;
+}
+
 // sin(x) and cos(x) together, branch-free.  __sin and __cos (s_sin.c) pick one of four argument
 // ranges; every range ends in do_sin on one (a, da) pair and do_cos on another:
 //   |x| < 0.855469          sin = do_sin(x, 0)                         cos = do_cos(x, 0)
@@ -124,6 +214,7 @@ template <bool U = false>
 RM_MATH_HD void rm_sincos(double x, double* sin_out, double* cos_out)
 {
     typedef SinCosK K;
+    if constexpr (U) return rm_sincos_team(x, sin_out, cos_out);      // what follows is the dense form: U never gets here
     const uint32_t k = (uint32_t)(rm_asuint64(x) >> 32) & 0x7fffffffu;
     const double ax = rm_fabs(x);
     const bool r1 = k < 0x3feb6000u;

@@ -17,6 +17,15 @@ Input: the assembly the build keeps next to each object with KEEP_ASM=1 (after t
                                                                                            # then the three side by side
   python tools/team_loop_isa.py scene_10.s --kernel march_rays_team_kernel --kernel resume_team_kernel
   python tools/team_loop_isa.py scene_10.s --json
+  python tools/team_loop_isa.py scene_10.s --kernel pipeline_team_kernel --blocks          # the loops block by block
+  python tools/team_loop_isa.py scene_10.s --kernel pipeline_team_kernel --without bb.158,bb.162,BB53_169
+
+The counts are static: one pass through every block of the loop.  The libm forms of a team wave branch on ballots
+(rm_band_needed<true>, rm_math_trig.h), so what a wave issues is the blocks its live lanes make it enter.  --blocks lists
+a loop's blocks with their counts and branch targets; --without drops the named blocks (the ones a given wave jumps
+over, read off that listing) and prints the mix of the path that is left as a second row.  A fall-through block is
+named bb.<n> after the compiler's comment, unique within one kernel only: give --kernel a name that matches one.  Block
+names change with every build; a name that matches no block of the reported loops is an error, not a shorter sum.
 """
 from __future__ import annotations
 
@@ -223,6 +232,21 @@ def resources(lines, name):
     return out
 
 
+def block_name(lines, lo):
+    """BB<f>_<n> for a labelled block, bb.<n> for one the compiler only comments (; %bb.<n>:)"""
+    m = BLOCK.match(lines[lo])
+    return f"BB{m.group(1)}" if m.group(1) else f"bb.{m.group(2)}"
+
+
+def block_rows(lines, ranges):
+    """per block of a loop: its name, its mix and the labels its branches name"""
+    rows = []
+    for lo, hi in ranges:
+        targets = [m.group(2) for m in (BRANCH.match(x.split(";", 1)[0]) for x in lines[lo:hi + 1]) if m]
+        rows.append((block_name(lines, lo), loop_mix(lines, [(lo, hi)]), ["BB" + t for t in targets]))
+    return rows
+
+
 def exchange_part(lines, ranges):
     """the team part a loop belongs to, from its exchange write: TeamXch.v[parity][2 * part][lane] and [2 * part + 1],
     one ds_write2st64_b64 whose offsets (units of 64 doubles) are 2 * part and 2 * part + 1"""
@@ -243,20 +267,36 @@ def main(argv=None):
                     help="mangled name or a substring of it (repeatable); default: the split single launch's team kernel, the "
                          "fused bench kernel and march_rays_team_kernel")
     ap.add_argument("--json", action="store_true", help="one JSON object instead of the table")
+    ap.add_argument("--blocks", action="store_true", help="list every loop's blocks: counts and branch targets")
+    ap.add_argument("--without", default="", help="comma-separated block names (as --blocks prints them) to leave out: "
+                                                  "adds a row with the mix of the remaining path to each loop that holds one")
     args = ap.parse_args(argv)
     lines = open(args.asm).read().splitlines()
     funcs = functions(lines)
     wanted = args.kernel or DEFAULT_KERNELS
+    without = {w for w in args.without.split(",") if w}
     report = {}
     for w in wanted:
         for name, (a, b) in funcs.items():
             if w == name or w in name:
                 loops = team_loops(lines, a, b)
-                report[name] = dict(resources=resources(lines, name),
-                                    loops=[dict(header="BB" + h, part=exchange_part(lines, r), **loop_mix(lines, r))
-                                           for h, r in loops])
+                entries = []
+                for h, r in loops:
+                    L = dict(header="BB" + h, part=exchange_part(lines, r), **loop_mix(lines, r))
+                    kept = [(lo, hi) for lo, hi in r if block_name(lines, lo) not in without]
+                    if len(kept) < len(r):
+                        L["path"] = dict(without=[block_name(lines, lo) for lo, hi in r if (lo, hi) not in kept],
+                                         **loop_mix(lines, kept))
+                    if args.blocks:
+                        L["blocks"] = [dict(name=n, targets=t, **mix) for n, mix, t in block_rows(lines, r)]
+                    entries.append(L)
+                report[name] = dict(resources=resources(lines, name), loops=entries)
     if not report:
         sys.exit(f"no kernel matches {wanted}")
+    # block names change with every build: a name that matches nothing would leave a path row that looks right and is not
+    dropped = {n for r in report.values() for L in r["loops"] for n in L.get("path", {}).get("without", [])}
+    if without - dropped:
+        sys.exit(f"--without names no block of the reported loops: {sorted(without - dropped)} (see --blocks)")
     if args.json:
         print(json.dumps(report, indent=1))
         return
@@ -268,6 +308,11 @@ def main(argv=None):
         for L in r["loops"]:
             part = "?" if L["part"] is None else L["part"]
             print(f"  {L['header']:<13} {part:>4} " + " ".join(f"{L[c]:>8}" for c in cols))
+            if "path" in L:
+                print(f"  {'  path':<13} {'':>4} " + " ".join(f"{L['path'][c]:>8}" for c in cols) +
+                      "   without " + ",".join(L["path"]["without"]))
+            for B in L.get("blocks", []):
+                print(f"    {B['name']:<11} {'':>4} " + " ".join(f"{B[c]:>8}" for c in cols) + "   -> " + " ".join(B["targets"]))
     if len(report) > 1:
         # side by side, per part: static / scalar / literal s_mov of one pass of each kernel's loop
         short = {name: re.sub(r"^_ZN2rm\d+(\w+?)INS_.*$", r"\1", name) for name in report}
