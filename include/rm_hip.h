@@ -777,6 +777,63 @@ int rm_capture(const RmFrameDesc* desc, const RmCaptureOutputs* out, RmStats* st
 int rm_shade_frames(int scene_id, int32_t width, int32_t height, int32_t nframes, const double* cams, const double* t,
                     const float* depth, const uint8_t* hit, float* normal, float* color, RmTiming* timing);
 
+/* ---- discovery features of a (scene, viewpoint) (csrc/rm_features.h) -----------------------------------------------
+ * The strategy-independent description the reference's research layer joins sweep rows against (report/features.py):
+ * two intrinsic features of the scene's SDF sampled in a box, five view features of a dense-march capture;
+ * csrc/rm_features.h states every definition in full.
+ *
+ * One sample set's intrinsic result: lipschitz_p99 = np.percentile(|grad f|, 99) over the n_finite samples whose central-
+ * difference gradient magnitude is finite; slab_median = np.median of the lengths of the n_slabs solid (f < 0) runs along
+ * the set's chords -- a length: the caller divides by its box diagonal.  NaN (0x7ff8000000000000) for an empty sample. */
+typedef struct RmIntrinsicFeatures {
+    double lipschitz_p99, slab_median;
+    int64_t n_finite, n_slabs;
+} RmIntrinsicFeatures;
+/* Generates, evaluates and reduces `nsets` sample sets of scene `scene_id` (a catalogue scene or a scene program) on the
+ * device: the six points p +- eps e_axis of each of the n_lip points of a set, the chord_steps samples a + ts[i] * (b - a)
+ * of each of its n_chords chords, ONE call of the scene's own point-evaluation kernel over all of them, then gradients,
+ * runs of inside samples (one wavefront per chord) and two exact selections per set.  Only the caller's draws go up and
+ * only the results come down.  pts, chords, seglen (|b - a| as the caller computed it) and ts are HOST arrays and the
+ * caller's data on purpose: the draws are its random generator's and its norm and linspace are not restated here.
+ * Optional HOST outputs: gmag_out (nsets x n_lip, NaN = left out of the sample), slab_counts_out (nsets x n_chords runs
+ * per chord).  The same inputs give the same bits on every run, a set gives the same bits alone or in a batch, and a host
+ * build of csrc/rm_features.h reproduces them from the same SDF values.  `timing` (optional) times the kernels without the
+ * copies.  Limits: nsets in [1, 256], n_lip in [0, 65536], n_chords in [0, 4096], chord_steps in [2, 1024]; n_lip == 0 and
+ * n_chords == 0 are valid and give NaN and a count of 0.  Checked before the device is touched: RM_E_BAD_ARG for an
+ * argument out of range, a lip_eps that is not finite and positive or a NULL required pointer; RM_E_BAD_SCENE for an
+ * unknown or destroyed scene id. */
+int rm_intrinsic_features(int scene_id, int32_t nsets, int32_t n_lip, const double* pts, double lip_eps, int32_t n_chords,
+                          const double* chords, const double* seglen, int32_t chord_steps, const double* ts, RmIntrinsicFeatures* out,
+                          double* gmag_out, int32_t* slab_counts_out, RmTiming* timing);
+
+/* The maps of one width x height capture as rm_capture writes them, row-major HOST arrays, all required: depth (W*H),
+ * normal (W*H*3, interleaved), evals (W*H) as floats; hit (W*H bytes, non-zero = hit). */
+typedef struct RmViewMaps {
+    const float* depth;
+    const float* normal;
+    const float* evals;
+    const uint8_t* hit;
+} RmViewMaps;
+/* One capture's view features.  n_hit; n_grazing: hits with |ray . normal| < 0.20; n_perimeter: hits with a non-hit
+ * 4-neighbour (a neighbour beyond the image is a non-hit); sum_evals over the hits.  hit_rate = n_hit / (W * H),
+ * grazing_frac = n_grazing / n_hit, silhouette_cplx = n_perimeter / sqrt(n_hit), hardness_mean = sum_evals / n_hit,
+ * hardness_cv = population standard deviation of evals over the hits / hardness_mean (0 for a mean of 0); all four 0
+ * without a hit.  box_lo / box_hi: per-axis min / max of the hit points origin + depth * ray (+inf / -inf without a hit). */
+typedef struct RmViewFeatures {
+    int64_t n_hit, n_grazing, n_perimeter, sum_evals;
+    double hit_rate, grazing_frac, silhouette_cplx, hardness_mean, hardness_cv;
+    double box_lo[3], box_hi[3];
+} RmViewFeatures;
+/* The view features of `nviews` captures of width x height pixels in one call, view v seen by the camera
+ * cams[14 * v .. 14 * v + 14) (RmFrameDesc.cam layout); each pixel's ray is the one the march kernels shoot.  Counts are
+ * integer sums and the one floating-point sum has a fixed order (32 x 8 tiles folded by halves, added in tile order): the
+ * same inputs give the same bits on every run, alone or in a batch, and on a host build of csrc/rm_features.h.  `timing`
+ * (optional) times the kernels without the copies.  Checked before the device is touched: RM_E_BAD_ARG for a NULL
+ * argument or map, nviews outside [1, 65535] or a camera field that is not finite; RM_E_BAD_DIMS for a non-positive side
+ * or more than 2^31 - 1 pixels. */
+int rm_view_features(int32_t width, int32_t height, int32_t nviews, const double* cams, const RmViewMaps* maps, RmViewFeatures* out,
+                     RmTiming* timing);
+
 #ifdef __cplusplus
 }
 #endif

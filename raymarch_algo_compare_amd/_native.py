@@ -37,6 +37,7 @@ EXPORTS = [
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
     "rm_affine_supported", "rm_affine_range_eval", "rm_affine_march_rays", "rm_affine_render",
     "rm_ssim_scores", "rm_capture", "rm_shade_frames", "rm_score_captures",
+    "rm_intrinsic_features", "rm_view_features",
 ]
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
@@ -185,6 +186,25 @@ class RmScoreResult(ctypes.Structure):
                                                "normal_mean_deg", "normal_p95_deg")]
 
 
+class RmIntrinsicFeatures(ctypes.Structure):
+    """One sample set's intrinsic features (include/rm_hip.h); slab_median is a length, not yet in box diagonals."""
+    _fields_ = [("lipschitz_p99", ctypes.c_double), ("slab_median", ctypes.c_double), ("n_finite", ctypes.c_int64),
+                ("n_slabs", ctypes.c_int64)]
+
+
+class RmViewMaps(ctypes.Structure):
+    """The host maps of one capture as rm_view_features reads them (include/rm_hip.h): float32 depth / normal / evals,
+    uint8 hit; all required."""
+    _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("evals", ctypes.c_void_p), ("hit", ctypes.c_void_p)]
+
+
+class RmViewFeatures(ctypes.Structure):
+    """One capture's view features (include/rm_hip.h)."""
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_hit", "n_grazing", "n_perimeter", "sum_evals")] + \
+               [(k, ctypes.c_double) for k in ("hit_rate", "grazing_frac", "silhouette_cplx", "hardness_mean", "hardness_cv")] + \
+               [("box_lo", ctypes.c_double * 3), ("box_hi", ctypes.c_double * 3)]
+
+
 class RmCaptureOutputs(ctypes.Structure):
     """The host maps rm_capture writes (include/rm_hip.h): float32 geom / normal / depth / color / evals, uint8 hit; any but
     hit may be NULL."""
@@ -295,6 +315,10 @@ def load() -> ctypes.CDLL:
                                  ctypes.POINTER(RmTiming)]
         L.rm_shade_frames.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, dp, vp, vp, vp, vp, vp,
                                       ctypes.POINTER(RmTiming)]
+        L.rm_intrinsic_features.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, dp, ctypes.c_double, ctypes.c_int32, dp, dp,
+                                            ctypes.c_int32, dp, ctypes.POINTER(RmIntrinsicFeatures), dp, vp, ctypes.POINTER(RmTiming)]
+        L.rm_view_features.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, dp, ctypes.POINTER(RmViewMaps),
+                                       ctypes.POINTER(RmViewFeatures), ctypes.POINTER(RmTiming)]
         for name in EXPORTS:
             if name not in ("rm_shutdown", "rm_last_error", "rm_stats_device_bytes", "rm_default_strategy_params"):
                 getattr(L, name).restype = ctypes.c_int
@@ -819,3 +843,71 @@ def shade_frames(scene_id: int, cams, hit, t=None, depth=None, warmup=0, repeats
     if tm is not None:
         out["timing"] = timing_dict(tm)
     return out
+
+
+def intrinsic_features(scene_id: int, pts, eps: float, chords, seglen, ts, details=False, warmup=0, repeats=0):
+    """rm_intrinsic_features: pts (nsets, n_lip, 3), chords (nsets, n_chords, 6), seglen (nsets, n_chords), ts (chord_steps)
+    -> one dict of RmIntrinsicFeatures' fields per set; with `details` also gmag (n_lip; NaN = left out) and slab_counts
+    (n_chords).  With repeats > 0 also the kernels' timing dict."""
+    L = init()
+    pts = np.ascontiguousarray(pts, np.float64)
+    chords = np.ascontiguousarray(chords, np.float64)
+    seglen = np.ascontiguousarray(seglen, np.float64)
+    ts = np.ascontiguousarray(ts, np.float64).reshape(-1)
+    if pts.ndim != 3 or pts.shape[2] != 3 or chords.ndim != 3 or chords.shape[2] != 6 or chords.shape[0] != pts.shape[0]:
+        raise ValueError(f"pts {pts.shape} / chords {chords.shape}: want (nsets, n_lip, 3) and (nsets, n_chords, 6)")
+    if seglen.shape != chords.shape[:2]:
+        raise ValueError(f"seglen has shape {seglen.shape}, not {chords.shape[:2]}")
+    nsets, n_lip, n_chords = pts.shape[0], pts.shape[1], chords.shape[1]
+    res = (RmIntrinsicFeatures * max(nsets, 1))()
+    gmag = np.empty((nsets, n_lip), np.float64) if details else None
+    counts = np.empty((nsets, n_chords), np.int32) if details else None
+    dp = ctypes.POINTER(ctypes.c_double)
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(dp)      # noqa: E731
+    tm = _timing(warmup, repeats)
+    check(L.rm_intrinsic_features(int(scene_id), nsets, n_lip, ptr(pts), float(eps), n_chords, ptr(chords), ptr(seglen), len(ts),
+                                  ptr(ts), res, ptr(gmag), None if counts is None or counts.size == 0 else _ptr(counts), _ref(tm)))
+    out = [{name: getattr(res[i], name) for name, _ in RmIntrinsicFeatures._fields_} for i in range(nsets)]
+    if details:
+        for i, r in enumerate(out):
+            r["gmag"], r["slab_counts"] = gmag[i], counts[i]
+    return (out, timing_dict(tm)) if tm is not None else out
+
+
+def view_maps(capture: dict, width: int, height: int):
+    """(RmViewMaps, the arrays it points into) of a capture dict: depth / normal / evals as contiguous float32, hit (non-zero
+    = hit) as uint8."""
+    shape = (int(height), int(width))
+    keep = [np.ascontiguousarray(capture["depth"], np.float32), np.ascontiguousarray(capture["normal"], np.float32),
+            np.ascontiguousarray(capture["evals"], np.float32), np.ascontiguousarray(np.asarray(capture["hit"]) != 0, np.uint8)]
+    for a, key, tail in zip(keep, ("depth", "normal", "evals", "hit"), ((), (3,), (), ())):
+        if a.shape != shape + tail:
+            raise ValueError(f"{key} has shape {a.shape}, not {shape + tail}")
+    return RmViewMaps(*[a.ctypes.data for a in keep]), keep
+
+
+def view_features(cams, captures, warmup=0, repeats=0):
+    """rm_view_features: one dict of RmViewFeatures' fields (int counts, float features, box_lo / box_hi as (3,) arrays) per
+    capture dict of `captures` (one frame size), seen by the cameras `cams` (n, 14).  With repeats > 0 also the timing dict."""
+    L = init()
+    n = len(captures)
+    cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 14)
+    if len(cams) != n:
+        raise ValueError(f"{len(cams)} cameras for {n} captures")
+    if n == 0:
+        return []
+    height, width = np.asarray(captures[0]["hit"]).shape
+    marr = (RmViewMaps * n)()
+    keep = []
+    for i, c in enumerate(captures):
+        marr[i], k = view_maps(c, width, height)
+        keep.append(k)
+    res = (RmViewFeatures * n)()
+    tm = _timing(warmup, repeats)
+    check(L.rm_view_features(int(width), int(height), n, cams.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), marr, res, _ref(tm)))
+    out = []
+    for i in range(n):
+        r = {name: getattr(res[i], name) for name, _ in RmViewFeatures._fields_[:9]}
+        r["box_lo"], r["box_hi"] = np.array(res[i].box_lo[:]), np.array(res[i].box_hi[:])
+        out.append(r)
+    return (out, timing_dict(tm)) if tm is not None else out

@@ -82,6 +82,11 @@ CEILINGS = ("segment",)
 # against the oracle capture's (ssim.py; the frame's normals as GPURunner.capture takes them, at its own hit points).  The
 # oracle captures carry no colour, so the two colour columns are empty cells, as are all four without an oracle capture.
 SSIM_FIELDS = list(scoring.SSIM_KEYS)
+# with features (run_sweep(features=True)): the strategy-independent discovery features of the row's (scene, viewpoint)
+# (features.py: five from a dense-march capture, two from samples of the scene's SDF in the box of the visible hit
+# points), the same seven values on every row of a scene and viewpoint
+FEATURE_FIELDS = ["feat_hit_rate", "feat_grazing_frac", "feat_silhouette_cplx", "feat_hardness_mean", "feat_hardness_cv",
+                  "feat_lipschitz_p99", "feat_thin_slab"]
 
 
 def build_levels(mode: str, *, budgets: Sequence[int] = DEFAULT_BUDGETS, epsilons: Sequence[float] = DEFAULT_EPSILONS,
@@ -239,6 +244,14 @@ def ssim_columns(scene, kept: List, oracle_frames: Dict[str, Optional[Dict]], de
             row.update(cols)
 
 
+def feature_columns_for(scene, width: int, height: int, rng: np.random.Generator) -> Dict[str, Dict]:
+    """FEATURE_FIELDS of every curated viewpoint of `scene`: one dense-march capture per viewpoint, one rm_view_features
+    call over all of them and one rm_intrinsic_features call with one sample set per viewpoint (features.scene_features)."""
+    from . import features
+    feats = features.scene_features(scene, width, height, rng)
+    return {vp.name: {"feat_" + k: f[k] for k in features.FEATURE_KEYS} for vp, f in zip(viewpoints_for(scene), feats)}
+
+
 def sound_scene(scene, twins: bool = False):
     """The scene the sound side evaluates for `scene`: the scene itself when it has an interval extension; with `twins`,
     the registered program twin (scene_program.register_twin) of a catalogue scene that has none but has a twin; else
@@ -302,7 +315,8 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
               out_path: Optional[str] = None, device_id: int = 0, verbose: bool = False, grid: bool = False,
               oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL,
               ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL, ssim: bool = False,
-              oracle_twins: bool = False, device_capture: bool = False, device_score: bool = False) -> List[Dict]:
+              oracle_twins: bool = False, device_capture: bool = False, device_score: bool = False, features: bool = False,
+              feature_seed: int = 0) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
@@ -320,7 +334,9 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     device_score=True (only with an oracle): ORACLE_FIELDS, and the residual behind CEILING_FIELDS when a ceiling is asked
     for, come from the device -- one rm_score_captures call per viewpoint over all of its rows (device_oracle_columns); the
     count-derived and percentile columns equal the host's, the means differ by summation order only.  Off, the output is
-    unchanged."""
+    unchanged.  features=True: every row also carries FEATURE_FIELDS, the discovery features of its (scene, viewpoint),
+    computed on the device once per scene (feature_columns_for); the samples are drawn from
+    np.random.default_rng(feature_seed), scene after scene, viewpoint after viewpoint.  Off, the output is unchanged."""
     if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
         raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
     if ceiling is not None and ceiling not in CEILINGS:
@@ -336,8 +352,10 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
               else [_need(registry.get_shader_strategy(n) or registry.get_strategy_by_name(n), "strategy", n) for n in strategy_names])
     levels = build_levels(mode, budgets=budgets, epsilons=epsilons, cap=cap, hit_threshold=hit_threshold)
     collector = HipCollector(MarchConfig(), device_id=device_id)
+    feature_rng = np.random.default_rng(feature_seed) if features else None
     rows: List[Dict] = []
     for scene in scenes:
+        first = len(rows)
         truth = (oracle_frames_for(scene, width, height, "interval", oracle_tol, oracle_twins)
                  if oracle is not None or ceiling is not None else None)
         ofr = truth if oracle is not None else None
@@ -356,6 +374,10 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
             device_oracle_columns(kept, ofr)
         if kept and ssim:
             ssim_columns(scene, kept, ofr, device_normals=device_capture)
+        if features:
+            fcols = feature_columns_for(scene, width, height, feature_rng)
+            for row in rows[first:]:
+                row.update(fcols[row["viewpoint"]])
     if out_path:
         write_rows(rows, out_path)
     return rows
@@ -367,7 +389,8 @@ def write_rows(rows: List[Dict], path: str) -> None:
             json.dump(rows, f, indent=1, ensure_ascii=False)
         return
     fields = ROW_FIELDS + (ORACLE_FIELDS if rows and "oracle_iou" in rows[0] else []) + \
-        (CEILING_FIELDS if rows and "ceiling_iou" in rows[0] else []) + (SSIM_FIELDS if rows and "depth_ssim" in rows[0] else [])
+        (CEILING_FIELDS if rows and "ceiling_iou" in rows[0] else []) + (SSIM_FIELDS if rows and "depth_ssim" in rows[0] else []) + \
+        (FEATURE_FIELDS if rows and "feat_hit_rate" in rows[0] else [])
     with open(path, "w", newline="", encoding="utf-8") as f:
         w = csv.DictWriter(f, fieldnames=fields)
         w.writeheader()
@@ -411,6 +434,9 @@ def main(argv=None) -> int:
                     help="with --oracle / --ceiling: score a catalogue scene that has no interval form against its program twin "
                          "(Menger, Bad Lipschitz Sphere, Bumpy Sphere, Gyroid, Box Lattice); a twin's ceiling is traced with l_global = the "
                          "scene's Lipschitz bound, not the default 1")
+    ap.add_argument("--features", action="store_true",
+                    help="add the discovery features of every row's (scene, viewpoint), computed on the device (the feat_* columns)")
+    ap.add_argument("--feature-seed", type=int, default=0, help="seed of the features' random samples")
     a = ap.parse_args(argv)
     if a.ssim and a.oracle is None:
         ap.error("--ssim needs --oracle")
@@ -424,7 +450,7 @@ def main(argv=None) -> int:
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
                      a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol,
                      ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim, oracle_twins=a.oracle_twins,
-                     device_capture=a.device_capture, device_score=a.device_score)
+                     device_capture=a.device_capture, device_score=a.device_score, features=a.features, feature_seed=a.feature_seed)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 
