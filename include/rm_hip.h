@@ -309,7 +309,13 @@ int rm_march_rays(int scene_id, int strategy_id, const RmMarchConfig* cfg, const
  * RM_SOP_GYROID is the one op that evaluates trigonometry on the device: sin and cos are the library's exact restatements
  * of glibc's for |q| < 105414336 (0x1.921fbp+26) and NaN for larger or non-finite arguments, so the op's value is NaN
  * there (the catalogue's Gyroid scene has the same limit).
- * Every result is bit-identical to the reference's functions (binary64, its evaluation order).
+ * RM_SOP_CAPPED_TORUS (and the catalogue's Capped Torus) is NaN where p.p + ra^2 - 2 ra k rounds below zero: on the centre
+ * circle of the tube the terms cancel to +-1 ulp, about one point in six of the circle comes out negative, the reference's
+ * `** 0.5` turns complex there and its caller raises TypeError; the library's pow returns NaN for a negative base.
+ * Cylinders (RM_SOP_CYLINDER, Cylinder, Pillar Forest): where a `** 2` leaves binary64 (a radial or axial distance of
+ * 2^512 = 1.34e154 or more) the reference raises OverflowError; the library returns what libm's pow makes of it, +inf.
+ * Every result the reference defines is bit-identical to its functions (binary64, its evaluation order); the edges of that
+ * arithmetic are pinned by tests/golden/sdf_edges.npz.
  * Ids of programs start at RM_SCENE_PROGRAM_BASE, increase monotonically and are never reused within a process.  A
  * program id is accepted by every frame entry point (rm_render*, rm_render_device, rm_bench_device, rm_render_batch*,
  * rm_march_rays, rm_sdf_eval, rm_gather_frame*) until it is destroyed; afterwards they return RM_E_BAD_SCENE.  A program

@@ -22,7 +22,7 @@ Layout of each frames_*.npz (keys prefixed "s{scene_id}_k{strategy_id}_"):
 frames_config_<family>.npz and rays_config.npz (--only config, --only rays) are laid out differently: see the
 comment above CONFIG_SEED.
 
-Usage:  python oracle/gen_golden.py [--only frames64|frames160|rows1080|sdf|stats|leak|leakseq|params|schema|viewpoints|evals|analytic|config|rays]
+Usage:  python oracle/gen_golden.py [--only frames64|frames160|rows1080|sdf|stats|leak|leakseq|params|schema|viewpoints|evals|analytic|config|rays|sdf_edges|ray_edges]
 """
 from __future__ import annotations
 
@@ -803,10 +803,326 @@ def gen_rays(jobs):
     save_npz(os.path.join(OUT, "rays_config.npz"), store)
 
 
+# ---- edge points of the scene SDFs -------------------------------------------------------------------------------------
+# sdf_edges.npz / rays_edges.npz: layout, conditions and coverage are in tests/sdf_edge_cases.py, whose check_fixture
+# runs here before anything is written.  A uniform draw (gen_sdf) never lands on a measure-zero edge; these do.
+EDGE_SEED = 20261020
+REGION = 3.5
+
+
+def _edge_constants():
+    """The lengths the catalogue is written with, read from its classes where they are attributes; the literals of its
+    sdf() bodies are listed.  Returns (constants, sphere centres, spheres as (centre, radius))."""
+    from raymarching_benchmark.scenes import catalog as C
+    cloud = [(tuple(c), r) for c, r in C.SphereCloudScene.SPHERES]
+    bumps = [(tuple(c), C.BumpySphereScene.BUMP_R) for c in C.BumpySphereScene.BUMPS]
+    balls = [(tuple(c), r) for c, r in C.MetaballsScene.BALLS]
+    single = [((0.0, 0.0, 0.0), r) for r in (1.0, 1.3, 2.0, C.BumpySphereScene.BASE_R, C.GyroidScene.RADIUS)]
+    single += [((-1.01, 0.0, 0.0), 1.0), ((1.01, 0.0, 0.0), 1.0), ((-0.5, 0.0, 0.0), 0.8)]
+    consts = {1.0, 0.5, 1.5, 0.05, 1.01, 1.3, 0.8, 0.6, 2.0, 0.1, 3.0, 0.15, 0.25, 0.01, 4.0, 2.5,
+              C.BumpySphereScene.BASE_R, C.BumpySphereScene.BUMP_R, C.GyroidScene.FREQ, C.GyroidScene.LIP, C.GyroidScene.RADIUS,
+              C.CappedTorusScene.RA, C.CappedTorusScene.RB, *C.CappedTorusScene.SC, C.BoxLatticeScene.C, C.BoxLatticeScene.L,
+              C.BoxLatticeScene.BB, C.MetaballsScene.K}
+    consts |= {r for _, r in cloud + balls}
+    return sorted(consts), cloud, bumps, balls, single
+
+
+def _rows(rng, rows):
+    """points from rows of three entries; None is a coordinate drawn uniformly from the region"""
+    a = rng.uniform(-REGION, REGION, size=(len(rows), 3))
+    for i, r in enumerate(rows):
+        for c in range(3):
+            if r[c] is not None:
+                a[i, c] = r[c]
+    return a
+
+
+def _with_neighbours(rng, a, share=0.5):
+    """the points, and a copy of `share` of them with every coordinate moved one nextafter down, up or not at all"""
+    pick = a[rng.random(len(a)) < share]
+    step = rng.integers(-1, 2, size=pick.shape)
+    return np.concatenate([a, np.nextafter(pick, np.where(step == 0, pick, np.where(step > 0, np.inf, -np.inf)))])
+
+
+def _from_pools(rng, n, pools, weights, p_take=0.6, nudge=1.0 / 3.0):
+    """The shared recipe: every coordinate is taken with probability p_take (at least one per point) from a pool chosen by
+    weight, the others are uniform in the region; a share of all coordinates is nudged one nextafter either way."""
+    a = rng.uniform(-REGION, REGION, size=(n, 3))
+    take = rng.random((n, 3)) < p_take
+    take[np.arange(n), rng.integers(0, 3, size=n)] = True
+    which = rng.choice(len(pools), size=(n, 3), p=weights)
+    for k, pool in enumerate(pools):
+        pool = np.asarray(pool, dtype=np.float64)
+        m = take & (which == k)
+        a[m] = pool[rng.integers(0, len(pool), size=int(m.sum()))]
+    step = rng.integers(0, 2, size=(n, 3)) * 2 - 1
+    m = rng.random((n, 3)) < nudge
+    a[m] = np.nextafter(a[m], step[m] * np.inf)
+    return a, take
+
+
+def _unit(rng, n):
+    u = rng.normal(size=(n, 3))
+    return u / np.linalg.norm(u, axis=1, keepdims=True)
+
+
+def edge_points():
+    """[(group name, points)] in fixture order"""
+    rng = np.random.default_rng(EDGE_SEED)
+    consts, cloud, bumps, balls, single = _edge_constants()
+    pi = float(np.pi)
+    signed = lambda v: [s * x for x in v for s in (1.0, -1.0)]                                    # noqa: E731
+    core = [0.0, -0.0, 5e-324, -5e-324, 1e-300, -1e-300, 1e-12, -1e-12, 1e-13] + signed(consts)
+    thirds = [k / s for s in (3.0, 9.0, 27.0) for k in range(-40, 41) if abs(k / s) <= REGION]
+    sixths = [j * pi / 6.0 for j in range(-6, 7)]
+    centres = [c for ctr, _ in cloud + bumps + balls for c in ctr]
+    big = [100.0, -100.0, 1e3, -1e3, 1e4, 1e6]
+    out = []
+    out.append(("shared", _from_pools(rng, 1300, [core, thirds, sixths, centres, big], [0.4, 0.2, 0.1, 0.2, 0.1])[0]))
+
+    # sphere-type scenes: every centre, and the surfaces along the axes (all six for the single spheres, two for the clouds)
+    rows = [ctr for ctr, _ in cloud + bumps + balls + single]
+    for n, (ctr, r) in enumerate(cloud + bumps + balls + single):
+        few = n < len(cloud) + len(bumps)
+        for ax in range(3):
+            for s in ((1.0, -1.0) if not few else ((1.0 if n % 2 else -1.0,) if (n + ax) % 3 else ())):
+                rows.append(tuple(ctr[c] + (s * r if c == ax else 0.0) for c in range(3)))
+    out.append(("spheres", _with_neighbours(rng, _rows(rng, rows), 0.3)))
+
+    # Near Miss: the tie plane x = +-0 (both spheres at one distance) and the +-0.01 gap
+    rows = [(z, None, None) for z in (0.0, -0.0) * 15] + [(z, y, w) for z in (0.0, -0.0) for y in (0.0, 1e-300, 0.5) for w in (0.0, -1e-12)]
+    rows += [(g, y, w) for g in (0.01, -0.01, 0.0) for y in (0.0, -0.0, 1e-13, 0.1) for w in (0.0, 0.05)]
+    out.append(("near_miss", _with_neighbours(rng, _rows(rng, rows))))
+
+    # planes: Grazing Plane's y = -0.5; Thin Planes' cell edges y = 0.25 + 0.5 k and sheets 0.5 k +- 0.01
+    rows = [(None, -0.5, None)] * 6 + [(0.0, -0.5, 0.0), (1e6, -0.5, -1e6)]
+    rows += [(None, 0.25 + 0.5 * k, None) for k in range(-8, 8) for _ in range(3)]
+    rows += [(None, 0.5 * k + s, None) for k in range(-7, 8) for s in (0.01, -0.01, 0.0)]
+    out.append(("planes", _with_neighbours(rng, _rows(rng, rows))))
+
+    # boxes: faces, edges, corners and the q-tie diagonals (|x| - h == |y| - h) of half-extents 1 (Cube, Hollow Cube,
+    # Menger), 0.6 about (0.5, 0, 0) (Smooth Blend) and 0.3 about a lattice node (Box Lattice)
+    rows = []
+    for h, ctr in ((1.0, (0.0, 0.0, 0.0)), (0.6, (0.5, 0.0, 0.0)), (0.3, (0.0, 0.0, 0.0)), (0.3, (1.0, -2.0, 2.0))):
+        inside = lambda c: ctr[c] + float(rng.uniform(-h, h))                                   # noqa: E731
+        sg = lambda: float(rng.choice((-1.0, 1.0)))                                             # noqa: E731
+        for _ in range(10):                                                                       # faces
+            ax = int(rng.integers(3))
+            rows.append(tuple(ctr[c] + sg() * h if c == ax else inside(c) for c in range(3)))
+        for _ in range(10):                                                                       # edges
+            ax = int(rng.integers(3))
+            rows.append(tuple(inside(c) if c == ax else ctr[c] + sg() * h for c in range(3)))
+        rows += [tuple(ctr[c] + (h if (k >> c) & 1 else -h) for c in range(3)) for k in range(8)]   # corners
+        for _ in range(18):                                                                       # diagonals: two or three equal |q|
+            e = float(rng.choice((0.0, 0.25, -0.25, 0.5, 2.0 ** -30, -0.125)))
+            three = rng.random() < 0.4
+            ax = int(rng.integers(3))
+            rows.append(tuple(inside(c) if (c == ax and not three) else ctr[c] + sg() * (h + e) for c in range(3)))
+    out.append(("boxes", _with_neighbours(rng, _rows(rng, rows), 0.4)))
+
+    # Thin Torus / Cylinder / Pillar Forest's cylinder: the axis, the caps y = +-1.5 and +-3, the rims
+    rows = [(z, None, w) for z in (0.0, -0.0) for w in (0.0, -0.0) for _ in range(4)]
+    rows += [(0.0, y, 0.0) for y in (0.0, -0.0, 1.5, -1.5, 3.0, -3.0, 0.05, 1e-300)]
+    rows += [(float(rng.uniform(-0.7, 0.7)), y, float(rng.uniform(-0.7, 0.7))) for y in (1.5, -1.5, 3.0, -3.0) for _ in range(6)]
+    rows += [(x, y, w) for y in (1.5, -1.5) for x, w in ((1.0, 0.0), (-1.0, 0.0), (0.0, 1.0), (0.0, -1.0), (0.6, 0.8), (-0.8, 0.6))]
+    rows += [(x, y, w) for y in (3.0, -3.0) for x, w in ((0.15, 0.0), (0.0, -0.15), (2.15, 2.0), (-2.0, 1.85))]
+    th = rng.uniform(-pi, pi, size=16)
+    rows += [(float(np.sin(t)), y, float(np.cos(t))) for t, y in zip(th, (1.5, -1.5) * 8)]
+    out.append(("torus_cyl", _with_neighbours(rng, _rows(rng, rows))))
+
+    # Thin Torus: the centre circle r = 1.5 of its tube
+    th = rng.uniform(-pi, pi, size=32)
+    rows = [(1.5 * float(np.sin(t)), y, 1.5 * float(np.cos(t))) for t, y in zip(th, (0.0, -0.0, 0.05, -0.05) * 8)]
+    rows += [(x, y, w) for x, w in ((1.5, 0.0), (-1.5, 0.0), (0.0, 1.5), (0.0, -1.5), (0.9, 1.2), (1.2, -0.9)) for y in (0.0, -0.0, 0.05)]
+    out.append(("thin_torus", _with_neighbours(rng, _rows(rng, rows))))
+
+    # Onion Shell: the shells 2, 2 +- 0.1, 2 +- 0.1 +- 0.05 along the axes and in random directions
+    radii = [2.0, 2.0 + 0.1, 2.0 - 0.1, 2.0 + 0.1 + 0.05, 2.0 + 0.1 - 0.05, 2.0 - 0.1 + 0.05, 2.0 - 0.1 - 0.05]
+    rows = [tuple(s * r if c == ax else 0.0 for c in range(3)) for r in radii for ax in range(3) for s in (1.0, -1.0)]
+    a = np.concatenate([_rows(rng, rows), _unit(rng, 56) * np.repeat(radii, 8)[:, None]])
+    out.append(("onion", _with_neighbours(rng, a)))
+
+    # Pillar Forest: cell edges at odd x, z (a zero remainder of `%`), pillar axes at even x, z
+    odd, even = (-3.0, -1.0, 1.0, 3.0, 101.0), (-2.0, 0.0, -0.0, 2.0, 100.0)
+    rows = [(float(rng.choice(odd)), None, None) for _ in range(15)] + [(None, None, float(rng.choice(odd))) for _ in range(15)]
+    rows += [(float(rng.choice(odd)), y, float(rng.choice(odd))) for y in (None, 3.0, -3.0, 0.0) for _ in range(4)]
+    rows += [(float(rng.choice(even)), y, float(rng.choice(even))) for y in (None, 3.0, -3.0, 0.0, None) for _ in range(5)]
+    rows += [(float(rng.choice(even)) + s, None, float(rng.choice(even))) for s in (0.15, -0.15) for _ in range(5)]
+    out.append(("pillars", _with_neighbours(rng, _rows(rng, rows))))
+
+    # Menger: p * s an even integer for s = 1, 3, 9 (the jump of `%`), and +-1 / (3 s) beside it (the fold of the cross)
+    planes = [v for s in (1.0, 3.0, 9.0) for k in range(-12, 13) for v in (2.0 * k / s, 2.0 * k / s + 1.0 / (3.0 * s), 2.0 * k / s - 1.0 / (3.0 * s))
+              if abs(v) <= 1.5 or (s == 1.0 and abs(v) <= REGION)]
+    out.append(("menger", _from_pools(rng, 220, [planes], [1.0], p_take=0.6, nudge=0.2)[0]))
+
+    # Box Lattice: the ties x = k + 0.5 of floor(x + 0.5), the clamps |x| = 2.5 and beyond
+    ties = [k + 0.5 for k in range(-4, 4)] + [2.5, -2.5, 2.6, -2.6, 3.2, -3.2, 3.5, -3.5, 100.0, -100.0, 2.2, -1.7, 0.3, -0.3, 1.3, 0.7]
+    out.append(("lattice", _from_pools(rng, 160, [ties], [1.0], p_take=0.6, nudge=0.2)[0]))
+
+    # Capped Torus: x = +-0 (the |x| kink), the branch line cos2 |x| = sin2 y, both arc ends
+    from raymarching_benchmark.scenes.catalog import CappedTorusScene as CT
+    s2, c2, ra, rb = CT.SC[0], CT.SC[1], CT.RA, CT.RB
+    rows = [(z, None, w) for z in (0.0, -0.0) for w in (None, 0.0, -0.0) for _ in range(6)]
+    rows += [(z, y, 0.0) for z in (0.0, -0.0) for y in (ra, -ra, ra + rb, ra - rb, 0.0, -0.0)]
+    xs = np.concatenate([rng.uniform(-REGION, REGION, size=24), [1e-300, -1e-300, 5e-324, ra * s2, -ra * s2, 1.0]])
+    rows += [(float(x), c2 * abs(float(x)) / s2, w) for x, w in zip(xs, (None, 0.0, -0.0) * 10)]
+    rows += [(sx * (ra + e) * s2, (ra + e) * c2, w) for sx in (1.0, -1.0) for e in (0.0, rb, -rb) for w in (0.0, rb, -0.0)]
+    out.append(("capped_torus", _with_neighbours(rng, _rows(rng, rows), 0.6)))
+    # ... and 200 points of the centre circle of its tube, where p.p + ra^2 - 2 ra k cancels to +-1 ulp: the reference goes
+    # complex where it rounds below zero
+    th = rng.uniform(-2.0, 2.0, size=200)
+    out.append(("ctorus_circle", np.stack([ra * np.sin(th), ra * np.cos(th), np.zeros(200)], axis=1)))
+
+    # Gyroid: 3 x a multiple of pi / 2, the ball r = 2.2, coordinates on both sides of the sincos cut 105414336 / 3
+    a, _ = _from_pools(rng, 60, [sixths], [1.0], p_take=0.7, nudge=0.3)
+    R = 2.2
+    rows = [tuple(s * R if c == ax else 0.0 for c in range(3)) for ax in range(3) for s in (1.0, -1.0)]
+    b = np.concatenate([_rows(rng, rows), _unit(rng, 24) * R])
+    cut = 105414336.0 / 3.0
+    near = [cut, -cut, float(np.nextafter(cut, 0.0)), float(np.nextafter(cut, np.inf)), -float(np.nextafter(cut, 0.0)), cut - 1.0, cut + 1.0,
+            cut - 0.125, 1e7, -3.5e7, 3.4e7]
+    c, _ = _from_pools(rng, 44, [near], [1.0], p_take=0.5, nudge=0.0)
+    out.append(("gyroid", np.concatenate([a, b, c])))
+
+    # Mandelbulb: the origin, |p| on both sides of the 1e-12 clamps, the poles x = y = 0, the atan2 cut y = +-0 with x < 0,
+    # x = +-0, and |p| = 1 and 4 (log r = 0, the bail-out) with neighbours on both sides
+    rows = [(0.0, 0.0, 0.0), (-0.0, 0.0, -0.0), (-0.0, -0.0, -0.0), (0.0, -0.0, 0.0)]
+    tiny = (1e-13, 9.99e-13, 1e-12, 1.0000001e-12, 2e-12, 5e-324, 1e-300, 1e-160, 1e-7)
+    rows += [tuple(s * m if c == ax else z for c in range(3)) for m in tiny for ax in range(3) for s, z in ((1.0, 0.0), (-1.0, -0.0))]
+    a = np.concatenate([_rows(rng, rows), _unit(rng, 24) * rng.choice(tiny, size=(24, 1))])
+    rows = [(zx, zy, z) for zx in (0.0, -0.0) for zy in (0.0, -0.0) for z in (0.5, -0.5, 1.0, -1.0, 1.1, 4.0, -4.0, 1e-12, None, None)]
+    rows += [(-abs(float(rng.uniform(0.05, 1.3))), zy, w) for zy in (0.0, -0.0) for w in (None, 0.0, -0.0, None, 0.3) for _ in range(3)]
+    rows += [(zx, None, w) for zx in (0.0, -0.0) for w in (None, 0.0, -0.0, None, 0.3) for _ in range(3)]
+    b = _rows(rng, rows)
+    b[len(rows) - 60:] = np.clip(b[len(rows) - 60:], -1.3, 1.3)
+    u = _unit(rng, 48)
+    ring = [u[k] * (rad * (1.0 + (k - 24) * 2.0 ** -50)) for rad in (1.0, 4.0) for k in range(48)]
+    for rad in (1.0, float(np.nextafter(1.0, 0.0)), float(np.nextafter(1.0, 2.0)), 4.0, float(np.nextafter(4.0, 0.0)), float(np.nextafter(4.0, 5.0))):
+        ring += [np.array(r) for r in ((rad, 0.0, 0.0), (0.0, -rad, 0.0), (0.0, 0.0, rad), (-rad, -0.0, 0.0), (0.0, 0.0, -rad))]
+    out.append(("mandelbulb", np.concatenate([a, b, np.array(ring)])))
+
+    # huge: the shared recipe with magnitudes whose square leaves binary64's range or precision
+    hugepool = [1e15, 2.0 ** 53, 1e100, 1e154, 1.4e154, 1e200, -1e200]
+    a, take = _from_pools(rng, 380, [hugepool, core], [0.75, 0.25], nudge=0.1)
+    none = ~(np.abs(a) >= 1e15).any(axis=1)
+    a[none, 0] = np.asarray(hugepool)[rng.integers(0, len(hugepool), size=int(none.sum()))]
+    out.append(("huge", a))
+    return out
+
+
+def _ref_sdf(scene, p):
+    """(value, None) or (0.0, the exception's name); a complex value is the TypeError float() would raise"""
+    try:
+        v = scene.sdf(Vec3(float(p[0]), float(p[1]), float(p[2])))
+        if isinstance(v, complex):
+            return 0.0, "TypeError(complex)"
+        return float(v), None
+    except (OverflowError, TypeError, ValueError, ZeroDivisionError) as e:
+        return 0.0, type(e).__name__
+
+
+def _edge_cases_module():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import sdf_edge_cases
+    return sdf_edge_cases
+
+
+def gen_sdf_edges():
+    ec = _edge_cases_module()
+    groups = edge_points()
+    names = [g for g, _ in groups]
+    pts = np.ascontiguousarray(np.concatenate([a for _, a in groups]), dtype=np.float64)
+    group = np.concatenate([np.full(len(a), i, dtype=np.int16) for i, (_, a) in enumerate(groups)])
+    assert np.isfinite(pts).all()
+    store = {"pts": pts, "group": group, "group_names": np.array(names)}
+    want, raised = {}, {}
+    for sid, scene in enumerate(SCENES):
+        res = [_ref_sdf(scene, p) for p in pts]
+        want[sid] = np.array([v for v, _ in res], dtype=np.float64)
+        raised[sid] = np.array([e is not None for _, e in res], dtype=bool)
+        kinds = {}
+        for _, e in res:
+            if e:
+                kinds[e] = kinds.get(e, 0) + 1
+        print(f"  [sdf_edges] {scene.name}: raised {int(raised[sid].sum())} {kinds}, NaN {int(np.isnan(want[sid]).sum())}, "
+              f"-0.0 {int(((want[sid] == 0.0) & np.signbit(want[sid]) & ~raised[sid]).sum())}", flush=True)
+        store[f"s{sid}"] = want[sid]
+        store[f"raised_s{sid}"] = raised[sid]
+    store["unclaimed_s16"] = ec.unclaimed_gyroid(pts)
+    cov = ec.check_fixture(pts, group, names, want, raised)
+    print(f"  [sdf_edges] {len(pts)} points, groups {dict(zip(names, np.bincount(group).tolist()))}")
+    print(f"  [sdf_edges] coverage {cov}; minima {ec.MINIMA}")
+    assert all(cov[k] >= v for k, v in ec.MINIMA.items()), (cov, ec.MINIMA)
+    path = os.path.join(OUT, "sdf_edges.npz")
+    save_npz(path, store)
+    assert os.path.getsize(path) <= min(ec.LARGEST_FIXTURE_BEFORE, 1 << 20), os.path.getsize(path)
+    print(f"  [sdf_edges] {os.path.getsize(path)} bytes")
+
+
+def edge_rays(n=240):
+    """Origins among the edge points of the non-huge groups where no scene's reference value is missing, every group met;
+    directions by turns random, along an axis and aimed at the origin."""
+    ec = _edge_cases_module()
+    E = ec.Edges(np.load(os.path.join(OUT, "sdf_edges.npz")))
+    rng = np.random.default_rng(EDGE_SEED + 1)
+    ok = ~E.in_group("huge", "ctorus_circle")
+    for sid in range(len(SCENES)):
+        ok &= E.pinned(sid)
+    ok &= (np.abs(E.pts) <= 1e4).all(axis=1)
+    gids = [g for g in range(len(E.names)) if (ok & (E.group == g)).any()]
+    o = []
+    for k in range(n):
+        cand = np.flatnonzero(ok & (E.group == gids[k % len(gids)]))
+        o.append(E.pts[cand[rng.integers(len(cand))]])
+    o = np.array(o)
+    d = _unit(rng, n)
+    for k in range(n):
+        if k % 3 == 1:
+            d[k] = 0.0
+            d[k, (k // 3) % 3] = 1.0 if (k // 9) % 2 else -1.0
+        elif k % 3 == 2 and np.abs(o[k]).sum() > 1e-6:
+            d[k] = -o[k]                                  # un-normalised: Ray.__init__ normalises
+    return np.ascontiguousarray(o), np.ascontiguousarray(d)
+
+
+def run_edge_cells(sid):
+    from raymarching_benchmark.core.ray import Ray
+    ec = _edge_cases_module()
+    scene = SCENES[sid]
+    o, d = edge_rays()
+    sha = np.zeros((len(STRAT_KEYS), len(ec.BUDGETS), 32), dtype=np.uint8)
+    lips = np.zeros(len(STRAT_KEYS))
+    for kid in range(len(STRAT_KEYS)):
+        for bi, b in enumerate(ec.BUDGETS):
+            strategy, lip, _ = build_strategy(scene, kid, {}, None, None)
+            lips[kid] = lip
+            mc = MarchConfig(max_iterations=b)
+            res = [strategy.march(Ray(Vec3(*oi), Vec3(*di)), scene.sdf, mc) for oi, di in zip(o.tolist(), d.tolist())]   # a raise fails the run
+            assert all(isinstance(r.t, float) and isinstance(r.final_sdf, float) for r in res), (sid, kid, b)
+            sha[kid, bi] = np.frombuffer(ec.cell_hash(np.array([bool(r.hit) for r in res]), np.array([r.iterations for r in res]),
+                                                      np.array([r.t for r in res]), np.array([r.final_sdf for r in res])), dtype=np.uint8)
+    return sid, sha, lips
+
+
+def gen_ray_edges(jobs):
+    """rays_edges.npz: every scene x strategy x budget 0..3 marched by the reference's own march() from edge points; budget 0
+    makes final_sdf the SDF at the origin itself, for every strategy."""
+    import multiprocessing
+    ec = _edge_cases_module()
+    o, d = edge_rays()
+    sha = np.zeros((len(SCENES), len(STRAT_KEYS), len(ec.BUDGETS), 32), dtype=np.uint8)
+    lip = np.zeros((len(SCENES), len(STRAT_KEYS)))
+    with multiprocessing.Pool(jobs) as pool:
+        for sid, s, l in pool.imap(run_edge_cells, range(len(SCENES))):
+            sha[sid], lip[sid] = s, l
+            print(f"  [ray_edges] {SCENES[sid].name}: {s.shape[0] * s.shape[1]} cells of {len(o)} rays", flush=True)
+    save_npz(os.path.join(OUT, "rays_edges.npz"), {"o": o, "d": d, "lip": lip, "budgets": np.array(ec.BUDGETS, dtype=np.int32), "sha": sha})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="all")
-    ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1), help="worker processes of --only config / rays")
+    ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1), help="worker processes of --only config / rays / ray_edges")
     a = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     all_pairs = [(s, k) for s in range(len(SCENES)) for k in range(len(STRAT_KEYS))]
@@ -839,6 +1155,10 @@ def main():
         gen_config(a.jobs)
     if a.only in ("all", "rays"):
         gen_rays(a.jobs)
+    if a.only in ("all", "sdf_edges"):
+        gen_sdf_edges()
+    if a.only in ("all", "ray_edges"):
+        gen_ray_edges(a.jobs)
     if a.only in ("all", "small"):
         # max_iterations=100, 16x12: the configuration of the reference's own smoke test
         # (tests/test_smoke.py:31-43), every registry key on the Sphere.

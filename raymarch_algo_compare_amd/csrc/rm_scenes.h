@@ -36,7 +36,12 @@ RM_HD double sd_cylinder(vec3 p, double radius, double half_height)             
     double d_radial = pow_half(p.x * p.x + p.z * p.z) - radius;
     double d_height = rm_fabs(p.y) - half_height;
     double outside = pow_half(rm_pow(py_max(d_radial, 0.0), 2.0) + rm_pow(py_max(d_height, 0.0), 2.0));
-    double inside = py_min(py_max(d_radial, d_height), 0.0);
+    double larger = py_max(d_radial, d_height);
+    // A `** 2` that leaves binary64: the reference raises OverflowError, libm's pow returns +inf (exactly from 2^512 on: the
+    // square of the double below it is finite and more than an ulp away from rounding up) and the distance is +inf, while
+    // rm_pow claims nothing for 512 <= |y log x| (rm_math_pow.h).  The one compare makes the value libm's there.
+    outside = (larger >= 0x1p512) ? __builtin_inf() : outside;
+    double inside = py_min(larger, 0.0);
     return outside + inside;
 }
 
