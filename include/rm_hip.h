@@ -806,14 +806,16 @@ typedef struct RmIntrinsicFeatures {
  * build of csrc/rm_features.h reproduces them from the same SDF values.  `timing` (optional) times the kernels without the
  * copies.  Limits: nsets in [1, 256], n_lip in [0, 65536], n_chords in [0, 4096], chord_steps in [2, 1024]; n_lip == 0 and
  * n_chords == 0 are valid and give NaN and a count of 0.  Checked before the device is touched: RM_E_BAD_ARG for an
- * argument out of range, a lip_eps that is not finite and positive or a NULL required pointer; RM_E_BAD_SCENE for an
+ * argument out of range, a lip_eps that is not finite and positive, a NULL required pointer or a seglen element that is
+ * NaN or has its sign bit set (a length: +inf is valid; the message names the index); RM_E_BAD_SCENE for an
  * unknown or destroyed scene id. */
 int rm_intrinsic_features(int scene_id, int32_t nsets, int32_t n_lip, const double* pts, double lip_eps, int32_t n_chords,
                           const double* chords, const double* seglen, int32_t chord_steps, const double* ts, RmIntrinsicFeatures* out,
                           double* gmag_out, int32_t* slab_counts_out, RmTiming* timing);
 
 /* The maps of one width x height capture as rm_capture writes them, row-major HOST arrays, all required: depth (W*H),
- * normal (W*H*3, interleaved), evals (W*H) as floats; hit (W*H bytes, non-zero = hit). */
+ * normal (W*H*3, interleaved), evals (W*H) as floats; hit (W*H bytes, non-zero = hit).  evals are counts, integers in
+ * [0, 2^24]: a NaN or a negative value is read as 0, a value above 2^24 (+inf too) as 2^24, any other is truncated. */
 typedef struct RmViewMaps {
     const float* depth;
     const float* normal;
@@ -824,7 +826,8 @@ typedef struct RmViewMaps {
  * 4-neighbour (a neighbour beyond the image is a non-hit); sum_evals over the hits.  hit_rate = n_hit / (W * H),
  * grazing_frac = n_grazing / n_hit, silhouette_cplx = n_perimeter / sqrt(n_hit), hardness_mean = sum_evals / n_hit,
  * hardness_cv = population standard deviation of evals over the hits / hardness_mean (0 for a mean of 0); all four 0
- * without a hit.  box_lo / box_hi: per-axis min / max of the hit points origin + depth * ray (+inf / -inf without a hit). */
+ * without a hit.  box_lo / box_hi: per-axis min / max of the hit points origin + depth * ray (+inf / -inf without a hit);
+ * an axis over which any hit point's coordinate is NaN is NaN (0x7ff8000000000000) in both. */
 typedef struct RmViewFeatures {
     int64_t n_hit, n_grazing, n_perimeter, sum_evals;
     double hit_rate, grazing_frac, silhouette_cplx, hardness_mean, hardness_cv;

@@ -2504,6 +2504,7 @@ int rm_intrinsic_features(int scene_id, int32_t nsets, int32_t n_lip, const doub
 {
     if (const char* why = rm::feat_check_intrinsic(nsets, n_lip, pts, lip_eps, n_chords, chords, seglen, chord_steps, ts, out))
         return fail(RM_E_BAD_ARG, "rm_intrinsic_features: %s", why);
+    if (const char* why = rm::feat_check_seglen(nsets, n_chords, seglen)) return fail(RM_E_BAD_ARG, "rm_intrinsic_features: %s", why);
     int rc = check_scene(scene_id);
     if (rc || (timing && (rc = check_timing(timing)))) return rc;
     Entry e;

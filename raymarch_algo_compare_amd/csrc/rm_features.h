@@ -16,7 +16,8 @@
 //   (double)(end - start) * (seglen / (double)(chord_steps - 1)).  A chord has at most ceil(chord_steps / 2) runs; run r of
 //   chord c of set s sits in slot (s * n_chords + c) * feat_max_runs(chord_steps) + r, the chord's count beside it.
 //   slab_median = np.median of all run lengths of the set (not divided by the box diagonal: the caller does that).
-//   Both samples are non-negative, so their bit patterns order as uint64 (score_key).  An empty sample gives the one quiet
+//   Both samples are non-negative (seglen is a length: an element that is NaN or has its sign bit set is refused, +inf is
+//   valid), so their bit patterns order as uint64 (score_key).  An empty sample gives the one quiet
 //   NaN 0x7ff8000000000000 and a count of 0.
 //
 // View features, per capture of width x height pixels (depth, normal xyz, evals as binary32; hit bytes, non-zero = hit),
@@ -24,6 +25,13 @@
 //   n_hit; n_grazing: hit and |(rd.x * (double)n.x + rd.y * (double)n.y) + rd.z * (double)n.z| < 0.20; n_perimeter: hit with
 //   a non-hit 4-neighbour, a neighbour beyond the image being a non-hit; sum_evals: the exact integer sum of evals over hits;
 //   box: per-axis min / max of o + (double)depth * rd over hits (+inf / -inf without a hit).
+//   Evals are counts: integers in [0, 2^24], every one of which a binary32 holds.  feat_evals_count turns the float into the
+//   integer that is summed, averaged and deviated from: a NaN or a negative value is 0, a value above 2^24 (+inf too) is
+//   2^24, anything else is truncated; a count keeps every bit.  (The reference reads evals from its own integer map and
+//   has no treatment of other values.)
+//   A box axis over which any hit point's coordinate is NaN -- a NaN depth, or an infinite one times a zero ray component --
+//   is the quiet NaN 0x7ff8000000000000 in box_lo and in box_hi, wherever the pixel sits (NumPy's min / max); feat_box_min
+//   and feat_box_max are the one statement of it, for a tile's fold, the fold over tiles and the host build's loop.
 //   hit_rate = n_hit / (W * H); grazing_frac = n_grazing / n_hit; silhouette_cplx = n_perimeter / sqrt(n_hit);
 //   hardness_mean = sum_evals / n_hit (exact sum, one rounding: what np.mean gives while the sum is below 2^53);
 //   hardness_cv = sqrt(sum((evals - mean)^2) / n_hit) / mean, 0 when the mean is 0; all four 0 without a hit.
@@ -33,6 +41,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "rm_camera.h"
 #include "rm_score.h"         // score_key, the rank rules, the tile helpers
@@ -88,6 +97,20 @@ inline const char* feat_check_intrinsic(int32_t nsets, int32_t n_lip, const doub
     if (n_lip > 0 && !pts) return "pts is NULL";
     if (n_chords > 0 && (!chords || !seglen)) return "chords or seglen is NULL";
     if (!ts) return "ts is NULL";
+    return nullptr;
+}
+
+// The second half of rm_intrinsic_features' argument check, for arguments feat_check_intrinsic has passed: it reads the
+// nsets x n_chords lengths.  seglen is a length: the key order needs a clear sign bit (-0.0 is refused with the negatives)
+// and a NaN has no place in it; +inf is a length.  The reason names the first refused element.
+inline const char* feat_check_seglen(int32_t nsets, int32_t n_chords, const double* seglen)
+{
+    for (size_t i = 0; i < (size_t)nsets * (size_t)n_chords; ++i)
+        if (score_key(seglen[i]) > 0x7ff0000000000000ull) {
+            static thread_local char why[64];
+            snprintf(why, sizeof why, "seglen[%zu] is NaN or negative", i);
+            return why;
+        }
     return nullptr;
 }
 
@@ -200,9 +223,18 @@ RM_HD double feat_statistic(int sel, uint64_t lo, uint64_t hi, int64_t n)
 
 struct ViewPixel {
     bool hit, grazing, perimeter;
-    double evals;              // on a hit, else 0
+    int64_t evals;             // on a hit, else 0
     double p[3];               // the hit point
 };
+
+constexpr int64_t kFeatMaxEvals = 1 << 24;
+
+// the count a pixel's evals stand for (the header comment): a NaN fails both comparisons
+RM_HD int64_t feat_evals_count(float evals) { return evals >= (float)kFeatMaxEvals ? kFeatMaxEvals : evals >= 0.0f ? (int64_t)evals : 0; }
+
+// one step of a box corner's fold; a NaN on either side stays
+RM_HD double feat_box_min(double m, double p) { return m != m || p != p ? feat_nan() : (p < m ? p : m); }
+RM_HD double feat_box_max(double m, double p) { return m != m || p != p ? feat_nan() : (p > m ? p : m); }
 
 RM_HD ViewPixel feat_view_pixel(const ViewMaps& m, const CameraParams& cam, int width, int height, int x, int y)
 {
@@ -210,7 +242,8 @@ RM_HD ViewPixel feat_view_pixel(const ViewMaps& m, const CameraParams& cam, int 
     ViewPixel px;
     px.hit = m.hit[i] != 0;
     px.grazing = px.perimeter = false;
-    px.evals = px.p[0] = px.p[1] = px.p[2] = 0.0;
+    px.evals = 0;
+    px.p[0] = px.p[1] = px.p[2] = 0.0;
     if (!px.hit) return px;
     vec3 o, rd;
     camera_ray(cam, width, height, x, y, o, rd);
@@ -218,7 +251,7 @@ RM_HD ViewPixel feat_view_pixel(const ViewMaps& m, const CameraParams& cam, int 
     px.grazing = rm_fabs(cosine) < kFeatGrazingCos;
     px.perimeter = x == 0 || y == 0 || x == width - 1 || y == height - 1 || !m.hit[i - 1] || !m.hit[i + 1] ||
                    !m.hit[i - (size_t)width] || !m.hit[i + (size_t)width];
-    px.evals = (double)m.evals[i];
+    px.evals = feat_evals_count(m.evals[i]);
     const double t = (double)m.depth[i];
     px.p[0] = o.x + t * rd.x; px.p[1] = o.y + t * rd.y; px.p[2] = o.z + t * rd.z;
     return px;

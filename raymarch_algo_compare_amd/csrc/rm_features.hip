@@ -11,7 +11,8 @@
 //                         (score_next_rank); the p99 of gmag and the median of the run lengths
 // View features:
 //   view_tile_kernel      one workgroup per (tile, view), one pixel per thread: the pixel's flags (ballot + popcount per
-//                         wave), its evals as an integer, the hit point's box; per-tile integers and boxes into fixed slots
+//                         wave), its evals as a count (feat_evals_count), the hit point's box (feat_box_min / _max: a NaN
+//                         coordinate stays); per-tile integers and boxes into fixed slots
 //   view_mean_kernel      one workgroup per view: the tiles' integers and boxes in tile order; the mean of evals
 //   view_var_kernel       one workgroup per (tile, view): (evals - mean)^2 folded by halves into the tile's partial sum
 //   view_finish_kernel    one thread per view: the partial sums in tile order, feat_view_combine
@@ -200,7 +201,8 @@ __global__ __launch_bounds__(kSsimTile) void view_tile_kernel(ViewLaunch a)
     const int x = (tile % tiles_x) * kSsimTileW + t % kSsimTileW, y = (tile / tiles_x) * kSsimTileH + t / kSsimTileW;
     ViewPixel px;
     px.hit = px.grazing = px.perimeter = false;
-    px.evals = px.p[0] = px.p[1] = px.p[2] = 0.0;
+    px.evals = 0;
+    px.p[0] = px.p[1] = px.p[2] = 0.0;
     if (x < a.width && y < a.height) px = feat_view_pixel(a.maps[v], a.cams[v], a.width, a.height, x, y);
 
     __shared__ int cnt[3][kSsimTile / 64];
@@ -212,7 +214,7 @@ __global__ __launch_bounds__(kSsimTile) void view_tile_kernel(ViewLaunch a)
         const unsigned long long b = __ballot(flags[c]);
         if ((t & 63) == 0) cnt[c][t >> 6] = __popcll(b);
     }
-    ev[t] = (long long)px.evals;
+    ev[t] = px.evals;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         lo[j][t] = px.hit ? px.p[j] : feat_inf(false);
@@ -224,8 +226,8 @@ __global__ __launch_bounds__(kSsimTile) void view_tile_kernel(ViewLaunch a)
             ev[t] += ev[t + h];
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                lo[j][t] = lo[j][t + h] < lo[j][t] ? lo[j][t + h] : lo[j][t];
-                hi[j][t] = hi[j][t + h] > hi[j][t] ? hi[j][t + h] : hi[j][t];
+                lo[j][t] = feat_box_min(lo[j][t], lo[j][t + h]);
+                hi[j][t] = feat_box_max(hi[j][t], hi[j][t + h]);
             }
         }
         __syncthreads();
@@ -253,7 +255,7 @@ __global__ __launch_bounds__(64) void view_mean_kernel(ViewLaunch a)
         double* b = box + (size_t)(t - kViewCounts) * ntiles;
         const bool low = t - kViewCounts < 3;
         double m = b[0];
-        for (int i = 1; i < ntiles; ++i) m = low ? (b[i] < m ? b[i] : m) : (b[i] > m ? b[i] : m);
+        for (int i = 1; i < ntiles; ++i) m = low ? feat_box_min(m, b[i]) : feat_box_max(m, b[i]);
         b[0] = m;
     }
     __syncthreads();
@@ -271,7 +273,7 @@ __global__ __launch_bounds__(kSsimTile) void view_var_kernel(ViewLaunch a)
         const size_t i = (size_t)y * (size_t)a.width + (size_t)x;
         const ViewMaps m = a.maps[v];
         if (m.hit[i]) {
-            const double d = (double)m.evals[i] - a.mean[v];
+            const double d = (double)feat_evals_count(m.evals[i]) - a.mean[v];
             d2 = d * d;
         }
     }

@@ -251,6 +251,8 @@ def view_features_numpy(capture: Dict, camera) -> Dict:
     out["n_perimeter"] = int((hit & ~interior).sum())
     out["silhouette_cplx"] = out["n_perimeter"] / float(np.sqrt(n_hit))
     ev = np.asarray(capture["evals"])[hit].astype(np.float64)
+    with np.errstate(invalid="ignore"):      # evals are counts (rm_features.h): NaN and negatives 0, above 2^24 2^24, truncated
+        ev = np.trunc(np.clip(np.where(np.isnan(ev), 0.0, ev), 0.0, float(1 << 24)))
     m = float(ev.mean())
     out["sum_evals"] = int(ev.sum())
     out["hardness_mean"] = m

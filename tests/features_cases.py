@@ -72,6 +72,8 @@ class Host:
         i32, vp = ctypes.c_int32, ctypes.c_void_p
         L.rmft_check_intrinsic.argtypes = [i32, i32, vp, ctypes.c_double, i32, vp, vp, i32, vp, vp]
         L.rmft_check_intrinsic.restype = ctypes.c_char_p
+        L.rmft_check_seglen.argtypes = [i32, i32, vp]
+        L.rmft_check_seglen.restype = ctypes.c_char_p
         L.rmft_num_points.argtypes = [ctypes.c_int] * 4
         L.rmft_num_points.restype = ctypes.c_size_t
         L.rmft_points.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double, dp, dp, dp, dp]

@@ -50,6 +50,9 @@ const char* rmft_check_intrinsic(int32_t nsets, int32_t n_lip, const double* pts
     return feat_check_intrinsic(nsets, n_lip, pts, lip_eps, n_chords, chords, seglen, chord_steps, ts, out);
 }
 
+// ... and of its lengths, which rm_intrinsic_features checks once the arguments above are in order
+const char* rmft_check_seglen(int32_t nsets, int32_t n_chords, const double* seglen) { return feat_check_seglen(nsets, n_chords, seglen); }
+
 size_t rmft_num_points(int nsets, int n_lip, int n_chords, int steps) { return feat_lip_points(nsets, n_lip) + feat_chord_points(nsets, n_chords, steps); }
 
 // the xyz buffer of a call: 3 doubles per point
@@ -153,9 +156,9 @@ int rmft_view(int W, int H, const double* cam14, const float* depth, const float
         for (int x = 0; x < W; ++x) {
             const ViewPixel px = feat_view_pixel(m, cam, W, H, x, y);
             counts[VC_HIT] += px.hit; counts[VC_GRAZING] += px.grazing; counts[VC_PERIMETER] += px.perimeter;
-            counts[VC_EVALS] += (long long)px.evals;
+            counts[VC_EVALS] += px.evals;
             if (!px.hit) continue;
-            for (int j = 0; j < 3; ++j) { lo[j] = px.p[j] < lo[j] ? px.p[j] : lo[j]; hi[j] = px.p[j] > hi[j] ? px.p[j] : hi[j]; }
+            for (int j = 0; j < 3; ++j) { lo[j] = feat_box_min(lo[j], px.p[j]); hi[j] = feat_box_max(hi[j], px.p[j]); }
         }
     const double mean = counts[VC_HIT] ? feat_mean_evals(counts[VC_EVALS], counts[VC_HIT]) : 0.0;
     std::vector<double> part((size_t)tx * ty);
@@ -166,7 +169,7 @@ int rmft_view(int W, int H, const double* cam14, const float* depth, const float
             const int x = x0 + i % kSsimTileW, y = y0 + i / kSsimTileW;
             v[i] = 0.0;
             if (x >= W || y >= H || !hit[(size_t)y * W + x]) continue;
-            const double d = (double)evals[(size_t)y * W + x] - mean;
+            const double d = (double)feat_evals_count(evals[(size_t)y * W + x]) - mean;
             v[i] = d * d;
         }
         part[t] = ssim_fold(v);

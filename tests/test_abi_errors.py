@@ -139,6 +139,14 @@ def _cpu_rows():
     add("long_ray_marks: NULL", lambda L: L.rm_long_ray_marks(None), BAD_ARG, "NULL output")
     add("runtime_info: NULL", lambda L: L.rm_runtime_info(None), BAD_ARG, "out is NULL")
     add("comm_destroy: nothing to destroy", lambda L: L.rm_comm_destroy(), OK, None)
+    # rm_intrinsic_features: seglen is a length (csrc/rm_features.h); 2 sets of 3 chords, the message names the element
+    ts, res = np.linspace(0.0, 1.0, 160), (_native.RmIntrinsicFeatures * 2)()
+    for what, i, v in (("NaN", 4, math.nan), ("negative", 5, -1.0), ("-0.0", 0, -0.0), ("-inf", 2, -math.inf)):
+        seg = np.ones(6)
+        seg[i] = v
+        add(f"intrinsic_features: seglen {what}",
+            lambda L, seg=seg: L.rm_intrinsic_features(0, 2, 4, B.p("a"), 1e-4, 3, B.p("b"), seg.ctypes.data_as(dp), 160, ts.ctypes.data_as(dp),
+                                                       res, None, None, None), BAD_ARG, f"rm_intrinsic_features: seglen[{i}] is NaN or negative")
     return rows
 
 

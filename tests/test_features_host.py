@@ -16,6 +16,7 @@ import pytest
 
 import features_cases as C
 from conftest import ROOT
+from features_edge_cases import numpy_runs, sign_patterns
 from oracle import oracle
 from raymarch_algo_compare_amd import _native, features, sweep
 
@@ -90,37 +91,6 @@ def test_points_are_numpy_s(host):
 
 
 # ---- 2. run detection --------------------------------------------------------------------------------------------------------
-
-def numpy_runs(inside, seglen):
-    """the reference's expressions"""
-    inside = np.asarray(inside, bool)
-    steps = len(inside)
-    if not inside.any():
-        return np.empty(0)
-    d = np.diff(inside.astype(np.int8))
-    starts, ends = np.where(d == 1)[0] + 1, np.where(d == -1)[0] + 1
-    if inside[0]:
-        starts = np.r_[0, starts]
-    if inside[-1]:
-        ends = np.r_[ends, steps]
-    step_len = seglen / (steps - 1)
-    return np.array([(e - s) * step_len for s, e in zip(starts, ends)])
-
-
-def sign_patterns(steps):
-    rng = np.random.default_rng(steps)
-    idx = np.arange(steps)
-    out = [("all inside", np.ones(steps, bool)), ("none inside", np.zeros(steps, bool)), ("alternating from 0", idx % 2 == 0),
-           ("alternating from 1", idx % 2 == 1), ("both ends", (idx < 1) | (idx >= steps - 1)),
-           ("both ends wide", (idx < steps // 3) | (idx >= steps - steps // 4)), ("first only", idx == 0), ("last only", idx == steps - 1),
-           ("random", rng.random(steps) < 0.5), ("sparse", rng.random(steps) < 0.1), ("dense", rng.random(steps) < 0.9)]
-    for edge in (64, 128):
-        if steps > edge:
-            out += [(f"across {edge - 1}/{edge}", (idx >= edge - 1) & (idx <= edge)), (f"ends at {edge - 1}", (idx >= edge - 3) & (idx < edge)),
-                    (f"starts at {edge}", (idx >= edge) & (idx < edge + 2)), (f"long across {edge}", (idx >= 5) & (idx < steps - 2)),
-                    (f"one at {edge - 1} one at {edge + 1}", (idx == edge - 1) | (idx == edge + 1))]
-    return out
-
 
 @pytest.mark.parametrize("steps", [2, 3, 63, 64, 65, 127, 128, 129, 160, 1023, 1024])
 def test_runs_on_sign_patterns(host, steps):
@@ -252,6 +222,21 @@ def test_limits_are_the_header_s(host):
                 dict(steps=1025), dict(eps=0.0), dict(eps=-1e-4), dict(eps=float("nan")), dict(eps=float("inf")), dict(pts=None),
                 dict(chords=None), dict(seglen=None), dict(ts=None), dict(out=None)):
         assert why(**bad), bad
+
+    # the lengths, which the call checks once the arguments above are in order (feat_check_seglen): NaN or a set sign bit is
+    # refused and the element named; +inf, 0 and a subnormal are lengths
+    def lengths(nsets, n_chords, i=0, v=1.0, n=None):
+        a = np.ones(nsets * n_chords if n is None else n)
+        a[i] = v
+        return host.L.rmft_check_seglen(nsets, n_chords, a.ctypes.data)
+    for v in (1.0, np.inf, 0.0, 5e-324, 1e308):
+        assert lengths(1, 2, 1, v) is None, v
+    for i, v in ((0, np.nan), (1, -1.0), (1, -0.0), (0, -np.inf), (1, -np.nan), (0, -5e-324)):
+        assert lengths(1, 2, i, v) == f"seglen[{i}] is NaN or negative".encode(), (i, v)
+    assert lengths(3, 5, 14, np.nan) == b"seglen[14] is NaN or negative"
+    assert lengths(256, 4096, 256 * 4096 - 1, -1.0) == f"seglen[{256 * 4096 - 1}] is NaN or negative".encode()
+    assert lengths(3, 4, 14, np.nan, n=15) is None                               # beyond nsets x n_chords: not read
+    assert lengths(1, 0, 0, np.nan, n=1) is None and host.L.rmft_check_seglen(1, 0, None) is None      # no chord: no length
 
 
 def test_argument_checks_answer_without_a_device():
