@@ -463,6 +463,39 @@ int rm_affine_march_rays(int scene_id, int mode, const RmIntervalConfig* cfg, co
 int rm_affine_render(const RmFrameDesc* desc, int mode, const RmIntervalConfig* cfg, double* depth, uint8_t* hit,
                      int32_t* steps, RmTiming* timing);
 
+/* ---- Exact first hit (csrc/rm_exact.h) -----------------------------------------------------------------------------------
+ * Closed-form ray / surface intersection of a hard-CSG scene program: no march.  For the ray o + t d (d as given) the set
+ * S = { t : f(o + t d) <= 0 } is built from closed per-leaf sets (union, intersection, A with the closure of the complement
+ * of B for op_subtract(a, b); round, scale and onion move the level at which a leaf is cut), and the result is the smallest
+ * end point t_min < t <= t_max of a maximal interval of S: an entry, the exit when the eye is inside the solid, or a contact
+ * of measure zero.  The normal is the outward unit normal of the solid there, `leaf` the index in the program of the
+ * primitive whose boundary was hit.
+ * Scenes: catalogue ids 0-6, 8 and 14 and every live scene program made of sphere, box, plane, cylinder, torus, capsule,
+ * union, subtract, intersect, translate and -- directly over a sphere, plane, torus or capsule -- round, onion and scale.
+ * Anything else has no exact form here (rm_exact_supported says why): the smooth combinators, the repeats, cone, capped
+ * torus, Menger cross and gyroid; a modifier over a box or a cylinder; and three cases narrower than the op subset suggests --
+ * a modifier over the result of a union, subtract or intersect (modifiers are folded into the leaf they follow; write
+ * round(union(a, b)) as union(round(a), round(b))), more than three onions over one leaf, and a torus cut at a level where
+ * its tube closes the hole (minor radius + level >= major radius).  RM_E_BAD_SCENE, also for a destroyed program.
+ * Errors, stream and timing conventions: as the interval oracle above (RM_E_BAD_SCENE / RM_E_BAD_ARG without a GPU). */
+typedef struct RmExactConfig {
+    double t_min;                  /* roots at or below it are behind / at the eye; 0 = 1e-6 */
+    double t_max;                  /* roots above it are misses; 0 = no limit */
+    int32_t reserved[2];           /* 0 */
+} RmExactConfig;
+/* Negative or NaN fields, reserved != 0: RM_E_BAD_ARG. */
+
+/* 1 when scene_id has an exact form, else 0 with the reason in rm_last_error.  Host only. */
+int rm_exact_supported(int scene_id);
+/* The exact first hit of n explicit rays (origins, dirs: n x 3; directions as given).  t: +inf on a miss.  normals (n x 3,
+ * optional): 0 on a miss.  leaf (n int32, optional): -1 on a miss.  cfg may be NULL (all defaults). */
+int rm_exact_march_rays(int scene_id, const RmExactConfig* cfg, const double* origins, const double* dirs, size_t n,
+                        double* t, double* normals, int32_t* leaf);
+/* The same over rows [row0, row0 + rows) of the frame desc describes (as rm_interval_render: the library's camera rays).
+ * Per pixel: depth (t on a hit, 0 on a miss), hit (0 / 1), normal (3 doubles, optional), leaf (int32, optional). */
+int rm_exact_render(const RmFrameDesc* desc, const RmExactConfig* cfg, double* depth, uint8_t* hit, double* normal,
+                    int32_t* leaf, RmTiming* timing);
+
 /* Same contract, evaluated by wavefront TEAMS (scenes whose SDF is a loop of independent
  * transcendental chains -- Mandelbulb: three waves carry the same 64 rays and each evaluates one
  * chain per trip; see rm_kernels.h).  Identical results; RM_E_BAD_SCENE for scenes without a team form. */

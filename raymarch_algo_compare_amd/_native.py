@@ -36,6 +36,7 @@ EXPORTS = [
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
     "rm_affine_supported", "rm_affine_range_eval", "rm_affine_march_rays", "rm_affine_render",
+    "rm_exact_supported", "rm_exact_march_rays", "rm_exact_render",
     "rm_ssim_scores", "rm_capture", "rm_shade_frames", "rm_score_captures",
     "rm_intrinsic_features", "rm_view_features",
 ]
@@ -158,6 +159,11 @@ class RmIntervalConfig(ctypes.Structure):
     _fields_ = [("t_max", ctypes.c_double), ("tol", ctypes.c_double), ("h0", ctypes.c_double), ("growth", ctypes.c_double),
                 ("h_max", ctypes.c_double), ("normal_eps", ctypes.c_double), ("bound_radius", ctypes.c_double),
                 ("max_steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class RmExactConfig(ctypes.Structure):
+    """The exact first hit's constants (include/rm_hip.h): t_min 0 = 1e-6, t_max 0 = no limit."""
+    _fields_ = [("t_min", ctypes.c_double), ("t_max", ctypes.c_double), ("reserved", ctypes.c_int32 * 2)]
 
 
 class RmSegmentConfig(ctypes.Structure):
@@ -307,6 +313,10 @@ def load() -> ctypes.CDLL:
         L.rm_affine_march_rays.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(RmIntervalConfig), dp, dp, ctypes.c_size_t, dp, vp]
         L.rm_affine_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.c_int, ctypes.POINTER(RmIntervalConfig), vp, vp, vp,
                                        ctypes.POINTER(RmTiming)]
+        L.rm_exact_supported.argtypes = [ctypes.c_int]
+        L.rm_exact_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmExactConfig), dp, dp, ctypes.c_size_t, dp, vp, vp]
+        L.rm_exact_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmExactConfig), vp, vp, vp, vp,
+                                      ctypes.POINTER(RmTiming)]
         L.rm_ssim_scores.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(RmCaptureMaps), ctypes.POINTER(RmCaptureMaps),
                                      ctypes.c_int32, dp, ctypes.POINTER(RmTiming)]
         L.rm_score_captures.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(RmScoreMaps),
@@ -624,6 +634,51 @@ def interval_render(scene_id: int, cam14, width: int, height: int, cfg: RmInterv
     check(L.rm_interval_render(ctypes.byref(d), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(normal), _ptr(steps), _ref(tm)))
     maps = dict(depth=depth, hit=hit, normal=normal, steps=steps) if want_normal else dict(depth=depth, hit=hit, steps=steps)
     return _frame_maps(d, tm, **maps)
+
+
+def exact_config(t_min=0.0, t_max=0.0) -> RmExactConfig:
+    """RmExactConfig; t_min 0 = 1e-6, t_max 0 or inf = no limit."""
+    c = RmExactConfig()
+    c.t_min, c.t_max = float(t_min), 0.0 if t_max == float("inf") else float(t_max)
+    return c
+
+
+def exact_supported(scene_id: int) -> bool:
+    """rm_exact_supported (no GPU needed); exact_refusal has the reason."""
+    return load().rm_exact_supported(int(scene_id)) == 1
+
+
+def exact_refusal(scene_id: int) -> str | None:
+    """Why rm_exact_supported refuses the scene (rm_last_error's text); None when it does not."""
+    L = load()
+    if L.rm_exact_supported(int(scene_id)) == 1:
+        return None
+    return L.rm_last_error().decode("utf-8", "replace")
+
+
+def exact_march_rays(scene_id: int, origins, dirs, cfg: RmExactConfig | None = None, want_normals=True):
+    """rm_exact_march_rays: (t (+inf on a miss), normals or None, leaf (-1 on a miss)) of n explicit rays."""
+    L = init()
+    origins, dirs = _rays(origins, dirs)
+    n = len(dirs)
+    t, leaf = np.empty(n), np.empty(n, np.int32)
+    normals = np.empty((n, 3)) if want_normals else None
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_exact_march_rays(int(scene_id), _ref(cfg), origins.ctypes.data_as(dp), dirs.ctypes.data_as(dp), n,
+                                t.ctypes.data_as(dp), _ptr(normals), _ptr(leaf)))
+    return t, normals, leaf
+
+
+def exact_render(scene_id: int, cam14, width: int, height: int, cfg: RmExactConfig | None = None, row0=0, rows=None,
+                 warmup=0, repeats=0) -> dict:
+    """rm_exact_render: depth (0 on a miss), hit, normal, leaf of rows [row0, row0 + rows); `timing` with repeats > 0."""
+    L = init()
+    d = make_desc(scene_id, 0, cam14, width, height, row0, rows)
+    n = int(width) * int(d.rows)
+    depth, hit, normal, leaf = np.empty(n), np.empty(n, np.uint8), np.empty((n, 3)), np.empty(n, np.int32)
+    tm = _timing(warmup, repeats)
+    check(L.rm_exact_render(ctypes.byref(d), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(normal), _ptr(leaf), _ref(tm)))
+    return _frame_maps(d, tm, depth=depth, hit=hit, normal=normal, leaf=leaf)
 
 
 def segment_config(t_max=0.0, tol=0.0, h0=0.0, kappa=0.0, h_min=0.0, h_max=0.0, k_min=0.0, l_global=0.0, bound_radius=0.0,

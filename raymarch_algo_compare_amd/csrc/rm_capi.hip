@@ -27,6 +27,7 @@
 #include "rm_scene_program.h"
 #include "rm_interval.h"
 #include "rm_interval_catalogue.h"
+#include "rm_exact.h"
 #include "rm_segment.h"
 #include "rm_affine.h"
 #include "rm_score.h"
@@ -62,6 +63,11 @@ hipError_t launch_interval_march(const void* prog, const IntervalParams& P, cons
                                  double* t, int32_t* steps, double* normals, hipStream_t s);
 hipError_t launch_interval_render(const void* prog, const IntervalParams& P, const CameraParams& cam, int width, int height,
                                   int row0, int rows, double* depth, uint8_t* hit, double* normal, int32_t* steps, hipStream_t s);
+// rm_exact.hip: the exact first hit (rm_exact_*)
+hipError_t launch_exact_march(const void* prog, const ExactParams& P, const double* origins, const double* dirs, size_t n, double* t,
+                              double* normals, int32_t* leaf, hipStream_t s);
+hipError_t launch_exact_render(const void* prog, const ExactParams& P, const CameraParams& cam, int width, int height, int row0,
+                               int rows, double* depth, uint8_t* hit, double* normal, int32_t* leaf, hipStream_t s);
 // rm_segment.hip: the sound segment tracer (rm_segment_*)
 hipError_t launch_segment_sdf(const void* prog, const double* segs, size_t n, double* out, hipStream_t s);
 hipError_t launch_segment_march(const void* prog, const SegmentParams& P, const double* origins, const double* dirs, size_t n,
@@ -2091,6 +2097,82 @@ int rm_interval_render(const RmFrameDesc* d, const RmIntervalConfig* cfg, double
     // (a timed call waits twice: timed() before it reads its events, finish() for the maps)
     rc = once_or_timed(*c.e, timing, g.stream, [&] {
         HIP_TRY(rm::launch_interval_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_normal, d_steps, g.stream));
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
+}
+
+// ---- exact first hit (rm_exact.h, rm_exact.hip): the interval oracle's scenes that pass exact_supported ---------------
+
+namespace {
+
+// RM_OK when the scene has an exact form; RM_E_BAD_SCENE with the reason otherwise.  Host only.
+int exact_check_scene(int id)
+{
+    char why[160];
+    if (is_program_id(id)) {
+        std::lock_guard<std::mutex> lk(g_prog_mu);
+        auto it = g_programs.find(id);
+        if (it == g_programs.end()) return no_such_program(id);
+        if (!rm::exact_supported(*it->second.img, why, sizeof why)) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: %s", id, why);
+        return RM_OK;
+    }
+    const rm::ProgramImage* img = interval_catalogue_image(id);
+    if (!img) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: it is no composition of primitives", id);
+    if (!rm::exact_supported(*img, why, sizeof why)) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: %s", id, why);
+    return RM_OK;
+}
+
+int exact_params(int id, const RmExactConfig* cfg, rm::ExactParams* P)
+{
+    int rc = exact_check_scene(id);
+    if (rc) return rc;
+    char why[160];
+    if (!rm::exact_resolve(cfg, P, why, sizeof why)) return fail(RM_E_BAD_ARG, "RmExactConfig: %s", why);
+    return RM_OK;
+}
+
+}  // namespace
+
+int rm_exact_supported(int scene_id) { return exact_check_scene(scene_id) == RM_OK ? 1 : 0; }
+
+int rm_exact_march_rays(int scene_id, const RmExactConfig* cfg, const double* origins, const double* dirs, size_t n, double* t,
+                        double* normals, int32_t* leaf)
+{
+    rm::ExactParams P;
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return exact_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_origins = st.in(g.in[0], origins, n * 24);
+    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
+    double* d_t = st.out(g.out[0], t, n * 8);
+    double* d_normals = st.out(g.out[1], normals, n * 24);
+    int32_t* d_leaf = st.out(g.out[2], leaf, n * 4);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_exact_march(c.prog, P, d_origins, d_dirs, n, d_t, d_normals, d_leaf, g.stream));
+    return st.finish();
+}
+
+int rm_exact_render(const RmFrameDesc* d, const RmExactConfig* cfg, double* depth, uint8_t* hit, double* normal, int32_t* leaf,
+                    RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    rm::ExactParams P;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return exact_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
+                    "depth and hit are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    double* d_depth = st.out(g.out[0], depth, n * 8);
+    uint8_t* d_hit = st.out(g.out[1], hit, n);
+    double* d_normal = st.out(g.out[2], normal, n * 24);
+    int32_t* d_leaf = st.out(g.out[3], leaf, n * 4);
+    if ((rc = st.begin())) return rc;
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, g.stream, [&] {
+        HIP_TRY(rm::launch_exact_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_normal, d_leaf, g.stream));
         return (int)RM_OK;
     });
     return rc ? rc : st.finish();

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import faithful_segment, interval_oracle, registry, scoring
+from . import exact_oracle, faithful_segment, interval_oracle, registry, scoring
 from .camera import Camera
 from .collector import HipCollector
 from .config import MarchConfig
@@ -71,7 +71,9 @@ ROW_FIELDS = ["scene", "strategy", "params", "viewpoint", "category", "sweep_axi
 # (interval_oracle.interval_capture, scoring.py); empty cells for a scene without an interval extension
 ORACLE_FIELDS = ["oracle_iou", "oracle_false_hit", "oracle_false_miss", "oracle_depth_mae", "oracle_depth_rmse",
                  "oracle_depth_p95"]
-ORACLES = ("interval",)
+# "exact": the closed-form first hit instead (exact_oracle.exact_capture): no tolerance, the same columns; empty cells for a
+# scene without an exact form
+ORACLES = ("interval", "exact")
 # with a ceiling (run_sweep(ceiling="segment")): the sound segment tracer's frame of the viewpoint (faithful_segment.
 # faithful_capture) against the interval oracle's (scoring.residual) and its steps over the hit rays -- what a tracer that
 # cannot tunnel reaches there and pays for it; the same four values on every row of a scene and viewpoint, empty cells for a
@@ -265,10 +267,30 @@ def sound_scene(scene, twins: bool = False):
     return None
 
 
+def exact_scene(scene, twins: bool = False):
+    """sound_scene for the exact first hit: the scene itself when it has an exact form; with `twins`, its registered
+    program twin when that has one (Bad Lipschitz Sphere, Bumpy Sphere); else None."""
+    if exact_oracle.has_exact(scene):
+        return scene
+    if twins:
+        from . import scene_program
+        if scene.id in scene_program.catalogue_twins():
+            twin = scene_program.register_twin(scene)
+            if exact_oracle.has_exact(twin):
+                return twin
+    return None
+
+
 def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float, twins: bool = False) -> Dict[str, Optional[Dict]]:
-    """The oracle capture of every curated viewpoint of `scene` (None for each when it has no interval extension and,
-    with `twins`, no program twin either); `oracle` is one of ORACLES (run_sweep has checked it)."""
+    """The oracle capture of every curated viewpoint of `scene` (None for each when it has no interval extension -- for
+    "exact": no exact form -- and, with `twins`, no program twin that has one either); `oracle` is one of ORACLES (run_sweep
+    has checked it).  `tol` is the interval oracle's; the exact first hit has none."""
     vps = viewpoints_for(scene)
+    if oracle == "exact":
+        sound = exact_scene(scene, twins)
+        if sound is None:
+            return {vp.name: None for vp in vps}
+        return {vp.name: exact_oracle.exact_capture(sound, Camera(vp.position, vp.target, vp.up, 60.0, width, height)) for vp in vps}
     sound = sound_scene(scene, twins)
     if sound is None:
         return {vp.name: None for vp in vps}
@@ -321,7 +343,8 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
     interval oracle's first hit of its viewpoint (ORACLE_FIELDS; one oracle frame per scene and viewpoint, tolerance
-    `oracle_tol`).  ceiling="segment": every row also carries the sound segment tracer's result at its viewpoint
+    `oracle_tol`).  oracle="exact": the same columns against the closed-form first hit (exact_oracle.exact_capture; empty
+    cells for a scene without an exact form; with oracle_twins also Bad Lipschitz Sphere and Bumpy Sphere).  ceiling="segment": every row also carries the sound segment tracer's result at its viewpoint
     (CEILING_FIELDS; hit tolerance `ceiling_tol`, scored against the interval oracle at `oracle_tol`).  ssim=True (only
     with an oracle): every row also carries SSIM_FIELDS against the oracle capture of its viewpoint.  oracle_twins=True: a
     catalogue scene without an interval extension but with a program twin (scene_program.catalogue_twins: Menger, Bad
@@ -357,8 +380,9 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     for scene in scenes:
         first = len(rows)
         truth = (oracle_frames_for(scene, width, height, "interval", oracle_tol, oracle_twins)
-                 if oracle is not None or ceiling is not None else None)
-        ofr = truth if oracle is not None else None
+                 if oracle == "interval" or ceiling is not None else None)          # (the ceiling is scored against the interval oracle)
+        ofr = None if oracle is None else (truth if oracle == "interval" else
+                                           oracle_frames_for(scene, width, height, oracle, oracle_tol, oracle_twins))
         ccols = (ceiling_columns_for(scene, width, height, truth, ceiling_tol, oracle_twins, device_score)
                  if ceiling is not None else None)
         kept: Optional[List] = [] if ssim or device_score else None
@@ -417,7 +441,8 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="sweep.csv")
     ap.add_argument("--grid", action="store_true", help="also sweep each strategy's tunable parameters (STRATEGY_PARAM_GRID)")
     ap.add_argument("--oracle", default=None, choices=list(ORACLES),
-                    help="score every frame against a sound first-hit oracle (adds the oracle_* columns)")
+                    help="score every frame against a first-hit oracle (adds the oracle_* columns): the sound interval march or the "
+                         "closed-form exact first hit")
     ap.add_argument("--oracle-tol", type=float, default=interval_oracle.DEFAULT_TOL, help="the oracle's hit tolerance")
     ap.add_argument("--ceiling", default=None, choices=list(CEILINGS),
                     help="add the sound segment tracer's result per scene and viewpoint (the ceiling_* columns)")
