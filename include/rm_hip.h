@@ -306,6 +306,21 @@ int rm_march_rays(int scene_id, int strategy_id, const RmMarchConfig* cfg, const
  *                               (min(max(r.x, r.y), min(max(r.y, r.z), max(r.z, r.x))) - 1.0) / (s * 3.0)         :221-237
  *   RM_SOP_GYROID               freq, lipschitz (finite, > 0): primitive, with q = freq * p
  *                               (sin(q.x) * cos(q.y) + sin(q.y) * cos(q.z) + sin(q.z) * cos(q.x)) / lipschitz      :510-514
+ * Two placement ops, point transforms closed by RM_SOP_POP_POINT like RM_SOP_TRANSLATE (neither is in the reference):
+ *   RM_SOP_ROTATE               cx, sx, cy, sy, cz, sz: the cosine and sine of three angles, each pair finite with
+ *                               |c * c + s * s - 1| <= 2^-50.  The child solid is turned about the world x axis, then y,
+ *                               then z; the point therefore goes the other way round, each step forming its products first
+ *                               and then one add or subtract, both from the old pair:
+ *                                 z: (x, y) <- (cz * x + sz * y, cz * y - sz * x)
+ *                                 y: (z, x) <- (cy * z + sy * x, cy * x - sy * z)
+ *                                 x: (y, z) <- (cx * y + sx * z, cx * z - sx * y)
+ *                               A pair that is exactly (1, 0) leaves its plane untouched (no arithmetic); a pair of 0 and
+ *                               +-1 (a quarter turn) permutes two axes and rounds nothing.
+ *   RM_SOP_MIRROR               flag x, y, z, each exactly 0.0 or 1.0: a flagged coordinate becomes its absolute value
+ * Both keep a 1-Lipschitz child 1-Lipschitz (a rotation is an isometry, abs is 1-Lipschitz).  A rotated child's value is
+ * its distance; a mirror's value is the child's distance only where the child's solid lies on the positive side of every
+ * flagged plane (a solid that crosses a mirror plane gives a bound of the distance to its mirrored union, not the distance).
+ * One RM_SOP_ROTATE is a full orientation in one of the RM_SCENE_PROGRAM_MAX_POINTS point slots.
  * RM_SOP_GYROID is the one op that evaluates trigonometry on the device: sin and cos are the library's exact restatements
  * of glibc's for |q| < 105414336 (0x1.921fbp+26) and NaN for larger or non-finite arguments, so the op's value is NaN
  * there (the catalogue's Gyroid scene has the same limit).
@@ -333,7 +348,8 @@ enum {
     RM_SOP_TRANSLATE = 14, RM_SOP_REPEAT = 15, RM_SOP_POP_POINT = 16,
     RM_SOP_ROUND = 17, RM_SOP_ONION = 18,
     RM_SOP_SCALE = 19, RM_SOP_LIMITED_REPEAT = 20, RM_SOP_MENGER_CROSS = 21, RM_SOP_GYROID = 22,
-    RM_SOP_COUNT = 23
+    RM_SOP_ROTATE = 23, RM_SOP_MIRROR = 24,
+    RM_SOP_COUNT = 25
 };
 typedef struct RmSceneOp {
     int32_t op;       /* RM_SOP_* */
@@ -471,8 +487,10 @@ int rm_affine_render(const RmFrameDesc* desc, int mode, const RmIntervalConfig* 
  * of measure zero.  The normal is the outward unit normal of the solid there, `leaf` the index in the program of the
  * primitive whose boundary was hit.
  * Scenes: catalogue ids 0-6, 8 and 14 and every live scene program made of sphere, box, plane, cylinder, torus, capsule,
- * union, subtract, intersect, translate and -- directly over a sphere, plane, torus or capsule -- round, onion and scale.
- * Anything else has no exact form here (rm_exact_supported says why): the smooth combinators, the repeats, cone, capped
+ * union, subtract, intersect, translate, rotate (the ray is turned into the child's frame, the normal back into the world's)
+ * and -- directly over a sphere, plane, torus or capsule -- round, onion and scale.
+ * Anything else has no exact form here (rm_exact_supported says why): the smooth combinators, the repeats, the mirror (it
+ * folds the ray), cone, capped
  * torus, Menger cross and gyroid; a modifier over a box or a cylinder; and three cases narrower than the op subset suggests --
  * a modifier over the result of a union, subtract or intersect (modifiers are folded into the leaf they follow; write
  * round(union(a, b)) as union(round(a), round(b))), more than three onions over one leaf, and a torus cut at a level where

@@ -152,6 +152,17 @@ struct AffineAlgebra {
         if (n == limited_repeat_cell(r.hi, c, l)) return x - c * n;
         return aff_from_range(ilimited_repeat_axis(r, c, l));
     }
+    // RM_SOP_ROTATE is linear: both coordinates keep their dependence on the march symbol and no remainder appears (along a
+    // ray e stays 0 -- the rotated segment is still a segment, where the interval walk boxes it anew).  RM_SOP_MIRROR: the
+    // identity or the negation where the range keeps one sign, else the interval fallback.
+    RM_HD Aff lincomb(Aff a, double ca, Aff b, double cb) const { return a * ca + b * cb; }
+    RM_HD Aff mirror(Aff x) const
+    {
+        const Ival r = arange(x);
+        if (r.lo >= 0.0) return x;
+        if (r.hi <= 0.0) return -x;
+        return aff_from_range(iabs_pw(r));
+    }
     RM_HD Aff menger_cross(AVec3 p, double s, double s3) const { return aff_from_range(i_menger_cross(aranges(p), s, s3)); }
     RM_HD Aff gyroid(AVec3 p, double freq, double lipschitz) const { return aff_from_range(i_gyroid(aranges(p), freq, lipschitz)); }
     RM_HD Aff round(Aff a, double k) const { return a - k; }

@@ -235,7 +235,7 @@ struct Program {
     std::unique_ptr<rm::ProgramImage> img;
     void* dev = nullptr;
     double lipschitz = 1.0;
-    bool ext = false;                         // holds RM_SOP_SCALE .. RM_SOP_GYROID: rendered by SceneExtProgram's kernels
+    bool ext = false;                         // holds RM_SOP_SCALE .. RM_SOP_MIRROR: rendered by SceneExtProgram's kernels
 };
 std::mutex g_prog_mu;                          // guards g_programs and g_next_program; taken after g_mu where both are held
 std::map<int32_t, Program> g_programs;
@@ -263,7 +263,7 @@ bool program_exists(int id, bool* ext = nullptr)
 }
 
 // The kernels of scene `id` (a catalogue scene or a program; check_scene has accepted the id): a program that holds an
-// op beyond primitives.py (RM_SOP_SCALE .. RM_SOP_GYROID) has its own instantiation of the interpreter
+// op beyond primitives.py (RM_SOP_SCALE .. RM_SOP_MIRROR) has its own instantiation of the interpreter
 // (looked up by id again rather than carried out of check_scene through plan_for / launch_frame; the program cannot
 // vanish in between: the caller holds g_mu, which rm_scene_program_destroy takes first)
 const rm::SceneLaunchers* launchers(int id)

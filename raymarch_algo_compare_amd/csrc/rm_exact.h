@@ -3,7 +3,8 @@
 // first hit").  Compiles for the device and, with g++ -ffp-contract=off, for the host (tests/native/exact_check.cpp).
 //
 // Semantics.  For the ray o + t d (d as given) S = { t : f(o + t d) <= 0 } is built from closed per-leaf sets: op_union
-// is the union, op_intersect the intersection, op_subtract(a, b) is A with closure(R \ B); op_translate moves the origin;
+// is the union, op_intersect the intersection, op_subtract(a, b) is A with closure(R \ B); op_translate moves the origin,
+// op_rotate / op_turn turn origin and direction into the child's frame (the hit normal is turned back into the world's);
 // op_round(child, r) cuts the child at level + r, op_scale(child, k) at level / k, op_onion(child, th) maps a level range
 // [a, b] to [max(a + th, 0), b + th] and its mirror image.  The result is the smallest end point t_min < t <= t_max of a
 // maximal interval of S -- an entry, an exit (eye inside the solid) or a contact of measure zero ([t, t]).
@@ -343,19 +344,29 @@ RM_HD bool exact_leaf_negated(const Src& src, int pc, int slot)
 
 // ---- the two walks -------------------------------------------------------------------------------------------------
 
-// the point walk of a program's transforms (translate only; exact_supported refuses the repeats)
+// The walk of a program's transforms (translate and rotate; exact_supported refuses the repeats and the mirror): the ray is
+// transformed, not the solid, so every leaf stays closed-form in its own frame.  A translate moves the origin; a rotate turns
+// origin and direction by the point walk's own arithmetic (rotate_plane), so t along the ray means the same in every frame.
 struct ExFrame {
-    vec3 p;
-    Slots<vec3, RM_SCENE_PROGRAM_MAX_POINTS> saved;
-    RM_HD explicit ExFrame(vec3 o) : p(o), saved(o) {}
+    vec3 p, d;
+    Slots<vec3, RM_SCENE_PROGRAM_MAX_POINTS> saved, saved_d;
+    RM_HD ExFrame(vec3 o, vec3 dir) : p(o), d(dir), saved(o), saved_d(dir) {}
     template <class Src>
     RM_HD void transform(const Src& src, ProgWord w)
     {
+        const int ko = w.ko();
         if (w.op() == RM_SOP_POP_POINT) {
             p = saved.get(w.pslot(), p);
+            d = saved_d.get(w.pslot(), d);
         } else {
             saved.set(w.pslot(), p);
-            if (w.op() == RM_SOP_TRANSLATE) p = p - v3(src.k(w.ko()), src.k(w.ko() + 1), src.k(w.ko() + 2));
+            saved_d.set(w.pslot(), d);
+            if (w.op() == RM_SOP_TRANSLATE) p = p - v3(src.k(ko), src.k(ko + 1), src.k(ko + 2));
+            if (w.op() == RM_SOP_ROTATE) {
+                if (w.axis(2)) { rotate_plane(p.x, p.y, src.k(ko + 4), src.k(ko + 5)); rotate_plane(d.x, d.y, src.k(ko + 4), src.k(ko + 5)); }
+                if (w.axis(1)) { rotate_plane(p.z, p.x, src.k(ko + 2), src.k(ko + 3)); rotate_plane(d.z, d.x, src.k(ko + 2), src.k(ko + 3)); }
+                if (w.axis(0)) { rotate_plane(p.y, p.z, src.k(ko), src.k(ko + 1)); rotate_plane(d.y, d.z, src.k(ko), src.k(ko + 1)); }
+            }
         }
     }
     // the frame and the constants of the primitive word w
@@ -374,7 +385,7 @@ struct ExFrame {
 template <class Src>
 RM_HD uint32_t exact_germ_at(const Src& src, vec3 o, vec3 d, double t)
 {
-    ExFrame fr(o);
+    ExFrame fr(o, d);
     uint32_t st = 0;
     const int n = src.nops();
     for (int pc = 0; pc < n; ++pc) {
@@ -394,8 +405,8 @@ RM_HD uint32_t exact_germ_at(const Src& src, vec3 o, vec3 d, double t)
                 double la, lb;
                 exact_range(src, pc, slot, last, combo, &la, &lb);
                 if (!(la <= lb)) continue;
-                uint32_t gr = ex_cut_germ(exact_leaf_cut(src, op, ko, q, d, lb), t);
-                if (la > -__builtin_inf()) gr &= ex_cc(ex_cut_germ(exact_leaf_cut(src, op, ko, q, d, la), t));
+                uint32_t gr = ex_cut_germ(exact_leaf_cut(src, op, ko, q, fr.d, lb), t);
+                if (la > -__builtin_inf()) gr &= ex_cc(ex_cut_germ(exact_leaf_cut(src, op, ko, q, fr.d, la), t));
                 g |= gr;
             }
         } else if (ex_is_modifier(op)) {
@@ -407,6 +418,31 @@ RM_HD uint32_t exact_germ_at(const Src& src, vec3 o, vec3 d, double t)
         st = (st & ~(7u << (3 * slot))) | (g << (3 * slot));
     }
     return st & 7u;
+}
+
+// A gradient in the frame of the leaf at word `pc`, turned into the world frame: the transposes of the rotations open at
+// the leaf, innermost first.  A walk back over the words before the leaf (wave-uniform) finds them: a pop point hides the
+// transform it closes.  Each plane is rotate_plane with the sine negated, the planes in the reverse of the point walk's order.
+template <class Src>
+RM_HD vec3 exact_frame_to_world(const Src& src, int pc, vec3 g)
+{
+    int closed = 0;
+    for (int q = pc - 1; q >= 0; --q) {
+        const ProgWord w{ src.word(q) };
+        const int op = w.op();
+        if (!prog_is_transform(op)) continue;
+        if (op == RM_SOP_POP_POINT) {
+            ++closed;
+        } else if (closed > 0) {
+            --closed;
+        } else if (op == RM_SOP_ROTATE) {
+            const int ko = w.ko();
+            if (w.axis(0)) rotate_plane(g.y, g.z, src.k(ko), -src.k(ko + 1));
+            if (w.axis(1)) rotate_plane(g.z, g.x, src.k(ko + 2), -src.k(ko + 3));
+            if (w.axis(2)) rotate_plane(g.x, g.y, src.k(ko + 4), -src.k(ko + 5));
+        }
+    }
+    return g;
 }
 
 struct ExactHit {
@@ -423,7 +459,7 @@ RM_HD ExactHit exact_first_hit(const Src& src, vec3 o, vec3 d, double t_min, dou
     best.normal = v3(0.0, 0.0, 0.0);
     best.leaf = -1;
     if (!(dot(d, d) > 0.0)) return best;
-    ExFrame fr(o);
+    ExFrame fr(o, d);
     const int n = src.nops();
     int fused = 0;                        // words before pc that stand for `translate, primitive, pop point`
     for (int pc = 0; pc < n; ++pc) {
@@ -446,7 +482,7 @@ RM_HD ExactHit exact_first_hit(const Src& src, vec3 o, vec3 d, double t_min, dou
             if (!(la <= lb)) continue;
             for (int side = 0; side < 2; ++side) {                     // 0: the cut at lb, 1: the cut at la (the inner side)
                 if (side == 1 && !(la > -__builtin_inf())) continue;
-                const ExCut c = exact_leaf_cut(src, op, ko, q, d, side == 0 ? lb : la);
+                const ExCut c = exact_leaf_cut(src, op, ko, q, fr.d, side == 0 ? lb : la);
 #pragma unroll 1
                 for (int j = 0; j < 4; ++j) {
                     const double t = j == 0 ? c.a0 : (j == 1 ? c.b0 : (j == 2 ? c.a1 : c.b1));
@@ -454,7 +490,8 @@ RM_HD ExactHit exact_first_hit(const Src& src, vec3 o, vec3 d, double t_min, dou
                     if (!ex_boundary(exact_germ_at(src, o, d, t))) continue;
                     best.t = t;
                     best.leaf = index;
-                    const vec3 g = exact_leaf_gradient(src, op, ko, v3(q.x + t * d.x, q.y + t * d.y, q.z + t * d.z));
+                    const vec3 g = exact_frame_to_world(
+                        src, pc, exact_leaf_gradient(src, op, ko, v3(q.x + t * fr.d.x, q.y + t * fr.d.y, q.z + t * fr.d.z)));
                     const double len = rm_sqrt((g.x * g.x + g.y * g.y) + g.z * g.z);
                     const double inv = ((side == 1) != exact_leaf_negated(src, pc, slot) ? -1.0 : 1.0) / (len > 1e-300 ? len : 1e-300);
                     best.normal = v3(g.x * inv, g.y * inv, g.z * inv);
@@ -501,7 +538,7 @@ inline bool exact_resolve(const RmExactConfig* c, ExactParams* P, char* why, siz
 }
 
 // (host code) Does the encoded program have an exact form here?  false with the reason in `why`: a smooth combinator, a
-// repeat (needs a cell traversal), a primitive without a closed form (cone, capped torus, Menger cross, gyroid), a
+// repeat (needs a cell traversal), a mirror (it folds the ray), a primitive without a closed form (cone, capped torus, Menger cross, gyroid), a
 // modifier over a box or a cylinder (cut at level 0 only) or over a combinator's result, more than kExactMaxOnions onions
 // over one leaf, a torus cut at a level where its tube closes the hole (minor radius + level >= major radius: the quartic
 // then has roots that are not on the surface).  Op numbers are those of the encoded image.
@@ -539,7 +576,9 @@ inline bool exact_supported(const ProgramImage& img, char* why, size_t why_len)
                 if (kd < 0) return snprintf(why, why_len, "op %d: %s over a combinator's result", pc, name), false;
                 break;
             }
-            case RM_SOP_TRANSLATE: case RM_SOP_POP_POINT: break;
+            case RM_SOP_MIRROR:
+                return snprintf(why, why_len, "op %d: a mirror folds the ray (its image is no single ray)", pc), false;
+            case RM_SOP_TRANSLATE: case RM_SOP_ROTATE: case RM_SOP_POP_POINT: break;
             default:                      // sphere, box, plane, cylinder, torus, capsule
                 if (slot >= 0 && slot < RM_SCENE_PROGRAM_MAX_VALUES) kind[slot] = op;
                 int last, onions;

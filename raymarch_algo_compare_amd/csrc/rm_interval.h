@@ -329,6 +329,10 @@ struct IntervalAlgebra {
     RM_HD IVec3 translate(IVec3 p, double kx, double ky, double kz) const { return ivec3(p.x - kx, p.y - ky, p.z - kz); }
     RM_HD Ival repeat(Ival x, double spacing, bool pow2) const { return irepeat_axis(x, spacing, pow2); }
     RM_HD Ival limited_repeat(Ival x, double spacing, double limit) const { return ilimited_repeat_axis(x, spacing, limit); }
+    // RM_SOP_ROTATE: the two coordinates are taken as independent, so a tilted box is enclosed by an axis-aligned one (the
+    // wrapping effect); a degenerate box evaluates the pointwise expression.  RM_SOP_MIRROR: the exact range of |x|.
+    RM_HD Ival lincomb(Ival a, double ca, Ival b, double cb) const { return a * ca + b * cb; }
+    RM_HD Ival mirror(Ival x) const { return iabs_pw(x); }
     RM_HD Ival round(Ival a, double k) const { return a - k; }
     RM_HD Ival scale(Ival a, double k) const { return i_scale(a, k); }
     RM_HD Ival abs(Ival a) const { return iabs_pw(a); }

@@ -33,8 +33,8 @@ constexpr int kProgMaxConst = kProgMaxArgs * kProgMaxOps;
 constexpr uint32_t kProgTranslated = 1u << 13;
 
 // The device image of a program (what a launch's scene_data points to).  code[i]: bits 0-5 opcode, 6-9 value slot,
-// 10-12 point slot, 13-15 axes of RM_SOP_REPEAT / RM_SOP_LIMITED_REPEAT with a positive spacing, 16-31 offset of the
-// constants in k[].  Two flags reuse bits a word's opcode leaves free:
+// 10-12 point slot, 13-15 axes of RM_SOP_REPEAT / RM_SOP_LIMITED_REPEAT with a positive spacing, of RM_SOP_ROTATE whose
+// (cos, sin) is not exactly (1, 0) and of RM_SOP_MIRROR that are flagged, 16-31 offset of the constants in k[].  Two flags reuse bits a word's opcode leaves free:
 //  * a primitive with bit 13 set is `translate, primitive, pop point` fused (its first three constants are the offset):
 //    the same arithmetic, p - offset then the primitive, without the trip through the point stack;
 //  * RM_SOP_REPEAT: bits 6-8 mark the axes whose spacing is a power of two in [2^-64, 2^64]; there py_mod_pow2 (the
@@ -53,7 +53,8 @@ struct ProgWord {
     RM_HD int pslot() const { return (int)((w >> 10) & 7u); }          // point slot saved to / restored from
     RM_HD int ko() const { return (int)(w >> 16); }                    // offset of the constants in k[]
     RM_HD bool translated() const { return (w & kProgTranslated) != 0; }           // a primitive fused with its translate
-    RM_HD bool axis(int a) const { return (w & (1u << (13 + a))) != 0; }           // RM_SOP_REPEAT, RM_SOP_LIMITED_REPEAT: axis a is repeated
+    RM_HD bool axis(int a) const { return (w & (1u << (13 + a))) != 0; }           // RM_SOP_REPEAT, RM_SOP_LIMITED_REPEAT: axis a is repeated;
+                                                                                   // RM_SOP_ROTATE: turned about; RM_SOP_MIRROR: folded
     RM_HD bool pow2(int a) const { return (w & (1u << (6 + a))) != 0; }            // ... with a power-of-two spacing
 };
 
@@ -74,13 +75,20 @@ RM_HD int program_op_args(int op)
         case RM_SOP_ROUND: case RM_SOP_ONION: case RM_SOP_SCALE: return 1;
         case RM_SOP_LIMITED_REPEAT: return 6;
         case RM_SOP_MENGER_CROSS: case RM_SOP_GYROID: return 2;
+        case RM_SOP_ROTATE: return 6;
+        case RM_SOP_MIRROR: return 3;
         default: return 0;
     }
 }
 
 // the three kinds of op the walks tell apart by their opcode (wave-uniform)
-RM_HD bool prog_is_transform(int op) { return (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) || op == RM_SOP_LIMITED_REPEAT; }
-RM_HD bool prog_is_primitive(int op) { return op <= RM_SOP_CONE || op >= RM_SOP_MENGER_CROSS; }
+RM_HD bool prog_is_transform(int op)
+{
+    return (op >= RM_SOP_TRANSLATE && op <= RM_SOP_POP_POINT) || op == RM_SOP_LIMITED_REPEAT || op >= RM_SOP_ROTATE;
+}
+RM_HD bool prog_is_primitive(int op) { return op <= RM_SOP_CONE || op == RM_SOP_MENGER_CROSS || op == RM_SOP_GYROID; }
+// ... of an op that is no transform (the walks take those first): the two comparisons the test had before the placement ops
+RM_HD bool prog_pushes(int op) { return op <= RM_SOP_CONE || op >= RM_SOP_MENGER_CROSS; }
 
 // ---- scenes/primitives.py functions rm_scenes.h does not already hold ---------------------------------------------
 
@@ -173,6 +181,17 @@ RM_HD double sd_gyroid(vec3 p, double freq, double lipschitz)
     return (sx * cy + sy * cz + sz * cx) / lipschitz;
 }
 
+// ---- the two placement ops --------------------------------------------------------------------------------------------------
+
+// one plane of RM_SOP_ROTATE: (u, v) <- (c u + s v, c v - s u), four products and then one add and one subtract (no
+// contraction), both from the old pair.  c = 0, s = +-1 (a quarter turn) gives (+-v, -+u) without rounding.
+RM_HD void rotate_plane(double& u, double& v, double c, double s)
+{
+    const double cu = c * u, sv = s * v, cv = c * v, su = s * u;
+    u = cu + sv;
+    v = cv - su;
+}
+
 // ---- the interpreter ----------------------------------------------------------------------------------------------
 
 // N register slots of a T (a record of doubles: double, vec3, Ival, IVec3, DIval), kept lane by lane.  Slot i
@@ -224,8 +243,19 @@ struct Slots {
 // and over a box with the derivative along a ray (DualAlgebra, rm_segment.h).  (program_eval below keeps its own loop:
 // DESIGN.md section 3, "Interval oracle".)
 // An algebra names its Value and its Point (a record with members x, y, z) and provides the ten primitives, translate,
-// repeat and limited repeat of one coordinate, the three modifiers and the six combinators; it is an object because the dual one carries the
-// ray's direction.  Src: nops(), word(i) (wave-uniform), k(i).
+// repeat and limited repeat of one coordinate, lincomb (a * ca + b * cb of two coordinates) and mirror (abs of a coordinate) for
+// the placement ops, the three modifiers and the six combinators.  Src: nops(), word(i) (wave-uniform), k(i).
+// One plane of RM_SOP_ROTATE in an algebra: (u, v) <- (c u + s v, c v - s u), the products first, both from the old pair.
+// `on` (wave-uniform) is clear for a pair that is exactly (1, 0).
+template <class A, class C>
+RM_HD void prog_rotate(const A& alg, C& u, C& v, bool on, double c, double s)
+{
+    if (!on) return;
+    const C u0 = u;
+    u = alg.lincomb(u0, c, v, s);
+    v = alg.lincomb(v, c, u0, -s);
+}
+
 template <class A, class Src>
 RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::Point p)
 {
@@ -250,16 +280,24 @@ RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::P
                     if (w.axis(0)) p.x = alg.repeat(p.x, kx, w.pow2(0));
                     if (w.axis(1)) p.y = alg.repeat(p.y, ky, w.pow2(1));
                     if (w.axis(2)) p.z = alg.repeat(p.z, kz, w.pow2(2));
-                } else {                                                             // RM_SOP_LIMITED_REPEAT
+                } else if (op == RM_SOP_LIMITED_REPEAT) {
                     if (w.axis(0)) p.x = alg.limited_repeat(p.x, kx, src.k(ko + 3));
                     if (w.axis(1)) p.y = alg.limited_repeat(p.y, ky, src.k(ko + 4));
                     if (w.axis(2)) p.z = alg.limited_repeat(p.z, kz, src.k(ko + 5));
+                } else if (op == RM_SOP_ROTATE) {                                    // about z, then y, then x: the solid's order reversed
+                    prog_rotate(alg, p.x, p.y, w.axis(2), src.k(ko + 4), src.k(ko + 5));
+                    prog_rotate(alg, p.z, p.x, w.axis(1), kz, src.k(ko + 3));
+                    prog_rotate(alg, p.y, p.z, w.axis(0), kx, ky);
+                } else {                                                             // RM_SOP_MIRROR
+                    if (w.axis(0)) p.x = alg.mirror(p.x);
+                    if (w.axis(1)) p.y = alg.mirror(p.y);
+                    if (w.axis(2)) p.z = alg.mirror(p.z);
                 }
             }
             continue;
         }
         V r;
-        if (prog_is_primitive(op)) {                                                 // primitives: push
+        if (prog_pushes(op)) {                                                       // primitives: push
             P q = p;
             if (w.translated()) {                                                    // fused op_translate (:99-100)
                 q = alg.translate(q, src.k(ko), src.k(ko + 1), src.k(ko + 2));
@@ -322,8 +360,8 @@ RM_HD typename A::Value program_walk(const A& alg, const Src& src, typename A::P
         x##j = (i) == j ? q.x : x##j; y##j = (i) == j ? q.y : y##j; z##j = (i) == j ? q.z : z##j;                     \
     } while (0)
 
-// Src: nops(), word(i) (wave-uniform), k(i).  EXT: the four ops beyond primitives.py (RM_SOP_SCALE .. RM_SOP_GYROID) are
-// built in (SceneExtProgram below).  Without it every test on them is a compile-time constant and the walk is the one the
+// Src: nops(), word(i) (wave-uniform), k(i).  EXT: the four ops beyond primitives.py (RM_SOP_SCALE .. RM_SOP_GYROID) and the two
+// placement ops (RM_SOP_ROTATE, RM_SOP_MIRROR) are built in (SceneExtProgram below).  Without it every test on them is a compile-time constant and the walk is the one the
 // interpreter had before those ops existed -- the host never sends a program that holds one to such a kernel.
 template <bool EXT = true, class Src>
 RM_HD double program_eval(const Src& src, vec3 p)
@@ -351,16 +389,24 @@ RM_HD double program_eval(const Src& src, vec3 p)
                     if (w.axis(0)) p.x = repeat_axis_any(p.x, kx, w.pow2(0));
                     if (w.axis(1)) p.y = repeat_axis_any(p.y, ky, w.pow2(1));
                     if (w.axis(2)) p.z = repeat_axis_any(p.z, kz, w.pow2(2));
-                } else {                                                             // RM_SOP_LIMITED_REPEAT
+                } else if (op == RM_SOP_LIMITED_REPEAT) {
                     if (w.axis(0)) p.x = limited_repeat_axis(p.x, kx, src.k(ko + 3));
                     if (w.axis(1)) p.y = limited_repeat_axis(p.y, ky, src.k(ko + 4));
                     if (w.axis(2)) p.z = limited_repeat_axis(p.z, kz, src.k(ko + 5));
+                } else if (op == RM_SOP_ROTATE) {                                    // about z, then y, then x: the solid's order reversed
+                    if (w.axis(2)) rotate_plane(p.x, p.y, src.k(ko + 4), src.k(ko + 5));
+                    if (w.axis(1)) rotate_plane(p.z, p.x, kz, src.k(ko + 3));
+                    if (w.axis(0)) rotate_plane(p.y, p.z, kx, ky);
+                } else {                                                             // RM_SOP_MIRROR
+                    if (w.axis(0)) p.x = rm_fabs(p.x);
+                    if (w.axis(1)) p.y = rm_fabs(p.y);
+                    if (w.axis(2)) p.z = rm_fabs(p.z);
                 }
             }
             continue;
         }
         double r;
-        if (EXT ? prog_is_primitive(op) : op <= RM_SOP_CONE) {                       // primitives: push
+        if (EXT ? prog_pushes(op) : op <= RM_SOP_CONE) {                             // primitives: push
             vec3 p0 = p;
             int ko = w.ko();
             if (w.translated()) {                                               // fused op_translate (:99-100)
@@ -481,7 +527,8 @@ inline bool program_has_ext(const ProgramImage& img)
 // (host code) Validates a program and writes its device image.  false with the reason in `why` for a malformed program: opcode out
 // of range, reserved field set, non-finite or (for unused entries) non-zero constant, smooth k == 0 (a division by zero
 // in the reference), a scale factor, Menger scale or gyroid lipschitz that is not > 0, a Menger f[1] that is not f[0] * 3.0,
-// a negative limit of a limited repeat, value stack deeper than RM_SCENE_PROGRAM_MAX_VALUES or popped when empty, more than
+// a negative limit of a limited repeat, a rotate pair that is not a cosine and sine (|c c + s s - 1| > 2^-50), a mirror flag that
+// is neither 0.0 nor 1.0, value stack deeper than RM_SCENE_PROGRAM_MAX_VALUES or popped when empty, more than
 // RM_SCENE_PROGRAM_MAX_POINTS nested transforms or a pop without a transform, not exactly one value left, a transform
 // left open, length outside 1..RM_SCENE_PROGRAM_MAX_OPS.
 inline bool program_encode(const RmSceneOp* ops, int32_t nops, ProgramImage* img, char* why, size_t why_len)
@@ -515,14 +562,26 @@ inline bool program_encode(const RmSceneOp* ops, int32_t nops, ProgramImage* img
                 if (vsp < 1) return snprintf(why, why_len, "op %d: modifier needs a value, the stack is empty", i), false;
                 slot = (uint32_t)(vsp - 1);
                 break;
-            case RM_SOP_TRANSLATE: case RM_SOP_REPEAT: case RM_SOP_LIMITED_REPEAT:
+            case RM_SOP_TRANSLATE: case RM_SOP_REPEAT: case RM_SOP_LIMITED_REPEAT: case RM_SOP_ROTATE: case RM_SOP_MIRROR:
+                if (o.op == RM_SOP_ROTATE)
+                    for (int j = 0; j < 3; ++j) {
+                        const double c = o.f[2 * j], s = o.f[2 * j + 1];
+                        if (!(rm_fabs(c * c + s * s - 1.0) <= 0x1p-50))
+                            return snprintf(why, why_len, "op %d: (f[%d], f[%d]) is not the cosine and sine of an angle", i, 2 * j, 2 * j + 1), false;
+                        if (!(c == 1.0 && s == 0.0)) axes |= 1u << j;
+                    }
+                if (o.op == RM_SOP_MIRROR)
+                    for (int j = 0; j < 3; ++j) {
+                        if (o.f[j] != 0.0 && o.f[j] != 1.0) return snprintf(why, why_len, "op %d: mirror flag f[%d] must be 0 or 1", i, j), false;
+                        if (o.f[j] == 1.0) axes |= 1u << j;
+                    }
                 if (o.op == RM_SOP_LIMITED_REPEAT)
                     for (int j = 3; j < 6; ++j)
                         if (o.f[j] < 0.0) return snprintf(why, why_len, "op %d: limit f[%d] is negative", i, j), false;
                 if (psp >= RM_SCENE_PROGRAM_MAX_POINTS)
                     return snprintf(why, why_len, "op %d: more than %d nested transforms", i, RM_SCENE_PROGRAM_MAX_POINTS), false;
                 pslot = (uint32_t)psp++;
-                if (o.op != RM_SOP_TRANSLATE)
+                if (o.op == RM_SOP_REPEAT || o.op == RM_SOP_LIMITED_REPEAT)
                     for (int j = 0; j < 3; ++j)
                         if (o.f[j] > 0.0) {
                             axes |= 1u << j;

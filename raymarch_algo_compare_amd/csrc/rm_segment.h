@@ -10,8 +10,11 @@
 //  * every other op: `val` is the interval extension of rm_interval.h itself (i_cylinder, i_capsule, ... are called, not
 //    restated), `der` is the chain rule through the pointwise formula.  DESIGN.md section 3, "Segment ceiling", gives the
 //    soundness argument of each rule.
-// A translated, repeated or limited-repeated coordinate keeps d/dtau = rd_c (wherever it is differentiable), so the point is a box (IVec3) plus the constant direction and
-// the four saved boxes need no derivative slots.  Rounding is to nearest, as in the reference.
+// The walk's point is a dual point (DVec3): every coordinate carries the enclosure of its own d/dtau, seeded once with the ray's
+// direction rd_c as a degenerate interval.  A translated, repeated or limited-repeated coordinate keeps its derivative
+// (wherever it is differentiable); RM_SOP_ROTATE combines the derivatives as it combines the values, RM_SOP_MIRROR is the
+// dual abs.  In a program without those two every der stays the degenerate [rd_c, rd_c], and the arithmetic on it is the
+// arithmetic the constant direction had.  Rounding is to nearest, as in the reference.
 #pragma once
 
 #include "rm_interval.h"
@@ -169,8 +172,7 @@ RM_HD DIval d_cone(DVec3 p, double c, double s, double height)
 // of +-s |rd_c|.  The rest is abs, max and min: the decided branch's slope, else the hull.
 RM_HD DIval dmenger_fold(DIval x, double s)
 {
-    const double d = s * x.der.lo;                                       // x.der is the constant rd_c
-    const DIval b = dabs_pw(dv(imenger_a(x.val, s), iv(d, d)));
+    const DIval b = dabs_pw(dv(imenger_a(x.val, s), x.der * s));       // (x.der is rd_c unless a rotate or mirror came before)
     return dabs_pw(dv(iv(1.0 - 3.0 * b.val.hi, 1.0 - 3.0 * b.val.lo), -(b.der * 3.0)));
 }
 RM_HD DIval d_menger_cross(DVec3 p, double s, double s3)
@@ -190,7 +192,7 @@ RM_HD DIval d_gyroid(DVec3 p, double freq, double lipschitz)
 {
     const ISinCos3 sc = isincos3(dvals(p), freq);
     const ISinCos x = sc.x, y = sc.y, z = sc.z;
-    const double qx = freq * p.x.der.lo, qy = freq * p.y.der.lo, qz = freq * p.z.der.lo;
+    const Ival qx = p.x.der * freq, qy = p.y.der * freq, qz = p.z.der * freq;
     const DIval sx = dv(x.s, x.c * qx), cx = dv(x.c, -(x.s * qx));
     const DIval sy = dv(y.s, y.c * qy), cy = dv(y.c, -(y.s * qy));
     const DIval sz = dv(z.s, z.c * qz), cz = dv(z.c, -(z.s * qz));
@@ -200,22 +202,32 @@ RM_HD DIval d_gyroid(DVec3 p, double freq, double lipschitz)
 
 // ---- the interpreter ----------------------------------------------------------------------------------------------
 
-// evaluation over the box of a ray segment with direction rd (program_walk, rm_scene_program.h).  The point is the
-// interval walk's box; a primitive lifts it to a dual point.  A smooth combinator's partial derivatives are h and 1 - h
-// (h in [0, 1]) up to the signs of its arguments: the hull of the two ders.
-struct DualAlgebra : IntervalAlgebra {
+// evaluation over the dual point of a ray segment (program_walk, rm_scene_program.h): val is the interval walk's, operation for
+// operation.  A smooth combinator's partial derivatives are h and 1 - h (h in [0, 1]) up to the signs of its arguments: the
+// hull of the two ders.
+struct DualAlgebra {
     typedef DIval Value;
-    vec3 rd;
-    RM_HD DIval sphere(IVec3 p, double r) const { return d_sphere(dvec3(p, rd), r); }
-    RM_HD DIval box(IVec3 p, double h0, double h1, double h2) const { return d_box(dvec3(p, rd), h0, h1, h2); }
-    RM_HD DIval plane(IVec3 p, double n0, double n1, double n2, double offset) const { return d_plane(dvec3(p, rd), n0, n1, n2, offset); }
-    RM_HD DIval cylinder(IVec3 p, double radius, double half_height) const { return d_cylinder(dvec3(p, rd), radius, half_height); }
-    RM_HD DIval torus(IVec3 p, double major_radius, double minor_radius) const { return d_torus(dvec3(p, rd), major_radius, minor_radius); }
-    RM_HD DIval capsule(IVec3 p, vec3 a, vec3 b, double radius) const { return d_capsule(dvec3(p, rd), a, b, radius); }
-    RM_HD DIval capped_torus(IVec3 p, double sc0, double sc1, double ra, double rb) const { return d_capped_torus(dvec3(p, rd), sc0, sc1, ra, rb); }
-    RM_HD DIval cone(IVec3 p, double c, double s, double height) const { return d_cone(dvec3(p, rd), c, s, height); }
-    RM_HD DIval menger_cross(IVec3 p, double s, double s3) const { return d_menger_cross(dvec3(p, rd), s, s3); }
-    RM_HD DIval gyroid(IVec3 p, double freq, double lipschitz) const { return d_gyroid(dvec3(p, rd), freq, lipschitz); }
+    typedef DVec3 Point;
+    RM_HD DIval sphere(DVec3 p, double r) const { return d_sphere(p, r); }
+    RM_HD DIval box(DVec3 p, double h0, double h1, double h2) const { return d_box(p, h0, h1, h2); }
+    RM_HD DIval plane(DVec3 p, double n0, double n1, double n2, double offset) const { return d_plane(p, n0, n1, n2, offset); }
+    RM_HD DIval cylinder(DVec3 p, double radius, double half_height) const { return d_cylinder(p, radius, half_height); }
+    RM_HD DIval torus(DVec3 p, double major_radius, double minor_radius) const { return d_torus(p, major_radius, minor_radius); }
+    RM_HD DIval capsule(DVec3 p, vec3 a, vec3 b, double radius) const { return d_capsule(p, a, b, radius); }
+    RM_HD DIval capped_torus(DVec3 p, double sc0, double sc1, double ra, double rb) const { return d_capped_torus(p, sc0, sc1, ra, rb); }
+    RM_HD DIval cone(DVec3 p, double c, double s, double height) const { return d_cone(p, c, s, height); }
+    RM_HD DIval menger_cross(DVec3 p, double s, double s3) const { return d_menger_cross(p, s, s3); }
+    RM_HD DIval gyroid(DVec3 p, double freq, double lipschitz) const { return d_gyroid(p, freq, lipschitz); }
+    RM_HD DVec3 translate(DVec3 p, double kx, double ky, double kz) const
+    {
+        p.x = p.x - kx; p.y = p.y - ky; p.z = p.z - kz;
+        return p;
+    }
+    // piecewise a shift: the derivative is the coordinate's own wherever the map is differentiable
+    RM_HD DIval repeat(DIval x, double spacing, bool pow2) const { return dv(irepeat_axis(x.val, spacing, pow2), x.der); }
+    RM_HD DIval limited_repeat(DIval x, double spacing, double limit) const { return dv(ilimited_repeat_axis(x.val, spacing, limit), x.der); }
+    RM_HD DIval lincomb(DIval a, double ca, DIval b, double cb) const { return a * ca + b * cb; }       // linear: val and der alike
+    RM_HD DIval mirror(DIval x) const { return dabs_pw(x); }
     RM_HD DIval round(DIval a, double k) const { return a - k; }
     RM_HD DIval scale(DIval a, double k) const { return dv(i_scale(a.val, k), i_scale(a.der, k)); }
     RM_HD DIval abs(DIval a) const { return dabs_pw(a); }
@@ -232,9 +244,7 @@ struct DualAlgebra : IntervalAlgebra {
 template <class Src>
 RM_HD DIval program_eval_dual(const Src& src, IVec3 p, vec3 rd)
 {
-    DualAlgebra alg;
-    alg.rd = rd;
-    return program_walk(alg, src, p);
+    return program_walk(DualAlgebra{}, src, dvec3(p, rd));
 }
 
 // ---- gpu/faithful_offline.py -----------------------------------------------------------------------------------------

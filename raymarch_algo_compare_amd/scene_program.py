@@ -15,6 +15,11 @@ Four ops go beyond primitives.py, enough to write five more catalogue scenes as 
 `sd_menger_cross(scale)` is one trip of the Menger sponge's fold and `sd_gyroid(freq, lipschitz)` the gyroid sheet (the
 one op whose sin / cos the device evaluates, with the library's exact restatements of libm's).
 
+Three placement builders orient a subtree (PLACEMENT_OPCODES): `op_rotate(angles_rad, child)` turns it about the world x
+axis, then y, then z, `op_turn(quarters, child)` does so by exact quarter turns (the same opcode, constants 0 and +-1),
+`op_mirror(axes, child)` evaluates it at the absolute value of the flagged coordinates.  One of them is one nested point
+transform, of which a program may have MAX_POINTS open at once.
+
 A registered scene is found by registry.get_scene_by_name and accepted by run_once, HipCollector, run_gpu_benchmark,
 GPURunner (by its id), the sweep and the _native entry points; get_all_scenes() / SCENES stay the 20 catalogue scenes.
 Registration is process-wide; unregister_scene frees the program (its id is never reused).
@@ -41,7 +46,9 @@ OPCODES = {
 }
 # the four ops that are not primitives.py functions (RM_SOP_SCALE ..)
 EXT_OPCODES = {"op_scale": 19, "op_limited_repeat": 20, "sd_menger_cross": 21, "sd_gyroid": 22}
-_ALL_OPCODES = {**OPCODES, **EXT_OPCODES}
+# placement: one op_rotate / op_turn (the same opcode) is a full orientation in one point slot; op_mirror folds space
+PLACEMENT_OPCODES = {"op_rotate": 23, "op_turn": 23, "op_mirror": 24}
+_ALL_OPCODES = {**OPCODES, **EXT_OPCODES, **PLACEMENT_OPCODES}
 MAX_OPS, MAX_VALUES, MAX_POINTS = 256, 8, 4
 
 # op -> (parameters as (name, number of floats), children)
@@ -68,8 +75,13 @@ _SPEC: Dict[str, Tuple[Tuple[Tuple[str, int], ...], Tuple[str, ...]]] = {
     "op_limited_repeat": ((("spacing", 3), ("limit", 3)), ("child",)),
     "sd_menger_cross": ((("scale", 1),), ()),
     "sd_gyroid": ((("freq", 1), ("lipschitz", 1)), ()),
+    "op_rotate": ((("angles_rad", 3),), ("child",)),
+    "op_turn": ((("quarters", 3),), ("child",)),
+    "op_mirror": ((("axes", 3),), ("child",)),
 }
-_POINT_TRANSFORMS = ("op_translate", "op_repeat", "op_limited_repeat")
+_POINT_TRANSFORMS = ("op_translate", "op_repeat", "op_limited_repeat", "op_rotate", "op_turn", "op_mirror")
+# cos, sin of k quarter turns: exact, where math.cos(math.pi / 2) is 6.1e-17
+_QUARTER = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))
 
 
 @dataclass(frozen=True)
@@ -108,7 +120,14 @@ def _make(op: str, values: dict, children: Sequence[Expr]) -> Expr:
             vs = tuple(v) if isinstance(v, (list, tuple)) else None
             if vs is None or len(vs) != n:
                 raise TypeError(f"{op}: {name} must be a sequence of {n} numbers")
-            out.append((name, tuple(_num(name, x) for x in vs)))
+            nums = tuple(_num(name, x) for x in vs)
+            if op == "op_turn":
+                if any(not math.isfinite(x) or x != math.floor(x) for x in nums):
+                    raise ValueError(f"op_turn: quarters must be whole numbers, not {nums}")
+                nums = tuple(float(int(x) % 4) for x in nums)
+            if op == "op_mirror" and any(x not in (0.0, 1.0) for x in nums):
+                raise ValueError(f"op_mirror: axes must be 0 / 1 flags, not {nums}")
+            out.append((name, nums))
     for c in children:
         if not isinstance(c, Expr):
             raise TypeError(f"{op}: a subtree must be an expression, not {type(c).__name__}")
@@ -212,6 +231,26 @@ def sd_menger_cross(scale) -> Expr:
 def sd_gyroid(freq, lipschitz) -> Expr:
     """(sin(q.x) cos(q.y) + sin(q.y) cos(q.z) + sin(q.z) cos(q.x)) / lipschitz with q = freq * p (lipschitz > 0)."""
     return _make("sd_gyroid", {"freq": freq, "lipschitz": lipschitz}, ())
+
+
+def op_rotate(angles_rad, child: Expr) -> Expr:
+    """The child turned about the world x axis by angles_rad[0], then about y, then about z (radians, right-handed).  The
+    cosines and sines are computed here by Python's math, as sd_cone's are; an angle of exactly 0 leaves its plane untouched."""
+    return _make("op_rotate", {"angles_rad": angles_rad}, (child,))
+
+
+def op_turn(quarters, child: Expr) -> Expr:
+    """op_rotate by whole quarter turns (three integers, taken mod 4): the cosines and sines are exactly 0 and +-1, the
+    rotation is a permutation of the axes with signs and rounds nothing -- op_turn((0, 0, 1), sd_cylinder(r, h)) is the
+    cylinder about x."""
+    return _make("op_turn", {"quarters": quarters}, (child,))
+
+
+def op_mirror(axes, child: Expr) -> Expr:
+    """The child evaluated at the point with every flagged coordinate (three 0 / 1 flags) replaced by its absolute value:
+    the child's positive side, mirrored.  The value is the mirrored solid's distance only where the child's solid lies
+    on the positive side of each mirror plane (elsewhere it is still a 1-Lipschitz bound that is positive outside)."""
+    return _make("op_mirror", {"axes": axes}, (child,))
 
 
 # ---- the catalogue scenes expressible in primitives.py, restated -------------------------------------------------------
@@ -323,6 +362,10 @@ def compile_ops(expr: Expr) -> List[Tuple[int, Tuple[float, ...]]]:
             return (math.cos(a), math.sin(a), e.param("height"))
         if e.op == "sd_menger_cross":     # `s *= 3.0` before the division (catalog.py:226, :236)
             return (e.param("scale"), e.param("scale") * 3.0)
+        if e.op == "op_rotate":           # (cos, sin) per axis by the host's libm; (1.0, 0.0) exactly for an angle of 0
+            return tuple(v for a in e.param("angles_rad") for v in ((1.0, 0.0) if a == 0.0 else (math.cos(a), math.sin(a))))
+        if e.op == "op_turn":
+            return tuple(v for q in e.param("quarters") for v in _QUARTER[int(q) % 4])
         vals: List[float] = []
         for _, v in e.params:
             vals.extend(v if isinstance(v, tuple) else (v,))
@@ -500,4 +543,4 @@ __all__ = ["Expr", "sd_sphere", "sd_box", "sd_plane", "sd_cylinder", "sd_torus",
            "op_translate", "op_repeat", "op_round", "op_onion", "expr_from_json", "dumps", "loads", "compile_ops",
            "register_scene", "unregister_scene", "registered_scenes", "expression_of", "scene_entry", "save_scene_file",
            "load_scene_file", "catalogue_expressions", "op_scale", "op_limited_repeat", "sd_menger_cross", "sd_gyroid",
-           "catalogue_twins", "register_twin", "twin_name"]
+           "catalogue_twins", "register_twin", "twin_name", "op_rotate", "op_turn", "op_mirror"]
