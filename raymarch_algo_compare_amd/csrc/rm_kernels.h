@@ -918,22 +918,61 @@ constexpr int kTeam = 3;
 
 // Exchange buffer of a team: [trip parity][value 0..5][lane]; double-buffered so one barrier per trip
 // suffices (a wave can only overwrite a buffer after every wave has passed the barrier that follows
-// the reads of its previous use).  A trip without an exchange (team_trips THE SHORT LAST TRIP) touches neither buffer
+// the reads of its previous use).  A trip without an exchange (team_evaluate THE SHORT LAST TRIP) touches neither buffer
 // nor `turn`: the exchanges that remain keep alternating, which is all the argument needs.
 struct TeamXch {
     double v[2][2 * kTeam][64];
 };
 
-// One trip for a team; `turn` counts the team's trips (buffer parity).  Wave-uniform call.  The part is an int, or a
-// std::integral_constant<int, P> in a per-part trip loop (team_trips).
+// Scene::kSparseFlag: begin and trip_join take the wave's sparse flag (rm_scenes.h; set by the Mandelbulb).  team_sparse
+// is taken once per evaluation over the lanes that begin it; within the evaluation lanes only drop out, and the three
+// waves of a team hold the same lanes, so the flag is wave-uniform and the same in the whole team.
+template <class Scene, class = void>
+struct SceneSparseFlag : std::false_type {};
+template <class Scene>
+struct SceneSparseFlag<Scene, decltype((void)Scene::kSparseFlag)> : std::integral_constant<bool, Scene::kSparseFlag> {};
+__device__ __forceinline__ bool team_sparse(bool live) { return __popcll(__ballot(live)) <= kSparseLanes; }
+// One trip of a team that picked its loops by the sparse flag (team_evaluate; scenes with kSparseFlag and per-part
+// loops).  `turn` counts the team's trips (buffer parity).  Wave-uniform call.  SPARSE, the flag as a constant, picks the
+// layout of the libm forms and the root of the join.  The wave joins from its own two values in registers and reads only
+// the other four from LDS: a wave wrote exactly those two values, so the bits are the same.
+template <class Scene, int P, bool SPARSE>
+__device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, int lane, TeamXch& x, int& turn)
+{
+    double o0 = 0.0, o1 = 0.0;
+    if (go) Scene::template trip_part<P, SPARSE>(ev, o0, o1);
+    double (*buf)[64] = x.v[turn & 1];
+    ++turn;
+    buf[2 * P][lane] = o0;
+    buf[2 * P + 1][lane] = o1;
+    __syncthreads();
+    bool done = true;
+    if (go) {
+        double v[2 * kTeam];
+#pragma unroll
+        for (int k = 0; k < 2 * kTeam; ++k) v[k] = (k == 2 * P) ? o0 : (k == 2 * P + 1) ? o1 : buf[k][lane];
+        done = Scene::trip_join(ev, v[0], v[1], v[2], v[3], v[4], v[5], SPARSE);
+    }
+    return done;
+}
+
+template <class Scene, int P>
+__device__ __forceinline__ void team_trip_part_banded(const typename Scene::Eval& ev, double& o0, double& o1)
+{
+    if constexpr (SceneSparseFlag<Scene>::value) Scene::template trip_part<P, false>(ev, o0, o1);
+    else Scene::template trip_part<P>(ev, o0, o1);
+}
+// The trip as it was before the flag (kTeamBanded): banded libm forms, the live lanes counted in every root, all six
+// values read from LDS.  What the kernels that keep the previous forms run (team_trips), statement for statement, so
+// that they compile to what they were.
 template <class Scene, class PartT>
-__device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, PartT part, int lane, TeamXch& x, int& turn)
+__device__ __forceinline__ bool team_trip_banded(typename Scene::Eval& ev, bool go, PartT part, int lane, TeamXch& x, int& turn)
 {
     double o0 = 0.0, o1 = 0.0;
     if constexpr (std::is_same<PartT, int>::value) {
         if (go) Scene::trip_part(ev, part, o0, o1);
     } else {
-        if (go) Scene::template trip_part<PartT::value>(ev, o0, o1);
+        if (go) team_trip_part_banded<Scene, PartT::value>(ev, o0, o1);
     }
     double (*buf)[64] = x.v[turn & 1];
     ++turn;
@@ -945,7 +984,7 @@ __device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, Par
     return done;
 }
 
-// Scene::kPartLoops: the team runs one trip loop per part (team_trips).  Set by the Mandelbulb, whose parts are long
+// Scene::kPartLoops: the team runs one trip loop per part (team_trips_parts).  Set by the Mandelbulb, whose parts are long
 // chains of their own; the one-trip unions keep the single loop with the part chosen inside the trip (measured: per-part
 // loops made Sphere Cloud and Bumpy Sphere 4-6 % slower).
 template <class Scene, class = void>
@@ -960,8 +999,47 @@ struct SceneShortLastTrip : std::false_type {};
 template <class Scene>
 struct SceneShortLastTrip<Scene, decltype((void)Scene::kLastTrip)> : std::true_type {};
 
+// One whole SDF evaluation at o + d * t for the lanes that are `live`, in a team that picks its trip loops by the sparse
+// flag: Scene::begin, then the trips.  The loops exist twice, for a sparse wave and for a full one, and the flag --
+// constant within an evaluation, the same in the three waves, which is what lets each arm hold its barriers -- picks
+// between them outside the trip loop: each loop holds the layout of the libm forms that suits its waves and no branch on
+// the flag per trip.  THE SHORT LAST TRIP and the one-barrier argument are those of team_trips below.
+template <class Scene, int P, bool SPARSE>
+__device__ __forceinline__ void team_flag_trips(bool& ready, typename Scene::Eval& ev, int lane, TeamXch& x, int& turn)
+{
+#pragma unroll 1      // the count is bounded: keep the loop a loop
+    for (int n = 0; n < Scene::kLastTrip && __any(!ready); ++n) {
+        const bool fin = team_trip<Scene, P, SPARSE>(ev, !ready, lane, x, turn);
+        if (!ready) ready = fin;
+    }
+}
+template <class Scene, bool SPARSE>
+__device__ __forceinline__ void team_flag_evaluation(int part, bool live, vec3 o, vec3 d, double t, typename Scene::Eval& ev, int lane,
+                                                     TeamXch& x, int& turn)
+{
+    bool ready = true;
+    if (live) ready = Scene::begin(ev, o + d * t, SPARSE);
+    if (part == 0) team_flag_trips<Scene, 0, SPARSE>(ready, ev, lane, x, turn);
+    else if (part == 1) team_flag_trips<Scene, 1, SPARSE>(ready, ev, lane, x, turn);
+    else team_flag_trips<Scene, 2, SPARSE>(ready, ev, lane, x, turn);
+    if (__any(!ready)) {                  // only lanes entering trip Scene::kLastTrip are left
+        if (!ready) Scene::trip_last(ev);
+    }
+}
+template <class Scene>
+__device__ __forceinline__ void team_evaluate(int part, bool live, vec3 o, vec3 d, double t, typename Scene::Eval& ev, int lane, TeamXch& x,
+                                              int& turn)
+{
+    static_assert(ScenePartLoops<Scene>::value && SceneShortLastTrip<Scene>::value, "built for the Mandelbulb's loops");
+    part = __builtin_amdgcn_readfirstlane(part);
+    if (team_sparse(live)) team_flag_evaluation<Scene, true>(part, live, o, d, t, ev, lane, x, turn);
+    else team_flag_evaluation<Scene, false>(part, live, o, d, t, ev, lane, x, turn);
+}
+
+// The loops of the kernels that keep the previous forms (resume_team_kernel, the fused pipeline_kernel, every scene without
+// kSparseFlag), as they were.
 // The trips of one evaluation of every live ray (ready: the lane's value is ready; `ev` as Scene::begin left it).
-// `trip(part, go)` is team_trip bound to the team's exchange and barrier.  With per-part loops the part is dispatched
+// `trip(part, go)` is team_trip_banded bound to the team's exchange and barrier.  With per-part loops the part is dispatched
 // once, outside the trip loop, on a wave-uniform scalar: each wave's loop holds only its own part's chain, with no
 // branch on the part per trip.
 // THE SHORT LAST TRIP: every caller begins the evaluation of ALL its live lanes right before the call (no lane comes in
@@ -972,7 +1050,7 @@ struct SceneShortLastTrip<Scene, decltype((void)Scene::kLastTrip)> : std::true_t
 // barrier it saves): no exchange, no barrier, `turn` stays.  The exchanges that do happen still alternate between the
 // two halves of TeamXch, so its one-barrier argument holds.
 template <class Scene, int P, class Trip>
-__device__ __forceinline__ void team_trips_part(bool& ready, const Trip& trip)
+__device__ __forceinline__ void team_trips_banded_part(bool& ready, const Trip& trip)
 {
     if constexpr (SceneShortLastTrip<Scene>::value) {
 #pragma unroll 1      // the count is bounded: keep the loop a loop
@@ -992,9 +1070,9 @@ __device__ __forceinline__ void team_trips(int part, bool& ready, typename Scene
 {
     if constexpr (ScenePartLoops<Scene>::value) {
         part = __builtin_amdgcn_readfirstlane(part);
-        if (part == 0) team_trips_part<Scene, 0>(ready, trip);
-        else if (part == 1) team_trips_part<Scene, 1>(ready, trip);
-        else team_trips_part<Scene, 2>(ready, trip);
+        if (part == 0) team_trips_banded_part<Scene, 0>(ready, trip);
+        else if (part == 1) team_trips_banded_part<Scene, 1>(ready, trip);
+        else team_trips_banded_part<Scene, 2>(ready, trip);
         if constexpr (SceneShortLastTrip<Scene>::value) {
             if (__any(!ready)) {                  // only lanes entering trip Scene::kLastTrip are left
                 if (!ready) Scene::trip_last(ev);
@@ -1040,9 +1118,13 @@ __global__ __launch_bounds__(64 * kTeam) void march_rays_team_kernel(MarchCfg cf
     typename Scene::Eval ev;
     int turn = 0;
     while (__any(!done)) {
-        bool ready = true;
-        if (!done) ready = Scene::begin(ev, o + d * s.te);
-        team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
+        if constexpr (SceneSparseFlag<Scene>::value) {
+            team_evaluate<Scene>(part, !done, o, d, s.te, ev, lane, xch, turn);
+        } else {
+            bool ready = true;
+            if (!done) ready = Scene::begin(ev, o + d * s.te);
+            team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip_banded<Scene>(ev, go, P, lane, xch, turn); });
+        }
         if (!done) done = s.step(Scene::value(ev), cfg);
     }
     if (have && part == 0) {
@@ -1141,7 +1223,7 @@ __global__ __launch_bounds__(64 * kTeam) void resume_team_kernel(const KernelArg
         // ---- one whole SDF evaluation for every live ray, trips shared by the team -------------------
         bool ready = true;
         if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-        team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, xch, turn); });
+        team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip_banded<Scene>(ev, go, P, lane, xch, turn); });
         bool park = false;
         if (active) {
             ++nev;

@@ -193,6 +193,28 @@ RM_MATH_HD double rm_pow_half(double x)
 #endif
     return rm_pow(x, 0.5);
 }
+// The same with the live-lane test taken out: a team's live lanes only drop out within one SDF evaluation, so its
+// kernels count them once, before Scene::begin, and hand the answer down as a wave-uniform flag (rm_kernels.h
+// team_sparse) instead of paying a ballot, a count and a branch in every trip.  sparse: the guarded root is tried, and
+// it is the way the code falls through; the full pow behind the guard sits out of line.  Same bits either way.
+RM_MATH_HD double rm_pow_half_sparse(double x, bool sparse)
+{
+    if (__builtin_expect(sparse, 1)) {
+        bool safe;
+        double r = rm_pow_half_guard(x, &safe);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const bool any_unsafe = __any(!safe) != 0;
+#else
+        const bool any_unsafe = !safe;
+#endif
+        if (__builtin_expect(any_unsafe, 0)) {
+            const double full = rm_pow(x, 0.5);
+            r = safe ? r : full;
+        }
+        return r;
+    }
+    return rm_pow(x, 0.5);
+}
 // pow(x, ya) and pow(x, yb) sharing the one log(x) they both start from (catalog.py:280,283:
 // r ** 7.0 and r ** 8.0 of the same r); each result is bit-identical to a separate rm_pow call.
 RM_MATH_HD void rm_pow2(double x, double ya, double yb, double* ra, double* rb)

@@ -71,6 +71,41 @@ RM_MATH_HD bool rm_band_needed(bool lane_selects)
     return true;
 }
 
+// ONE RARE-PATH TEST PER CALL (the layout of the team forms below and of rm_math_atan.h).  A taken branch costs a wave
+// that is alone on its SIMD about 47 cycles, whether its condition was ready long before or not; a branch that is not
+// taken costs about one (tools/ubench/branch_cost.hip).  A form that jumps over the block of every
+// band its lanes do not need therefore pays for each band it skips.  The team forms are laid out the other way round:
+// one test at entry asks whether some live lane needs anything but the common band, and sends the wave to the general
+// body (every band behind its own ballot, as above) only then; otherwise the common band runs as straight-line
+// fall-through code with no ballot and no band select.  Both bodies call the same band functions, so the arithmetic is
+// stated once and the bits are the same whichever way the wave goes.
+// The layout is a bet on the wave: it pays where the live lanes agree -- a lone ray, a handful -- and loses where they
+// do not, because a wave of 64 unrelated lanes needs some rare band in nearly every call and then jumps out of line
+// and back, two taken branches a call.  Every team form is therefore a template on COMMON: true is the layout above,
+// false the BANDED form (rm_*_team_banded: every band behind its own ballot, inline, no entry test).  The banded forms
+// keep the text they had before the layout, statement for statement -- the compiler's schedule follows the statements,
+// and the kernels that keep them (resume_team_kernel, the fused pipeline_kernel) must compile to what they were -- so
+// they restate the arithmetic once more and are held to the dense forms and to libm like the others
+// (tests/test_math_exact_team_common.py).  A team picks once per SDF evaluation, by the count of its live lanes
+// (rm_kernels.h team_sparse); rm_acos<true>, rm_atan2<true> and rm_sincos<true> name the COMMON forms.
+// `site` names the test (RM_SITE_*).  The host check build decides it per lane -- a wave of one -- unless the harness
+// defines RM_TEAM_PATH_FORCE(lane_rare, site) to send a call down either body whatever its argument
+// (tests/test_math_exact_team_common.py).
+// (the hint has to stand in the `if` itself: inside an inlined function it is dropped before inlining)
+#define RM_UNLIKELY(c) __builtin_expect(!!(c), 0)
+enum { RM_SITE_ACOS = 0, RM_SITE_SINCOS = 1, RM_SITE_DO_SIN = 2, RM_SITE_ATAN2_ENTRY = 3, RM_SITE_ATAN2_FORM = 4 };
+RM_MATH_HD bool rm_team_rare(bool lane_rare, int site)
+{
+    (void)site;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __any(lane_rare) != 0;
+#elif defined(RM_TEAM_PATH_FORCE)
+    return RM_TEAM_PATH_FORCE(lane_rare, site);
+#else
+    return lane_rare;
+#endif
+}
+
 // TAYLOR_SIN(xx, x, dx): x + ((POLYNOMIAL(xx)*x - 0.5*dx)*xx + dx)
 RM_MATH_HD double rm_taylor_sin(double x, double dx)
 {
@@ -130,9 +165,34 @@ RM_MATH_HD double rm_do_cos(double a, double da)
     return cs + cor;
 }
 
-// do_sin for a team wave: the table form is the value, the Taylor form and its select run only for a wave that
-// holds a lane below 0.126
-RM_MATH_HD double rm_do_sin_team(double a, double da)
+// do_sin(x, dx) above 0.126: the table form (the arithmetic of rm_do_sin's `tab`)
+RM_MATH_HD double rm_do_sin_table(double a, double da)
+{
+    typedef SinCosK K;
+    const double aa = rm_fabs(a);
+    const double dx = (a <= 0.0) ? -da : da;
+    const double u = K::big + aa;
+    const double x = aa - (u - K::big);
+    const int k = rm_sincos_row(u);
+    const double sn = tab_sincos(k, 0), ssn = tab_sincos(k, 1), cs = tab_sincos(k, 2), ccs = tab_sincos(k, 3);
+    const double xx = x * x;
+    const double s = x + rm_fma(x * xx, rm_fma(xx, K::sn5, K::sn3), dx);
+    const double c = rm_fma(x, dx, xx * rm_fma(xx, rm_fma(xx, K::cs6, K::cs4), K::cs2));
+    const double cor = rm_fma(s, cs, rm_fnma(c, sn, rm_fma(s, ccs, ssn)));
+    return __builtin_copysign(sn + cor, a);
+}
+
+// do_sin for a team wave: the table form is the value; the Taylor form and its select run only for a wave that holds
+// a lane below 0.126 (|a| is known only after the reduction: this test is its own).  COMMON: the table form falls
+// through and the Taylor block sits out of line
+RM_MATH_HD double rm_do_sin_taylor_into(double a, double da, bool in_taylor, double res)
+{
+    const double taylor = rm_taylor_sin(a, da);                        // uses dx before the sign flip, as s_sin.c does
+    return in_taylor ? taylor : res;
+}
+// do_sin for a team wave, banded: the table form is the value, the Taylor form and its select run, inline, only for a
+// wave that holds a lane below 0.126
+RM_MATH_HD double rm_do_sin_team_banded(double a, double da)
 {
     typedef SinCosK K;
     const double aa = rm_fabs(a);
@@ -153,11 +213,73 @@ RM_MATH_HD double rm_do_sin_team(double a, double da)
     return res;
 }
 
+template <bool COMMON = true>
+RM_MATH_HD double rm_do_sin_team(double a, double da)
+{
+    if constexpr (!COMMON) return rm_do_sin_team_banded(a, da);
+    const bool in_taylor = rm_fabs(a) < 0.126;
+    double res = rm_do_sin_table(a, da);
+    if (RM_UNLIKELY(rm_team_rare(in_taylor, RM_SITE_DO_SIN))) res = rm_do_sin_taylor_into(a, da, in_taylor, res);
+    return res;
+}
+
+// reduce_sincos with range 1 folded in (rm_sincos below: xn = 0 there, so b == x and db == +0)
+RM_MATH_HD void rm_sincos_reduce(double x, bool r1, double* b_out, double* db_out, uint32_t* n_out)
+{
+    typedef SinCosK K;
+    const double t = rm_fma(x, K::hpinv, K::toint);
+    const double xn = r1 ? 0.0 : (t - K::toint);
+    const uint32_t n = r1 ? 0u : (uint32_t)rm_asuint64(t);
+    const double y = rm_fnma(xn, K::mp2, rm_fnma(xn, K::mp1, x));
+    const double t2 = rm_fnma(xn, K::pp3, y);
+    double db = rm_fnma(K::pp3, xn, y - t2);
+    const double b = rm_fnma(xn, K::pp4, t2);
+    db = db + rm_fnma(xn, K::pp4, t2 - b);
+    *b_out = b; *db_out = db; *n_out = n;
+}
+
+// range 3 (and 1, n = 0) routing: do_sincos(a, da, n) = (n & 1 ? do_cos : do_sin), negated when n & 2
+RM_MATH_HD void rm_sincos_route(uint32_t n, double dS, double dC, double* s_out, double* c_out)
+{
+    const uint32_t m = n + 1u;
+    double s = (n & 1u) ? dC : dS;
+    s = (n & 2u) ? -s : s;
+    double c = (m & 1u) ? dC : dS;
+    c = (m & 2u) ? -c : c;
+    *s_out = s; *c_out = c;
+}
+
+// range 2's inputs to do_sin / do_cos, selected over the reduced argument
+RM_MATH_HD void rm_sincos_r2_inputs(double ax, bool r2, double b, double db, double* aS, double* daS, double* aC, double* daC)
+{
+    typedef SinCosK K;
+    const double tt = K::hp0 - ax;
+    const double a2 = tt + K::hp1;
+    const double da2 = (tt - a2) + K::hp1;
+    *aS = r2 ? a2 : b, *daS = r2 ? da2 : db, *aC = r2 ? tt : b, *daC = r2 ? K::hp1 : db;
+}
+
+// range 2's outputs and the arguments below 2^-26 or beyond the claimed range, selected over the routed values
+RM_MATH_HD void rm_sincos_edge_outputs(double x, uint32_t k, bool r2, double dS, double dC, double* s_io, double* c_io)
+{
+    double s = *s_io, c = *c_io;
+    const double s2 = __builtin_copysign(dC, x);
+    s = r2 ? s2 : s, c = r2 ? dS : c;
+    s = (k < 0x3e500000u) ? x : s;                      // |x| < 2^-26
+    c = (k < 0x3e400000u) ? 1.0 : c;                    // |x| < 2^-27
+    const double bad = __builtin_nan("");                // inf / nan -> nan; __branred range unclaimed
+    const bool huge = k >= 0x419921fbu;
+    *s_io = huge ? bad : s;
+    *c_io = huge ? bad : c;
+}
+
 // rm_sincos for a team wave (the ranges and the routing are those of rm_sincos below).  Range 2's inputs to do_sin /
-// do_cos, its outputs, and the arguments below 2^-26 or beyond the claimed range are served by selects; here those
-// run only in a wave that holds such a lane (two ballots, one for the inputs and one for the outputs), and a wave of
-// range 1 and 3 arguments goes straight through.
-RM_MATH_HD void rm_sincos_team(double x, double* sin_out, double* cos_out)
+// do_cos, its outputs, and the arguments below 2^-26 or beyond the claimed range are served by selects.
+// COMMON: those live in the general body, which a wave enters only when it holds such a lane (ONE RARE-PATH TEST PER
+// CALL above: k is there at entry); a wave of range 1 and 3 arguments inside [2^-26, 105414350) falls through reduction,
+// do_sin, do_cos and routing.  Banded: they run inline behind two ballots, one for the inputs and one for the outputs.
+// rm_sincos for a team wave, banded: range 2's inputs and the edge outputs run inline behind two ballots
+RM_MATH_HD void rm_sincos_team_banded(double x, double* sin_out, double* cos_out)
 {
     typedef SinCosK K;
     const uint32_t k = (uint32_t)(rm_asuint64(x) >> 32) & 0x7fffffffu;
@@ -182,7 +304,7 @@ RM_MATH_HD void rm_sincos_team(double x, double* sin_out, double* cos_out)
         const double da2 = (tt - a2) + K::hp1;
         aS = r2 ? a2 : b, daS = r2 ? da2 : db, aC = r2 ? tt : b, daC = r2 ? K::hp1 : db;
     }
-    const double dS = rm_do_sin_team(aS, daS);
+    const double dS = rm_do_sin_team_banded(aS, daS);
     const double dC = rm_do_cos(aC, daC);
 
     const uint32_t m = n + 1u;
@@ -204,6 +326,34 @@ RM_MATH_HD void rm_sincos_team(double x, double* sin_out, double* cos_out)
     *cos_out = c;
 }
 
+template <bool COMMON = true>
+RM_MATH_HD void rm_sincos_team(double x, double* sin_out, double* cos_out)
+{
+    if constexpr (!COMMON) return rm_sincos_team_banded(x, sin_out, cos_out);
+    const uint32_t k = (uint32_t)(rm_asuint64(x) >> 32) & 0x7fffffffu;
+    const bool r1 = k < 0x3feb6000u;
+    const bool r2 = !r1 & (k < 0x400368fdu);
+    const bool edge = r2 | (k - 0x3e500000u >= 0x419921fbu - 0x3e500000u);
+    double b, db, s, c;
+    uint32_t n;
+    if (RM_UNLIKELY(rm_team_rare(edge, RM_SITE_SINCOS))) {
+        double aS, daS, aC, daC;
+        rm_sincos_reduce(x, r1, &b, &db, &n);
+        rm_sincos_r2_inputs(rm_fabs(x), r2, b, db, &aS, &daS, &aC, &daC);
+        const double dS = rm_do_sin_team<true>(aS, daS);
+        const double dC = rm_do_cos(aC, daC);
+        rm_sincos_route(n, dS, dC, &s, &c);
+        rm_sincos_edge_outputs(x, k, r2, dS, dC, &s, &c);
+    } else {
+        rm_sincos_reduce(x, r1, &b, &db, &n);
+        const double dS = rm_do_sin_team<true>(b, db);
+        const double dC = rm_do_cos(b, db);
+        rm_sincos_route(n, dS, dC, &s, &c);
+    }
+    *sin_out = s;
+    *cos_out = c;
+}
+
 // sin(x) and cos(x) together, branch-free.  __sin and __cos (s_sin.c) pick one of four argument
 // ranges; every range ends in do_sin on one (a, da) pair and do_cos on another:
 //   |x| < 0.855469          sin = do_sin(x, 0)                         cos = do_cos(x, 0)
@@ -214,7 +364,7 @@ template <bool U = false>
 RM_MATH_HD void rm_sincos(double x, double* sin_out, double* cos_out)
 {
     typedef SinCosK K;
-    if constexpr (U) return rm_sincos_team(x, sin_out, cos_out);      // what follows is the dense form: U never gets here
+    if constexpr (U) return rm_sincos_team<true>(x, sin_out, cos_out);      // what follows is the dense form: U never gets here
     const uint32_t k = (uint32_t)(rm_asuint64(x) >> 32) & 0x7fffffffu;
     const double ax = rm_fabs(x);
     const bool r1 = k < 0x3feb6000u;

@@ -292,7 +292,11 @@ __device__ __forceinline__ bool early_handover(const KernelArgs&, const E&, long
 // left in the kernel arguments, the camera, the output pointers and the queue fields are fetched at entry and sit in scalar
 // registers through every trip loop (36 of them against 17 in march_rays_team_kernel), and the loops rebuild their
 // 64-bit constants on every trip for want of registers.
-template <class Scene, class Strat, bool BATCH>
+// BY_FLAG: the trip loops picked by the team's sparse flag (rm_kernels.h team_evaluate), or the one set in the forms
+// from before the flag (team_trips).  The fused kernel keeps the latter: with the two sets the frames of the strategies that keep it
+// and the batches lose, while the split form's team kernel gains (DESIGN.md section 3 "Team libm forms: one rare-path
+// test per call").
+template <class Scene, class Strat, bool BATCH, bool BY_FLAG>
 __device__ __forceinline__ void pipe_team_role(const KernelArgs& a, const KernelArgs& ar, PipeTeamLds& L, const int part, const int lane)
 {
     WaveAcc acc;
@@ -399,9 +403,13 @@ __device__ __forceinline__ void pipe_team_role(const KernelArgs& a, const Kernel
 
         // ---- one whole SDF evaluation for every live ray, trips shared by the team -------------------
         ++since_try;
-        bool ready = true;
-        if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
-        team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip<Scene>(ev, go, P, lane, L.xch, turn); });
+        if constexpr (BY_FLAG && SceneSparseFlag<Scene>::value) {
+            team_evaluate<Scene>(part, active, origin, dir, s.te, ev, lane, L.xch, turn);      // ray.py:15-17
+        } else {
+            bool ready = true;
+            if (active) ready = Scene::begin(ev, origin + dir * s.te);   // ray.py:15-17
+            team_trips<Scene>(part, ready, ev, [&](auto P, bool go) { return team_trip_banded<Scene>(ev, go, P, lane, L.xch, turn); });
+        }
         const int live = a.trace ? __popcll(__ballot(active)) : 0;
         if (active) {
             ++nev;
@@ -497,7 +505,7 @@ __device__ __forceinline__ void pipeline_body(const KernelArgs& ka, const Kernel
         // allocate a few more VGPRs)
         const int team = wave_role / kTeam;
         const int part = wave_role % kTeam;
-        pipe_team_role<Scene, Strat, BATCH>(a, a, reinterpret_cast<PipeTeamLds*>(s_role)[team], part, lane);
+        pipe_team_role<Scene, Strat, BATCH, false>(a, a, reinterpret_cast<PipeTeamLds*>(s_role)[team], part, lane);
         return;
     }
     }
@@ -927,7 +935,7 @@ __global__ __launch_bounds__(64 * kTeam) void pipeline_team_kernel(const KernelA
     rm_load_tables<Scene>();
     __syncthreads();
     if (a.marks && threadIdx.x == 0) atomicMax(&a.stats[kWMarkStart], ~realtime());
-    pipe_team_role<Scene, Strat, BATCH>(a, s_args, T, (int)(threadIdx.x >> 6), lane_id());
+    pipe_team_role<Scene, Strat, BATCH, true>(a, s_args, T, (int)(threadIdx.x >> 6), lane_id());
 }
 
 }  // namespace rm

@@ -163,6 +163,16 @@ struct SceneMandelbulb {                                                        
         e.r = length_a(p);
         return e.r > 4.0;
     }
+    // begin and trip_join for a team (kSparseFlag): whether the wave is sparse -- few live lanes, the guarded root of
+    // rm_pow_half is worth trying -- is decided once per evaluation by the kernel and handed down, instead of a ballot
+    // and a count in every length (rm_math_pow.h rm_pow_half_sparse).  Same expressions, same bits.
+    static constexpr bool kSparseFlag = true;
+    static RM_HD bool begin(Eval& e, vec3 p, bool sparse)
+    {
+        e.p = p; e.z = p; e.dr = 1.0; e.i = 0;
+        e.r = length_a(p, sparse);
+        return e.r > 4.0;
+    }
     // iterations the evaluation ran (8 = no bail-out: the point is close to the set; rm_pipeline.h EARLY HAND-OVER)
     static RM_HD int eval_trips(const Eval& e) { return e.i; }
     // the body of one trip of `for i in range(8)` (:276-290) followed by the loop test and the next
@@ -199,7 +209,7 @@ struct SceneMandelbulb {                                                        
     // result, rm_math_pow.h).  e.i still ends at 8 (eval_trips feeds the producers' early hand-over); e.z is left
     // STALE on purpose -- nothing reads it after an evaluation has ended: value() does not, begin() overwrites it.
     // Taken where the lanes that are still looping share one trip index: sdf() below (lanes enter together) and the
-    // team loops (rm_kernels.h team_trips).  trip() itself stays a full pass for the interleaved producer turn, where
+    // team loops (rm_kernels.h team_evaluate).  trip() itself stays a full pass for the interleaved producer turn, where
     // the lanes of a wave sit at different trips.
     static constexpr int kLastTrip = 7;
     static RM_HD void trip_last(Eval& e)
@@ -219,20 +229,22 @@ struct SceneMandelbulb {                                                        
     // (wave-uniform band skipping inside acos / atan2 / sincos: a team wave is alone on its SIMD with few live
     // lanes, every instruction it does not issue shortens the frame's critical chain -- rm_math_trig.h)
     // trip_part<P>: the part as a template argument -- a team wave runs its trip loop for one part only (kPartLoops,
-    // rm_kernels.h team_trips), so the loop body holds that part's chain and no per-trip branch on the part
+    // rm_kernels.h team_trips_parts), so the loop body holds that part's chain and no per-trip branch on the part
+    // COMMON: the layout of the libm forms -- the common band as fall-through code for a wave whose live lanes agree, or
+    // the banded forms for a full one (rm_math_trig.h ONE RARE-PATH TEST PER CALL); a team picks with its sparse flag
     static constexpr bool kPartLoops = true;
-    template <int P>
+    template <int P, bool COMMON = true>
     static RM_HD void trip_part(const Eval& e, double& o0, double& o1)
     {
         const double power = 8.0;
         if constexpr (P == 0) {
-            double theta = rm_acos<true>(py_max(-1.0, py_min(1.0, e.z.z / py_max(e.r, 1e-12))));
+            double theta = rm_acos_team<COMMON>(py_max(-1.0, py_min(1.0, e.z.z / py_max(e.r, 1e-12))));
             theta *= power;
-            rm_sincos<true>(theta, &o0, &o1);
+            rm_sincos_team<COMMON>(theta, &o0, &o1);
         } else if constexpr (P == 1) {
-            double phi = rm_atan2<true>(e.z.y, e.z.x);
+            double phi = rm_atan2_team<COMMON>(e.z.y, e.z.x);
             phi *= power;
-            rm_sincos<true>(phi, &o0, &o1);
+            rm_sincos_team<COMMON>(phi, &o0, &o1);
         } else {
             rm_pow2(e.r, power - 1.0, power, &o0, &o1);
         }
@@ -250,6 +262,15 @@ struct SceneMandelbulb {                                                        
         e.z = v3(zr * st * cp, zr * st * sp, zr * ct) + e.p;
         if (++e.i >= 8) return true;
         e.r = length_a(e.z);
+        return e.r > 4.0;
+    }
+    static RM_HD bool trip_join(Eval& e, double st, double ct, double sp, double cp, double r7, double zr, bool sparse)
+    {
+        const double power = 8.0;
+        e.dr = r7 * power * e.dr + 1.0;
+        e.z = v3(zr * st * cp, zr * st * sp, zr * ct) + e.p;
+        if (++e.i >= 8) return true;
+        e.r = length_a(e.z, sparse);
         return e.r > 4.0;
     }
     static RM_HD double value(const Eval& e)

@@ -19,13 +19,25 @@ Input: the assembly the build keeps next to each object with KEEP_ASM=1 (after t
   python tools/team_loop_isa.py scene_10.s --json
   python tools/team_loop_isa.py scene_10.s --kernel pipeline_team_kernel --blocks          # the loops block by block
   python tools/team_loop_isa.py scene_10.s --kernel pipeline_team_kernel --without bb.158,bb.162,BB53_169
+  python tools/team_loop_isa.py scene_10.s --kernel pipeline_team_kernel --path BB53_227,bb.228,bb.229,...      # executed per trip
 
 The counts are static: one pass through every block of the loop.  The libm forms of a team wave branch on ballots
 (rm_band_needed<true>, rm_math_trig.h), so what a wave issues is the blocks its live lanes make it enter.  --blocks lists
 a loop's blocks with their counts and branch targets; --without drops the named blocks (the ones a given wave jumps
-over, read off that listing) and prints the mix of the path that is left as a second row.  A fall-through block is
-named bb.<n> after the compiler's comment, unique within one kernel only: give --kernel a name that matches one.  Block
-names change with every build; a name that matches no block of the reported loops is an error, not a shorter sum.
+over, read off that listing) and prints the mix of the path that is left as a second row.  --path is the same from the
+other side: it names the blocks a given wave DOES run (for a lone lane in the common bands: the chain of fall-throughs
+from the loop header, none of the join's alternatives it cannot reach) and prints their mix as the "executed" row -- the
+instructions issued per trip -- with `taken`, the branches on that path whose target is not the next block of the
+path (a taken branch costs a lone wave ~47 cycles, one that falls through ~1: tools/ubench/branch_cost.hip).  Block
+lists that were used are kept with the listings under profiles/.  A --path that no wave can walk -- a block whose
+successors (its branch targets and, unless it ends in s_branch, the next block in layout) do not hold the next block of
+the path -- is an error, not a row.  --fallthrough finds the path itself for loops laid out for it: from the header, no
+conditional branch taken but the back edge and the one to the latch block that holds it, every unconditional one
+followed; a loop in which that walk does not come back to the header gets no row.
+
+A fall-through block is named bb.<n> after the compiler's comment, unique within one kernel only: give --kernel a name
+that matches one.  Block names change with every build; a name that matches no block of the reported loops is an error,
+not a shorter sum.
 """
 from __future__ import annotations
 
@@ -247,6 +259,69 @@ def block_rows(lines, ranges):
     return rows
 
 
+def fallthrough_path(lines, ranges):
+    """the blocks a wave runs from the loop's header if it takes no conditional branch but the one back to the header
+    (or to the latch block that holds that branch), and every unconditional one: the way of a lone lane in the common bands through loops laid out for it (the rare
+    bodies sit out of line behind branches that are not taken; rm_math_trig.h ONE RARE-PATH TEST PER CALL)"""
+    names = [block_name(lines, lo) for lo, hi in ranges]
+    header = names[0]
+
+    def latch_targets(k):
+        return ["BB" + m.group(2) for m in (BRANCH.match(x.split(";", 1)[0]) for x in lines[ranges[k][0]:ranges[k][1] + 1]) if m]
+    path, k = [], 0
+    while k is not None and names[k] not in path:
+        path.append(names[k])
+        lo, hi = ranges[k]
+        nxt = k + 1 if k + 1 < len(names) else None
+        for x in lines[lo:hi + 1]:
+            m = BRANCH.match(x.split(";", 1)[0])
+            if not m:
+                continue
+            t = "BB" + m.group(2)
+            if m.group(1) == "branch":
+                nxt = names.index(t) if t in names else None
+            elif t == header:
+                nxt = None
+                break
+            elif t in names and header in latch_targets(names.index(t)):      # "more trips": on to the latch
+                nxt = names.index(t)
+                break
+        k = nxt
+    return set(path)
+
+
+def taken_branches(lines, ranges, path, strict=True):
+    """branches a wave takes when it runs exactly the blocks of `path`, in layout order, round and round: a block whose
+    last instruction is an unconditional branch, or one of whose conditional branches names a block of the path other
+    than the next one in layout (the loop's back edge among them); conditional branches to blocks off the path fall through"""
+    names = [block_name(lines, lo) for lo, hi in ranges]
+    on = [n for n in names if n in path]
+    taken = 0
+    for lo, hi in ranges:
+        n = block_name(lines, lo)
+        if n not in path:
+            continue
+        nxt = on[(on.index(n) + 1) % len(on)]
+        layout_next = names[names.index(n) + 1] if names.index(n) + 1 < len(names) else None
+        targets, falls = [], True
+        for x in lines[lo:hi + 1]:
+            ins = x.split(";", 1)[0]
+            m = BRANCH.match(ins)
+            if m:
+                targets.append("BB" + m.group(2))
+                falls = m.group(1) != "branch"
+            elif ins.strip() and not ins.strip().endswith(":") and not ins.strip().startswith("."):
+                falls = True
+        if nxt in targets and not (falls and nxt == layout_next):
+            taken += 1
+        elif not (falls and nxt == layout_next):
+            if not strict:
+                return None
+            sys.exit(f"--path cannot be walked: {n} leads to {sorted(set(targets + ([layout_next] if falls and layout_next else [])))}, "
+                     f"not to {nxt}, the next block of the path (see --blocks)")
+    return taken
+
+
 def exchange_part(lines, ranges):
     """the team part a loop belongs to, from its exchange write: TeamXch.v[parity][2 * part][lane] and [2 * part + 1],
     one ds_write2st64_b64 whose offsets (units of 64 doubles) are 2 * part and 2 * part + 1"""
@@ -270,11 +345,16 @@ def main(argv=None):
     ap.add_argument("--blocks", action="store_true", help="list every loop's blocks: counts and branch targets")
     ap.add_argument("--without", default="", help="comma-separated block names (as --blocks prints them) to leave out: "
                                                   "adds a row with the mix of the remaining path to each loop that holds one")
+    ap.add_argument("--path", default="", help="comma-separated block names (as --blocks prints them) that a wave runs: adds an "
+                                               "'executed' row with their mix and the branches taken among them to the loop that holds them")
+    ap.add_argument("--fallthrough", action="store_true",
+                    help="the 'executed' row of every loop for the path that takes no conditional branch but the back edge")
     args = ap.parse_args(argv)
     lines = open(args.asm).read().splitlines()
     funcs = functions(lines)
     wanted = args.kernel or DEFAULT_KERNELS
     without = {w for w in args.without.split(",") if w}
+    path = {w for w in args.path.split(",") if w}
     report = {}
     for w in wanted:
         for name, (a, b) in funcs.items():
@@ -287,6 +367,11 @@ def main(argv=None):
                     if len(kept) < len(r):
                         L["path"] = dict(without=[block_name(lines, lo) for lo, hi in r if (lo, hi) not in kept],
                                          **loop_mix(lines, kept))
+                    loop_path = fallthrough_path(lines, r) if args.fallthrough else path
+                    on_path = [(lo, hi) for lo, hi in r if block_name(lines, lo) in loop_path]
+                    taken = taken_branches(lines, r, loop_path, strict=not args.fallthrough) if on_path else None
+                    if taken is not None:       # (--fallthrough: a loop whose fall-through walk does not come back to its header has no such row)
+                        L["executed"] = dict(blocks=[block_name(lines, lo) for lo, hi in on_path], taken=taken, **loop_mix(lines, on_path))
                     if args.blocks:
                         L["blocks"] = [dict(name=n, targets=t, **mix) for n, mix, t in block_rows(lines, r)]
                     entries.append(L)
@@ -297,6 +382,9 @@ def main(argv=None):
     dropped = {n for r in report.values() for L in r["loops"] for n in L.get("path", {}).get("without", [])}
     if without - dropped:
         sys.exit(f"--without names no block of the reported loops: {sorted(without - dropped)} (see --blocks)")
+    ran = {n for r in report.values() for L in r["loops"] for n in L.get("executed", {}).get("blocks", [])}
+    if path - ran:
+        sys.exit(f"--path names no block of the reported loops: {sorted(path - ran)} (see --blocks)")
     if args.json:
         print(json.dumps(report, indent=1))
         return
@@ -311,6 +399,9 @@ def main(argv=None):
             if "path" in L:
                 print(f"  {'  path':<13} {'':>4} " + " ".join(f"{L['path'][c]:>8}" for c in cols) +
                       "   without " + ",".join(L["path"]["without"]))
+            if "executed" in L:
+                print(f"  {'  executed':<13} {'':>4} " + " ".join(f"{L['executed'][c]:>8}" for c in cols) +
+                      f"   taken {L['executed']['taken']}   blocks " + ",".join(L["executed"]["blocks"]))
             for B in L.get("blocks", []):
                 print(f"    {B['name']:<11} {'':>4} " + " ".join(f"{B[c]:>8}" for c in cols) + "   -> " + " ".join(B["targets"]))
     if len(report) > 1:

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void k(const double* __restrict__ pts, int liv
             ev.z = v3(p.x + acc * 1e-300, p.y, p.z);
             ev.r = length_a(ev.z) * (1.0 + acc * 1e-300);
             ev.dr = 1.0; ev.i = 0;
-            const bool f = team_trip<SceneMandelbulb>(ev, on, part, lane, xch, turn);
+            const bool f = team_trip_banded<SceneMandelbulb>(ev, on, part, lane, xch, turn);
             acc += ev.r + (f ? 1.0 : 0.0);
         }
     } else if (on) {
