@@ -451,6 +451,54 @@ int rm_segment_march_rays(int scene_id, const RmSegmentConfig* cfg, const double
 int rm_segment_render(const RmFrameDesc* desc, const RmSegmentConfig* cfg, double* depth, uint8_t* hit,
                       int32_t* iters, double* cursor, RmTiming* timing);
 
+/* ---- Certified first hit (csrc/rm_certify.h) ------------------------------------------------------------------------------
+ * An error bar on the interval oracle, per ray: a bracket [t_lo, t_hi] and a status such that, in real arithmetic and for a
+ * continuous g(tau) = f(o + tau d),
+ *   * [0, t_lo) is proven free of the solid: every sub-segment of it was discharged by a proof, never by "h <= tol";
+ *   * t_hi is witnessed: the computed pointwise value (the interval program at a degenerate box) has g(t_hi) < 0 (a
+ *     computed 0 is what rounding makes of a tangent contact and witnesses nothing); t_hi = +inf: no witness was found;
+ * so the first hit lies in [t_lo, t_hi].  A probe [a, a + h] is proven free when the interval enclosure has lo > 0 (the
+ * interval oracle's rule) or when g(a) > K h, K = clip(max |der|, k_min, l_global) the dual-interval bound of |g'| over the
+ * probe (the segment tracer's rule, with its caveats: l_global bounds |grad f| times the direction's length, and g must
+ * be continuous -- a repeat of a shape that is not even in the repeated coordinate jumps at cell boundaries).  The probe
+ * loop is the interval oracle's (h0, growth, h_max); an unproven probe halves, g at its end is looked at, and once a
+ * witness b exists the probes stay inside [a, b] and are at most half of it.  Rounding is to nearest.
+ *   RM_CERTIFY_MISS  all of [0, t_max] is proven free (or the ray misses the prune's sphere); t_lo = t_hi = +inf
+ *   RM_CERTIFY_HIT   witnessed, and t_hi - t_lo <= width; t_lo <= t_max
+ *   RM_CERTIFY_OPEN  anything else: no witness (a grazing contact, an enclosure that never clears), an unproven probe
+ *                    shrunk to 2^-50 t_lo (four units in the last place), or max_steps probes made.  The bracket reached is
+ *                    returned and is as sound as any other.
+ * Scenes, errors, stream and timing conventions: exactly as the interval oracle above. */
+#define RM_CERTIFY_MISS 0
+#define RM_CERTIFY_HIT 1
+#define RM_CERTIFY_OPEN 2
+typedef struct RmCertifyConfig {   /* every field 0 = its default; the first five as RmIntervalConfig */
+    double t_max;                  /* 100 */
+    double tol;                    /* 1e-5   the interval oracle's tolerance; checked, but no probe is discharged by it */
+    double h0;                     /* 0.25   first probe length */
+    double growth;                 /* 1.5    probe growth across proven space (> 1) */
+    double h_max;                  /* 10     probe ceiling */
+    double bound_radius;           /* rm_certify_render's prune, as RmIntervalConfig.bound_radius */
+    double width;                  /* a HIT's bracket is at most this wide; 0 = 1e-10 (1 + t_lo) */
+    double l_global;               /* 1      the global Lipschitz bound K is clamped to (RmSegmentConfig.l_global) */
+    double k_min;                  /* 1e-6   floor of the directional bound K */
+    int32_t max_steps;             /* 20000  probes per ray (at most RM_INTERVAL_MAX_STEPS); a probe is two evaluations */
+    int32_t reserved;              /* 0 */
+} RmCertifyConfig;
+/* Negative or non-finite fields, growth <= 1 after defaults, max_steps < 0 or > RM_INTERVAL_MAX_STEPS, reserved != 0:
+ * RM_E_BAD_ARG. */
+
+/* Same answer as rm_segment_supported.  Host only. */
+int rm_certify_supported(int scene_id);
+/* The bracket of n explicit rays (directions as given).  t_lo, t_hi: n doubles; status: n bytes (RM_CERTIFY_*); steps (n
+ * int32, optional): the probes made.  cfg may be NULL; its bound_radius is not used here. */
+int rm_certify_march_rays(int scene_id, const RmCertifyConfig* cfg, const double* origins, const double* dirs,
+                          size_t n, double* t_lo, double* t_hi, uint8_t* status, int32_t* steps);
+/* The brackets of rows [row0, row0 + rows) of the frame desc describes (as rm_interval_render).  Per pixel: t_lo, t_hi,
+ * status, steps (optional; 0 for a pruned ray, which is a MISS). */
+int rm_certify_render(const RmFrameDesc* desc, const RmCertifyConfig* cfg, double* t_lo, double* t_hi, uint8_t* status,
+                      int32_t* steps, RmTiming* timing);
+
 /* ---- Affine range (gpu/affine.py) ----------------------------------------------------------------------------------------
  * The third sound evaluation of a scene over a ray segment: revised affine arithmetic with one noise symbol for the march
  * parameter (csrc/rm_affine.h), and the interval oracle's march with that range plugged in (the reference's march_count).

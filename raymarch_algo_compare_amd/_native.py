@@ -35,6 +35,7 @@ EXPORTS = [
     "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy", "rm_debug_math_eval",
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
+    "rm_certify_supported", "rm_certify_march_rays", "rm_certify_render",
     "rm_affine_supported", "rm_affine_range_eval", "rm_affine_march_rays", "rm_affine_render",
     "rm_exact_supported", "rm_exact_march_rays", "rm_exact_render",
     "rm_ssim_scores", "rm_capture", "rm_shade_frames", "rm_score_captures",
@@ -43,6 +44,7 @@ EXPORTS = [
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
 RM_SEGMENT_MAX_STEPS = 40960     # RmSegmentConfig.budget ceiling
+RM_CERTIFY_MISS, RM_CERTIFY_HIT, RM_CERTIFY_OPEN = 0, 1, 2   # the `status` of the rm_certify_* calls
 RM_RANGE_AFFINE, RM_RANGE_MEET = 1, 2   # the `mode` of the rm_affine_* calls
 RM_SCENE_PROGRAM_BASE = 1024
 # RmMathFn (include/rm_hip.h): the device math routines rm_debug_math_eval evaluates
@@ -171,6 +173,13 @@ class RmSegmentConfig(ctypes.Structure):
     _fields_ = [("t_max", ctypes.c_double), ("tol", ctypes.c_double), ("h0", ctypes.c_double), ("kappa", ctypes.c_double),
                 ("h_min", ctypes.c_double), ("h_max", ctypes.c_double), ("k_min", ctypes.c_double), ("l_global", ctypes.c_double),
                 ("bound_radius", ctypes.c_double), ("budget", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class RmCertifyConfig(ctypes.Structure):
+    """The certified first hit's constants (include/rm_hip.h); every field 0 = its default."""
+    _fields_ = [("t_max", ctypes.c_double), ("tol", ctypes.c_double), ("h0", ctypes.c_double), ("growth", ctypes.c_double),
+                ("h_max", ctypes.c_double), ("bound_radius", ctypes.c_double), ("width", ctypes.c_double),
+                ("l_global", ctypes.c_double), ("k_min", ctypes.c_double), ("max_steps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class RmCaptureMaps(ctypes.Structure):
@@ -307,6 +316,10 @@ def load() -> ctypes.CDLL:
         L.rm_segment_sdf_eval.argtypes = [ctypes.c_int, dp, ctypes.c_size_t, dp]
         L.rm_segment_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmSegmentConfig), dp, dp, ctypes.c_size_t, dp, vp, vp]
         L.rm_segment_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmSegmentConfig), vp, vp, vp, vp,
+                                        ctypes.POINTER(RmTiming)]
+        L.rm_certify_supported.argtypes = [ctypes.c_int]
+        L.rm_certify_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmCertifyConfig), dp, dp, ctypes.c_size_t, dp, dp, vp, vp]
+        L.rm_certify_render.argtypes = [ctypes.POINTER(RmFrameDesc), ctypes.POINTER(RmCertifyConfig), vp, vp, vp, vp,
                                         ctypes.POINTER(RmTiming)]
         L.rm_affine_supported.argtypes = [ctypes.c_int]
         L.rm_affine_range_eval.argtypes = [ctypes.c_int, ctypes.c_int, dp, ctypes.c_size_t, dp, vp]
@@ -728,6 +741,44 @@ def segment_render(scene_id: int, cam14, width: int, height: int, cfg: RmSegment
     tm = _timing(warmup, repeats)
     check(L.rm_segment_render(ctypes.byref(d), _ref(cfg), _ptr(depth), _ptr(hit), _ptr(iters), _ptr(cursor), _ref(tm)))
     return _frame_maps(d, tm, depth=depth, hit=hit, iters=iters, cursor=cursor)
+
+
+def certify_config(t_max=0.0, tol=0.0, h0=0.0, growth=0.0, h_max=0.0, bound_radius=0.0, width=0.0, l_global=0.0, k_min=0.0,
+                   max_steps=0) -> RmCertifyConfig:
+    """RmCertifyConfig; 0 = the default (width 0: 1e-10 (1 + t_lo); bound_radius 0: the library's bound, < 0: no prune)."""
+    c = RmCertifyConfig()
+    c.t_max, c.tol, c.h0, c.growth, c.h_max = float(t_max), float(tol), float(h0), float(growth), float(h_max)
+    c.bound_radius, c.width, c.l_global, c.k_min, c.max_steps = float(bound_radius), float(width), float(l_global), float(k_min), int(max_steps)
+    return c
+
+
+def certify_supported(scene_id: int) -> bool:
+    """rm_certify_supported (no GPU needed)."""
+    return load().rm_certify_supported(int(scene_id)) == 1
+
+
+def certify_march_rays(scene_id: int, origins, dirs, cfg: RmCertifyConfig | None = None):
+    """rm_certify_march_rays: (t_lo, t_hi, status (RM_CERTIFY_*), steps) of n explicit rays."""
+    L = init()
+    origins, dirs = _rays(origins, dirs)
+    n = len(dirs)
+    t_lo, t_hi, status, steps = np.empty(n), np.empty(n), np.empty(n, np.uint8), np.empty(n, np.int32)
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_certify_march_rays(int(scene_id), _ref(cfg), origins.ctypes.data_as(dp), dirs.ctypes.data_as(dp), n,
+                                  t_lo.ctypes.data_as(dp), t_hi.ctypes.data_as(dp), _ptr(status), _ptr(steps)))
+    return t_lo, t_hi, status, steps
+
+
+def certify_render(scene_id: int, cam14, width: int, height: int, cfg: RmCertifyConfig | None = None, row0=0, rows=None,
+                   warmup=0, repeats=0) -> dict:
+    """rm_certify_render: t_lo, t_hi, status, steps of rows [row0, row0 + rows); `timing` with repeats > 0."""
+    L = init()
+    d = make_desc(scene_id, 0, cam14, width, height, row0, rows)
+    n = int(width) * int(d.rows)
+    t_lo, t_hi, status, steps = np.empty(n), np.empty(n), np.empty(n, np.uint8), np.empty(n, np.int32)
+    tm = _timing(warmup, repeats)
+    check(L.rm_certify_render(ctypes.byref(d), _ref(cfg), _ptr(t_lo), _ptr(t_hi), _ptr(status), _ptr(steps), _ref(tm)))
+    return _frame_maps(d, tm, t_lo=t_lo, t_hi=t_hi, status=status, steps=steps)
 
 
 def affine_supported(scene_id: int) -> bool:

@@ -29,6 +29,7 @@
 #include "rm_interval_catalogue.h"
 #include "rm_exact.h"
 #include "rm_segment.h"
+#include "rm_certify.h"
 #include "rm_affine.h"
 #include "rm_score.h"
 #include "rm_ssim.h"
@@ -74,6 +75,11 @@ hipError_t launch_segment_march(const void* prog, const SegmentParams& P, const 
                                 double* t, int32_t* iters, double* cursor, hipStream_t s);
 hipError_t launch_segment_render(const void* prog, const SegmentParams& P, const CameraParams& cam, int width, int height,
                                  int row0, int rows, double* depth, uint8_t* hit, int32_t* iters, double* cursor, hipStream_t s);
+// rm_certify.hip: the certified first hit (rm_certify_*)
+hipError_t launch_certify_march(const void* prog, const CertifyParams& P, const double* origins, const double* dirs, size_t n,
+                                double* t_lo, double* t_hi, uint8_t* status, int32_t* steps, hipStream_t s);
+hipError_t launch_certify_render(const void* prog, const CertifyParams& P, const CameraParams& cam, int width, int height,
+                                 int row0, int rows, double* t_lo, double* t_hi, uint8_t* status, int32_t* steps, hipStream_t s);
 // rm_affine.hip: the affine range and its march (rm_affine_*)
 hipError_t launch_affine_range(const void* prog, int mode, const double* segs, size_t n, double* out_range, double* out_form,
                                hipStream_t s);
@@ -2244,6 +2250,66 @@ int rm_segment_render(const RmFrameDesc* d, const RmSegmentConfig* cfg, double* 
     const rm::CameraParams cam = camera_of(d->cam);
     rc = once_or_timed(*c.e, timing, g.stream, [&] {
         HIP_TRY(rm::launch_segment_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_iters, d_cursor, g.stream));
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
+}
+
+// ---- certified first hit (rm_certify.h, rm_certify.hip): scenes and programs as the interval oracle --------------------
+
+namespace {
+
+int certify_params(int id, const RmCertifyConfig* cfg, rm::CertifyParams* P)
+{
+    char why[160];
+    if (!rm::certify_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
+        return fail(RM_E_BAD_ARG, "RmCertifyConfig: %s", why);
+    return RM_OK;
+}
+
+}  // namespace
+
+int rm_certify_supported(int scene_id) { return rm_segment_supported(scene_id); }
+
+int rm_certify_march_rays(int scene_id, const RmCertifyConfig* cfg, const double* origins, const double* dirs, size_t n,
+                          double* t_lo, double* t_hi, uint8_t* status, int32_t* steps)
+{
+    rm::CertifyParams P;
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return certify_params(scene_id, cfg, &P); }, nullptr, nullptr, n,
+                    origins && dirs && t_lo && t_hi && status, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_origins = st.in(g.in[0], origins, n * 24);
+    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
+    double* d_lo = st.out(g.out[0], t_lo, n * 8);
+    double* d_hi = st.out(g.out[1], t_hi, n * 8);
+    uint8_t* d_status = st.out(g.out[2], status, n);
+    int32_t* d_steps = st.out(g.out[3], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_certify_march(c.prog, P, d_origins, d_dirs, n, d_lo, d_hi, d_status, d_steps, g.stream));
+    return st.finish();
+}
+
+int rm_certify_render(const RmFrameDesc* d, const RmCertifyConfig* cfg, double* t_lo, double* t_hi, uint8_t* status, int32_t* steps,
+                      RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    rm::CertifyParams P;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return certify_params(d->scene_id, cfg, &P); }, d, timing, n, t_lo && t_hi && status,
+                    "t_lo, t_hi and status are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    double* d_lo = st.out(g.out[0], t_lo, n * 8);
+    double* d_hi = st.out(g.out[1], t_hi, n * 8);
+    uint8_t* d_status = st.out(g.out[2], status, n);
+    int32_t* d_steps = st.out(g.out[3], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, g.stream, [&] {
+        HIP_TRY(rm::launch_certify_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_lo, d_hi, d_status, d_steps, g.stream));
         return (int)RM_OK;
     });
     return rc ? rc : st.finish();

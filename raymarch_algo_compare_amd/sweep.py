@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import exact_oracle, faithful_segment, interval_oracle, registry, scoring
+from . import certified_oracle, exact_oracle, faithful_segment, interval_oracle, registry, scoring
 from .camera import Camera
 from .collector import HipCollector
 from .config import MarchConfig
@@ -80,6 +80,11 @@ ORACLES = ("interval", "exact")
 # scene without an interval extension
 CEILING_FIELDS = ["ceiling_iou", "ceiling_depth_med", "ceiling_iters_median", "ceiling_iters_p95"]
 CEILINGS = ("segment",)
+# with certify (run_sweep(oracle="interval", certify=True)): each frame against the certified first-hit bracket of its
+# viewpoint (certified_oracle.certified_capture) -- the share of pixels the certificate leaves OPEN, the frame's IoU against
+# the certified hit mask with every OPEN pixel counted against the frame and then for it, and |depth - t_hi| over the HIT
+# pixels the frame hits; empty cells for a scene without an interval extension
+CERTIFY_FIELDS = ["cert_open_frac", "cert_iou_lo", "cert_iou_hi", "cert_depth_mae", "cert_depth_p95"]
 # with ssim (run_sweep(oracle=..., ssim=True)): the tertiary tier of scoring.py -- each frame's depth and normal images
 # against the oracle capture's (ssim.py; the frame's normals as GPURunner.capture takes them, at its own hit points).  The
 # oracle captures carry no colour, so the two colour columns are empty cells, as are all four without an oracle capture.
@@ -298,6 +303,33 @@ def oracle_frames_for(scene, width: int, height: int, oracle: str, tol: float, t
             for vp in vps}
 
 
+def certify_columns(frame: Dict, cert: Optional[Dict]) -> Dict:
+    """CERTIFY_FIELDS of one frame against the certified capture of its viewpoint; None (empty cells) without one.  An OPEN
+    pixel's truth is unknown: cert_iou_lo takes it to be the opposite of the frame's answer, cert_iou_hi the frame's own, so
+    the IoU against the true mask lies between the two whatever the OPEN pixels are."""
+    if cert is None:
+        return {k: None for k in CERTIFY_FIELDS}
+    mine = np.asarray(frame["hit"], dtype=bool)
+    hit, open_ = cert["status"] == certified_oracle.HIT, cert["status"] == certified_oracle.OPEN
+    d = scoring._depth_metrics(frame, cert["capture"])
+    return {"cert_open_frac": float(open_.mean()),
+            "cert_iou_lo": scoring._hit_metrics(mine, hit | (open_ & ~mine))["iou"],
+            "cert_iou_hi": scoring._hit_metrics(mine, hit | (open_ & mine))["iou"],
+            "cert_depth_mae": d["mae"], "cert_depth_p95": d["p95"]}
+
+
+def certify_frames_for(scene, width: int, height: int, twins: bool = False) -> Dict[str, Optional[Dict]]:
+    """The certified capture of every curated viewpoint of `scene` (None for each without an interval extension and, with
+    `twins`, without a twin that has one); l_global is the scene's own Lipschitz bound, for a twin too."""
+    vps = viewpoints_for(scene)
+    sound = sound_scene(scene, twins)
+    if sound is None:
+        return {vp.name: None for vp in vps}
+    l_global = max(1.0, float(scene.known_lipschitz_bound() or 1.0))
+    return {vp.name: certified_oracle.certified_capture(sound, Camera(vp.position, vp.target, vp.up, 60.0, width, height),
+                                                        l_global=l_global) for vp in vps}
+
+
 def ceiling_columns(frame: Optional[Dict], oracle: Optional[Dict], device_score: bool = False) -> Dict:
     """CEILING_FIELDS of one faithful_capture frame against the oracle capture of its viewpoint; None (empty cells) without
     them.  `device_score`: the residual comes from the device (score_device.residual_batch)."""
@@ -338,7 +370,7 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
               oracle: Optional[str] = None, oracle_tol: float = interval_oracle.DEFAULT_TOL,
               ceiling: Optional[str] = None, ceiling_tol: float = faithful_segment.DEFAULT_TOL, ssim: bool = False,
               oracle_twins: bool = False, device_capture: bool = False, device_score: bool = False, features: bool = False,
-              feature_seed: int = 0) -> List[Dict]:
+              feature_seed: int = 0, certify: bool = False) -> List[Dict]:
     """Sweep `mode` over the curated viewpoints of the named scenes (default: all 20) for the named
     strategies (default: all 11).  Unknown names raise KeyError.  Returns the rows; writes CSV (or JSON
     for a .json path) when `out_path` is given.  oracle="interval": every row also scores its frame against the
@@ -359,7 +391,10 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
     count-derived and percentile columns equal the host's, the means differ by summation order only.  Off, the output is
     unchanged.  features=True: every row also carries FEATURE_FIELDS, the discovery features of its (scene, viewpoint),
     computed on the device once per scene (feature_columns_for); the samples are drawn from
-    np.random.default_rng(feature_seed), scene after scene, viewpoint after viewpoint.  Off, the output is unchanged."""
+    np.random.default_rng(feature_seed), scene after scene, viewpoint after viewpoint.  Off, the output is unchanged.
+    certify=True (only with oracle="interval"): every row also carries CERTIFY_FIELDS, its frame against the certified
+    first-hit bracket of its viewpoint (certify_columns; one certified frame per scene and viewpoint), after every other
+    column.  Off, the output is unchanged."""
     if oracle is not None and oracle not in ORACLES:                       # before anything touches the GPU
         raise ValueError(f"unknown oracle {oracle!r}: one of {ORACLES}")
     if ceiling is not None and ceiling not in CEILINGS:
@@ -370,6 +405,8 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
         raise ValueError("device_capture computes the normals of the ssim columns: pass ssim=True")
     if device_score and oracle is None:
         raise ValueError("device_score scores against an oracle: pass oracle=")
+    if certify and oracle != "interval":
+        raise ValueError("certify puts an error bar on the interval oracle: pass oracle=\"interval\"")
     scenes = registry.get_all_scenes() if not scene_names else [_need(registry.get_scene_by_name(n), "scene", n) for n in scene_names]
     strats = ([registry.get_strategy_by_name(k) for k in registry.list_strategies()] if not strategy_names
               else [_need(registry.get_shader_strategy(n) or registry.get_strategy_by_name(n), "strategy", n) for n in strategy_names])
@@ -385,7 +422,7 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
                                            oracle_frames_for(scene, width, height, oracle, oracle_tol, oracle_twins))
         ccols = (ceiling_columns_for(scene, width, height, truth, ceiling_tol, oracle_twins, device_score)
                  if ceiling is not None else None)
-        kept: Optional[List] = [] if ssim or device_score else None
+        kept: Optional[List] = [] if ssim or device_score or certify else None
         for strat in strats:
             if strat.has_lipschitz:
                 strat.lipschitz = scene.known_lipschitz_bound() or 1.0      # run_once wiring (reference main.py:58-61)
@@ -402,6 +439,10 @@ def run_sweep(scene_names: Optional[Sequence[str]] = None, strategy_names: Optio
             fcols = feature_columns_for(scene, width, height, feature_rng)
             for row in rows[first:]:
                 row.update(fcols[row["viewpoint"]])
+        if certify:
+            cert = certify_frames_for(scene, width, height, oracle_twins)
+            for row, name, _, hit_map, depth_map in kept:
+                row.update(certify_columns({"hit": hit_map, "depth": depth_map}, cert.get(name)))
     if out_path:
         write_rows(rows, out_path)
     return rows
@@ -414,7 +455,7 @@ def write_rows(rows: List[Dict], path: str) -> None:
         return
     fields = ROW_FIELDS + (ORACLE_FIELDS if rows and "oracle_iou" in rows[0] else []) + \
         (CEILING_FIELDS if rows and "ceiling_iou" in rows[0] else []) + (SSIM_FIELDS if rows and "depth_ssim" in rows[0] else []) + \
-        (FEATURE_FIELDS if rows and "feat_hit_rate" in rows[0] else [])
+        (FEATURE_FIELDS if rows and "feat_hit_rate" in rows[0] else []) + (CERTIFY_FIELDS if rows and "cert_open_frac" in rows[0] else [])
     with open(path, "w", newline="", encoding="utf-8") as f:
         w = csv.DictWriter(f, fieldnames=fields)
         w.writeheader()
@@ -459,6 +500,9 @@ def main(argv=None) -> int:
                     help="with --oracle / --ceiling: score a catalogue scene that has no interval form against its program twin "
                          "(Menger, Bad Lipschitz Sphere, Bumpy Sphere, Gyroid, Box Lattice); a twin's ceiling is traced with l_global = the "
                          "scene's Lipschitz bound, not the default 1")
+    ap.add_argument("--certify", action="store_true",
+                    help="with --oracle interval: add the cert_* columns, every frame against the certified first-hit bracket of "
+                         "its viewpoint (the interval oracle's per-ray error bar)")
     ap.add_argument("--features", action="store_true",
                     help="add the discovery features of every row's (scene, viewpoint), computed on the device (the feat_* columns)")
     ap.add_argument("--feature-seed", type=int, default=0, help="seed of the features' random samples")
@@ -469,13 +513,16 @@ def main(argv=None) -> int:
         ap.error("--device-capture needs --ssim")
     if a.device_score and a.oracle is None:
         ap.error("--device-score needs --oracle")
+    if a.certify and a.oracle != "interval":
+        ap.error("--certify needs --oracle interval")
     if a.oracle_twins and a.oracle is None and a.ceiling is None:
         ap.error("--oracle-twins needs --oracle or --ceiling")
     rows = run_sweep([s for s in a.scenes.split(",") if s], [s for s in a.strategies.split(",") if s], a.mode, a.width, a.height,
                      [int(v) for v in a.budgets.split(",")], [float(v) for v in a.epsilons.split(",")], a.cap, a.hit_threshold,
                      a.out, verbose=True, grid=a.grid, oracle=a.oracle, oracle_tol=a.oracle_tol,
                      ceiling=a.ceiling, ceiling_tol=a.ceiling_tol, ssim=a.ssim, oracle_twins=a.oracle_twins,
-                     device_capture=a.device_capture, device_score=a.device_score, features=a.features, feature_seed=a.feature_seed)
+                     device_capture=a.device_capture, device_score=a.device_score, features=a.features, feature_seed=a.feature_seed,
+                     certify=a.certify)
     print(f"{len(rows)} rows -> {a.out}")
     return 0
 
