@@ -766,6 +766,13 @@ enum RmMathFn {
  * Synchronous.  RM_E_BAD_ARG for fn out of range, lane_mask == 0 or a NULL buffer the routine needs. */
 int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1);
 
+/* Development / tests: the Mandelbulb's bail-out decision from the squared length (csrc/rm_math_pow.h rm_bail4) on the
+ * device, laid out over wavefronts as rm_debug_math_eval lays its elements out.  decision[e] = 1.0 where
+ * rm_pow(s[e], 0.5) > 4.0 is decided true, else 0.0; band[e] = 1.0 where s[e] lies in the band that takes the root
+ * itself (rm_bail4_band), else 0.0.  sparse != 0: with rm_pow_half_sparse's flag on.  Synchronous.  RM_E_BAD_ARG for
+ * lane_mask == 0 or a NULL buffer. */
+int rm_debug_bail4_eval(const double* s, size_t n, uint64_t lane_mask, int32_t sparse, double* decision, double* band);
+
 /* Store-path probe: writes the 9 B/ray outputs with the render kernel's flush code and no
  * marching, to measure the isolated HBM write bandwidth of the path. */
 int rm_bench_store_path(int32_t width, int32_t rows, void* d_depth, void* d_iters, void* d_hit,

@@ -33,6 +33,7 @@ EXPORTS = [
     "rm_comm_unique_id", "rm_comm_init", "rm_comm_destroy", "rm_shard_rows", "rm_gather_frame", "rm_assemble_frame", "rm_gather_frame_root",
     "rm_runtime_info", "rm_stream_create", "rm_stream_synchronize", "rm_stream_destroy", "rm_debug_poison_queues",
     "rm_debug_set_trace", "rm_debug_get_trace", "rm_scene_program_create", "rm_scene_program_destroy", "rm_debug_math_eval",
+    "rm_debug_bail4_eval",
     "rm_interval_supported", "rm_interval_sdf_eval", "rm_interval_march_rays", "rm_interval_render",
     "rm_segment_supported", "rm_segment_sdf_eval", "rm_segment_march_rays", "rm_segment_render",
     "rm_certify_supported", "rm_certify_march_rays", "rm_certify_render",
@@ -307,6 +308,7 @@ def load() -> ctypes.CDLL:
         L.rm_debug_get_trace.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), vp, vp, ctypes.c_int64,
                                          ctypes.POINTER(ctypes.c_uint32)]
         L.rm_debug_math_eval.argtypes = [ctypes.c_int32, dp, dp, ctypes.c_size_t, ctypes.c_uint64, dp, dp]
+        L.rm_debug_bail4_eval.argtypes = [dp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int32, dp, dp]
         L.rm_interval_supported.argtypes = [ctypes.c_int]
         L.rm_interval_sdf_eval.argtypes = [ctypes.c_int, dp, dp, ctypes.c_size_t, dp, dp]
         L.rm_interval_march_rays.argtypes = [ctypes.c_int, ctypes.POINTER(RmIntervalConfig), dp, dp, ctypes.c_size_t, dp, vp, vp]
@@ -591,6 +593,18 @@ def debug_math_eval(fn, a, b=None, lane_mask=(1 << 64) - 1):
     check(L.rm_debug_math_eval(MATH_FNS[name] if name in MATH_FNS else int(fn), ptr(a), ptr(b), len(a),
                                int(lane_mask), ptr(out0), ptr(out1)))
     return out0, out1
+
+
+def debug_bail4_eval(s, sparse, lane_mask=(1 << 64) - 1):
+    """rm_debug_bail4_eval: the Mandelbulb's bail-out decision from the squared length (csrc/rm_math_pow.h rm_bail4) on the
+    device, one element per live lane of `lane_mask`.  Returns (decision, band) as bool arrays."""
+    L = init()
+    s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+    out0, out1 = np.empty_like(s), np.empty_like(s)
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(L.rm_debug_bail4_eval(s.ctypes.data_as(dp), len(s), int(lane_mask), int(bool(sparse)), out0.ctypes.data_as(dp),
+                                out1.ctypes.data_as(dp)))
+    return out0 != 0.0, out1 != 0.0
 
 
 def interval_config(t_max=0.0, tol=0.0, h0=0.0, growth=0.0, h_max=0.0, normal_eps=0.0, bound_radius=0.0,

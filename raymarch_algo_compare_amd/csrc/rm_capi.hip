@@ -57,6 +57,7 @@ const SceneLaunchers* scene_launchers_program_ext();      // ... of programs wit
 // rm_math_check.hip: the device math routines one by one (rm_debug_math_eval)
 hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1,
                              hipStream_t s);
+hipError_t launch_bail4_check(bool sparse, const double* s, size_t n, uint64_t lane_mask, double* decision, double* band, hipStream_t st);
 // rm_interval.hip: the interval first-hit oracle (rm_interval_*)
 hipError_t launch_interval_sdf(const void* prog, const double* lo, const double* hi, size_t n, double* out_lo, double* out_hi,
                                hipStream_t s);
@@ -1859,6 +1860,23 @@ int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, u
     double* d_out1 = st.out(g.out[1], two_out ? out1 : nullptr, n * 8);
     if ((rc = st.begin())) return rc;
     HIP_TRY(rm::launch_math_check(fn, d_a, d_b, n, lane_mask, d_out0, d_out1, g.stream));
+    return st.finish();
+}
+
+int rm_debug_bail4_eval(const double* s, size_t n, uint64_t lane_mask, int32_t sparse, double* decision, double* band)
+{
+    Entry e;
+    int rc = e.rc();
+    if (rc) return rc;
+    if (lane_mask == 0) return fail(RM_E_BAD_ARG, "lane_mask is 0: no live lane");
+    if (n == 0) return RM_OK;
+    if (!s || !decision || !band) return fail(RM_E_BAD_ARG, "NULL buffer");
+    Staged st(e);
+    const double* d_s = st.in(g.in[0], s, n * 8);
+    double* d_out0 = st.out(g.out[0], decision, n * 8);
+    double* d_out1 = st.out(g.out[1], band, n * 8);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_bail4_check(sparse != 0, d_s, n, lane_mask, d_out0, d_out1, g.stream));
     return st.finish();
 }
 

@@ -69,6 +69,9 @@ RM_HD double pow_half_a(double x) { return rm_pow_half<true>(x); }
 RM_HD double length_a(vec3 a) { return pow_half_a(a.x * a.x + a.y * a.y + a.z * a.z); }
 // length_a for a team wave that already knows whether it is sparse (rm_math_pow.h rm_pow_half_sparse)
 RM_HD double length_a(vec3 a, bool sparse) { return rm_pow_half_sparse(a.x * a.x + a.y * a.y + a.z * a.z, sparse); }
+// the argument of that root on its own (same expression, same operation order): length_a(a, f) is
+// rm_pow_half_sparse(length_sq(a), f), bit for bit
+RM_HD double length_sq(vec3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
 RM_HD vec3 normalized(vec3 a)                                                          // vec3.py:52-56
 {
     double l = length(a);

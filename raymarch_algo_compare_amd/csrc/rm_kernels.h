@@ -936,8 +936,17 @@ __device__ __forceinline__ bool team_sparse(bool live) { return __popcll(__ballo
 // loops).  `turn` counts the team's trips (buffer parity).  Wave-uniform call.  SPARSE, the flag as a constant, picks the
 // layout of the libm forms and the root of the join.  The wave joins from its own two values in registers and reads only
 // the other four from LDS: a wave wrote exactly those two values, so the bits are the same.
+// Scene::kPartJoin: the join is the part's own (Scene::trip_join_part<P>, rm_scenes.h THE JOIN PER PART; set by the
+// Mandelbulb), with `s2` the squared length its part-1 wave keeps in place of the root.  The waves of a team still take the
+// same decisions: the part-1 wave's `done` is rm_bail4 of the squared length, the others' is the root's compare with 4.0,
+// and rm_math_pow.h proves the two equal for every double -- the lock-step of the team (above: same data, same decisions)
+// rests on that proof from here on.
+template <class Scene, class = void>
+struct ScenePartJoin : std::false_type {};
+template <class Scene>
+struct ScenePartJoin<Scene, decltype((void)Scene::kPartJoin)> : std::integral_constant<bool, Scene::kPartJoin> {};
 template <class Scene, int P, bool SPARSE>
-__device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, int lane, TeamXch& x, int& turn)
+__device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, int lane, TeamXch& x, int& turn, double& s2)
 {
     double o0 = 0.0, o1 = 0.0;
     if (go) Scene::template trip_part<P, SPARSE>(ev, o0, o1);
@@ -951,7 +960,8 @@ __device__ __forceinline__ bool team_trip(typename Scene::Eval& ev, bool go, int
         double v[2 * kTeam];
 #pragma unroll
         for (int k = 0; k < 2 * kTeam; ++k) v[k] = (k == 2 * P) ? o0 : (k == 2 * P + 1) ? o1 : buf[k][lane];
-        done = Scene::trip_join(ev, v[0], v[1], v[2], v[3], v[4], v[5], SPARSE);
+        if constexpr (ScenePartJoin<Scene>::value) done = Scene::template trip_join_part<P>(ev, v[0], v[1], v[2], v[3], v[4], v[5], SPARSE, s2);
+        else done = Scene::trip_join(ev, v[0], v[1], v[2], v[3], v[4], v[5], SPARSE);
     }
     return done;
 }
@@ -1004,12 +1014,18 @@ struct SceneShortLastTrip<Scene, decltype((void)Scene::kLastTrip)> : std::true_t
 // constant within an evaluation, the same in the three waves, which is what lets each arm hold its barriers -- picks
 // between them outside the trip loop: each loop holds the layout of the libm forms that suits its waves and no branch on
 // the flag per trip.  THE SHORT LAST TRIP and the one-barrier argument are those of team_trips below.
+// With Scene::kPartJoin the part-1 wave leaves the loops with e.r stale and takes the root once here, for every lane that
+// began the evaluation -- ready at begin, bailed out in a trip, or on its way into the short last trip, each from the
+// squared length it formed last -- before trip_last and the caller's value() read it.  No exchange follows, so the
+// root delays nothing but this wave's arrival at the next evaluation's first barrier.  Its begin and its root stand behind
+// tests of the wave-uniform `part` around the one dispatch of the loops (two scalar branches per evaluation): with begin
+// and the root inside a function per part the team kernel spilled four more scalar registers (49 against 45).
 template <class Scene, int P, bool SPARSE>
-__device__ __forceinline__ void team_flag_trips(bool& ready, typename Scene::Eval& ev, int lane, TeamXch& x, int& turn)
+__device__ __forceinline__ void team_flag_trips(bool& ready, typename Scene::Eval& ev, int lane, TeamXch& x, int& turn, double& s2)
 {
 #pragma unroll 1      // the count is bounded: keep the loop a loop
     for (int n = 0; n < Scene::kLastTrip && __any(!ready); ++n) {
-        const bool fin = team_trip<Scene, P, SPARSE>(ev, !ready, lane, x, turn);
+        const bool fin = team_trip<Scene, P, SPARSE>(ev, !ready, lane, x, turn, s2);
         if (!ready) ready = fin;
     }
 }
@@ -1018,10 +1034,23 @@ __device__ __forceinline__ void team_flag_evaluation(int part, bool live, vec3 o
                                                      TeamXch& x, int& turn)
 {
     bool ready = true;
-    if (live) ready = Scene::begin(ev, o + d * t, SPARSE);
-    if (part == 0) team_flag_trips<Scene, 0, SPARSE>(ready, ev, lane, x, turn);
-    else if (part == 1) team_flag_trips<Scene, 1, SPARSE>(ready, ev, lane, x, turn);
-    else team_flag_trips<Scene, 2, SPARSE>(ready, ev, lane, x, turn);
+    double s2 = 0.0;
+    if constexpr (ScenePartJoin<Scene>::value) {
+        if (part == 1) {
+            if (live) ready = Scene::template begin_part<1>(ev, o + d * t, SPARSE, s2);
+        } else {
+            if (live) ready = Scene::begin(ev, o + d * t, SPARSE);
+        }
+    } else {
+        if (live) ready = Scene::begin(ev, o + d * t, SPARSE);
+    }
+    if (part == 0) team_flag_trips<Scene, 0, SPARSE>(ready, ev, lane, x, turn, s2);
+    else if (part == 1) {
+        team_flag_trips<Scene, 1, SPARSE>(ready, ev, lane, x, turn, s2);
+        if constexpr (ScenePartJoin<Scene>::value) {
+            if (live) Scene::part1_root(ev, SPARSE, s2);
+        }
+    } else team_flag_trips<Scene, 2, SPARSE>(ready, ev, lane, x, turn, s2);
     if (__any(!ready)) {                  // only lanes entering trip Scene::kLastTrip are left
         if (!ready) Scene::trip_last(ev);
     }

@@ -105,4 +105,34 @@ hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n,
     return hipErrorInvalidValue;
 }
 
+// rm_bail4 (rm_math_pow.h), the Mandelbulb's bail-out decision from the squared length, behind an entry point of its own
+// (rm_debug_bail4_eval): the same launch shape and element layout as math_check_kernel, the sparse flag of the root behind
+// its band as a template argument, as the team loops hold it.  decision / band: 1.0 or 0.0.
+template <bool SPARSE>
+__global__ __launch_bounds__(64 * kWavesPerWG) void bail4_check_kernel(const double* __restrict__ s, size_t n, uint64_t lane_mask, int live,
+                                                                      double* __restrict__ decision, double* __restrict__ band)
+{
+    poison_tables();
+    rm_load_tables<MathCheckTables>();                 // all 256 threads, ends with the barrier
+    const unsigned lane = threadIdx.x & 63u;
+    if (!((lane_mask >> lane) & 1ull)) return;
+    const size_t wave = (size_t)blockIdx.x * kWavesPerWG + threadIdx.x / 64u;
+    const size_t e = wave * (size_t)live + (size_t)__popcll(lane_mask & ((1ull << lane) - 1ull));
+    if (e >= n) return;
+    const double x = s[e];
+    decision[e] = rm_bail4(x, SPARSE) ? 1.0 : 0.0;
+    band[e] = rm_bail4_band(x) ? 1.0 : 0.0;
+}
+
+// rm_capi.hip (rm_debug_bail4_eval) has checked lane_mask != 0, n > 0 and the buffers
+hipError_t launch_bail4_check(bool sparse, const double* s, size_t n, uint64_t lane_mask, double* decision, double* band, hipStream_t st)
+{
+    const int live = __builtin_popcountll(lane_mask);
+    const size_t waves = (n + live - 1) / live;
+    const dim3 grid((unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG)), block(64 * kWavesPerWG);
+    if (sparse) hipLaunchKernelGGL((bail4_check_kernel<true>), grid, block, 0, st, s, n, lane_mask, live, decision, band);
+    else hipLaunchKernelGGL((bail4_check_kernel<false>), grid, block, 0, st, s, n, lane_mask, live, decision, band);
+    return hipGetLastError();
+}
+
 }  // namespace rm

@@ -215,6 +215,51 @@ RM_MATH_HD double rm_pow_half_sparse(double x, bool sparse)
     }
     return rm_pow(x, 0.5);
 }
+// THE MANDELBULB'S BAIL-OUT FROM THE SQUARED LENGTH: whether rm_pow(s, 0.5) > 4.0, for s = x*x + y*y + z*z, without the
+// root (rm_scenes.h THE JOIN PER PART: the atan2 wave of a team needs the decision in every trip and the root once).
+//   Proof.  pow(s, 0.5) lies within 1 ulp of the true root (e_pow.c: 0.52 ulp), and so does rm_pow, which has its bits.
+//   s <= 16: the true root is at most 4.0; a result above 4.0 would be 4 + 2^-50 or more, over an ulp (2^-51 below 4.0,
+//     2^-50 above) from every value up to 4.0: the answer is false.  (-0, negative s -- which no sum of squares is --
+//     included: rm_pow returns +0 and NaN there, neither above 4.0.)
+//   s >= kBail4Hi = 16 + 4 ulp(16) = 16 + 2^-46: the true root is at least 4 sqrt(1 + 2^-50) > 4 + 2^-49 - 2^-99, nearly
+//     two ulps (2^-50) above 4.0, so a result within one ulp of it is above 4.0: the answer is true (+inf included:
+//     rm_pow(+inf, 0.5) = +inf).
+//   In between lie 16 + 1, 2, 3 ulp(16) -- true roots of 4 + 0.5, 1.0 and 1.5 ulp less a little, the first of them the
+//   near-midpoint case in which pow and the rounded root may differ -- and NaN (both compares fail): these take the root
+//   itself and compare.  rm_bail4_band is that lane-local test, shared with the host check build.
+// The band is three doubles wide and no ray is known to reach it: the root sits behind a wave-uniform test and out of
+// line, the two compares and the test are what a trip pays (rm_math_trig.h ONE RARE-PATH TEST PER CALL).  `sparse` is
+// rm_pow_half_sparse's flag; the answer does not depend on it.  Written for the one radius; not a general facility.
+// The compares are taken on u = (s / 16 - 1) * 2^50, formed by two ldexp and one subtraction, so that they read the
+// inline constants 0.0 and 1.0: 16.0 and kBail4Hi as 64-bit literals would hold four scalar registers through the
+// atan2 wave's trip loop, in a kernel that already spills scalar registers (tests/test_code_objects_pipeline_split.py).
+//   u is exact where the order matters: for 8 <= s <= 32 the quotient is exact and lies in [0.5, 2], so the difference
+//   is exact (Sterbenz) and the scaling is; s = 16 + k ulp(16) gives u = k / 4.  Below 8 the rounded difference is at
+//   most -0.5, above 32 at least 1 and u at least 2^50; +inf stays +inf, NaN stays NaN and fails both compares.
+//   So u <= 0.0 is s <= 16.0 and u >= 1.0 is s >= kBail4Hi, for every double.
+constexpr double kBail4Hi = 0x1.0000000000004p+4;
+RM_MATH_HD double rm_bail4_scaled(double s) { return __builtin_ldexp(__builtin_ldexp(s, -4) - 1.0, 50); }
+RM_MATH_HD bool rm_bail4_band(double s)
+{
+    const double u = rm_bail4_scaled(s);
+    return !((u <= 0.0) | (u >= 1.0));
+}
+RM_MATH_HD bool rm_bail4(double s, bool sparse)
+{
+    const double u = rm_bail4_scaled(s);
+    bool out = u >= 1.0;
+    const bool band = !((u <= 0.0) | out);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const bool any_band = __any(band) != 0;
+#else
+    const bool any_band = band;
+#endif
+    if (__builtin_expect(any_band, 0)) {
+        const bool exact = rm_pow_half_sparse(s, sparse) > 4.0;
+        out = band ? exact : out;
+    }
+    return out;
+}
 // pow(x, ya) and pow(x, yb) sharing the one log(x) they both start from (catalog.py:280,283:
 // r ** 7.0 and r ** 8.0 of the same r); each result is bit-identical to a separate rm_pow call.
 RM_MATH_HD void rm_pow2(double x, double ya, double yb, double* ra, double* rb)

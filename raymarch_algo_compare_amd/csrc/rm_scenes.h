@@ -273,6 +273,41 @@ struct SceneMandelbulb {                                                        
         e.r = length_a(e.z, sparse);
         return e.r > 4.0;
     }
+    // THE JOIN PER PART (kPartJoin), for the team loops picked by the sparse flag (rm_kernels.h team_flag_evaluation).  Every
+    // wave of a team repeats the join, and its `e.r = length_a(e.z)` is the longest dependent piece of it.  Part 0 reads r
+    // in its next trip (z.z / r), part 2 does (r ** 7, r ** 8); part 1 -- atan2(z.y, z.x) -- does not: inside the trip
+    // loop it needs only the bail-out decision, and r itself once, when the evaluation has ended (trip_last, value()).
+    // The decision comes from the squared length (rm_math_pow.h rm_bail4, equal to `length > 4.0` for every double), so
+    // the part-1 wave keeps s = length_sq(z) in a local of the loop (`s`), takes no root in begin or in a trip, and takes
+    // it once behind the loops (part1_root: the same rm_pow_half_sparse call and flag, hence the same e.r bits as in the
+    // other two waves; e.r is STALE in that wave until then).  Parts 0 and 2 run begin and trip_join as they are.
+    static constexpr bool kPartJoin = true;
+    template <int P>
+    static RM_HD bool begin_part(Eval& e, vec3 p, bool sparse, double& s)
+    {
+        if constexpr (P != 1) {
+            return begin(e, p, sparse);
+        } else {
+            e.p = p; e.z = p; e.dr = 1.0; e.i = 0;
+            s = length_sq(p);
+            return rm_bail4(s, sparse);
+        }
+    }
+    template <int P>
+    static RM_HD bool trip_join_part(Eval& e, double st, double ct, double sp, double cp, double r7, double zr, bool sparse, double& s)
+    {
+        if constexpr (P != 1) {
+            return trip_join(e, st, ct, sp, cp, r7, zr, sparse);
+        } else {
+            const double power = 8.0;
+            e.dr = r7 * power * e.dr + 1.0;
+            e.z = v3(zr * st * cp, zr * st * sp, zr * ct) + e.p;
+            if (++e.i >= 8) return true;                // s keeps the squared length measured before this update
+            s = length_sq(e.z);
+            return rm_bail4(s, sparse);
+        }
+    }
+    static RM_HD void part1_root(Eval& e, bool sparse, double s) { e.r = rm_pow_half_sparse(s, sparse); }
     static RM_HD double value(const Eval& e)
     {
         return 0.5 * rm_log(py_max(e.r, 1e-12)) * e.r / py_max(e.dr, 1e-12);
