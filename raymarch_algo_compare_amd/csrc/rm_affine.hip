@@ -6,6 +6,7 @@
 // branch.  The march loop is per lane; a wave runs as long as its longest ray.
 #include "rm_kernels.h"
 #include "rm_affine.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -68,28 +69,96 @@ __global__ __launch_bounds__(kAffineBlock) void affine_render_kernel(const void*
 
 static unsigned grid_of(size_t n) { return (unsigned)((n + kAffineBlock - 1) / kAffineBlock); }
 
-// rm_capi.hip has validated the arguments; `prog` is the device copy of the scene's ProgramImage, n > 0
-hipError_t launch_affine_range(const void* prog, int mode, const double* segs, size_t n, double* out_range, double* out_form,
-                               hipStream_t s)
-{
-    hipLaunchKernelGGL(affine_range_kernel, dim3(grid_of(n)), dim3(kAffineBlock), 0, s, prog, mode, segs, n, out_range, out_form);
-    return hipGetLastError();
-}
-
-hipError_t launch_affine_march(const void* prog, int mode, const IntervalParams& P, const double* origins, const double* dirs,
-                               size_t n, double* t, int32_t* steps, hipStream_t s)
-{
-    hipLaunchKernelGGL(affine_march_kernel, dim3(grid_of(n)), dim3(kAffineBlock), 0, s, prog, mode, P, origins, dirs, n, t, steps);
-    return hipGetLastError();
-}
-
-hipError_t launch_affine_render(const void* prog, int mode, const IntervalParams& P, const CameraParams& cam, int width, int height,
-                                int row0, int rows, double* depth, uint8_t* hit, int32_t* steps, hipStream_t s)
-{
-    const size_t n = (size_t)width * (size_t)rows;
-    hipLaunchKernelGGL(affine_render_kernel, dim3(grid_of(n)), dim3(kAffineBlock), 0, s, prog, mode, P, cam, width, height, row0, n,
-                       depth, hit, steps);
-    return hipGetLastError();
-}
-
 }  // namespace rm
+
+// ---- rm_affine_* of the C ABI: scenes and programs as the interval oracle -------------------------------------------------
+// (every launch below: the arguments are validated, `prog` is the device copy of the scene's ProgramImage, n > 0)
+using namespace rm::capi;
+
+namespace {
+
+int affine_mode(int mode)
+{
+    if (!rm::affine_mode_ok(mode))
+        return fail(RM_E_BAD_ARG, "mode %d is neither RM_RANGE_AFFINE (%d) nor RM_RANGE_MEET (%d)", mode, RM_RANGE_AFFINE, RM_RANGE_MEET);
+    return RM_OK;
+}
+
+// the mode, then the march's constants
+int affine_params(int id, int mode, const RmIntervalConfig* cfg, rm::IntervalParams* P)
+{
+    int rc = affine_mode(mode);
+    return rc ? rc : interval_params(id, cfg, P);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rm_affine_supported(int scene_id) { return rm_interval_supported(scene_id); }
+
+int rm_affine_range_eval(int scene_id, int mode, const double* segs, size_t n, double* out_range, double* out_form)
+{
+    SoundCall c;
+    int rc = c.open(scene_id, [&] {
+        int r = affine_mode(mode);
+        if (!r && mode == RM_RANGE_MEET && out_form) r = fail(RM_E_BAD_ARG, "out_form must be NULL in RM_RANGE_MEET: the meet is no form's range");
+        return r;
+    }, nullptr, nullptr, n, segs && out_range, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_segs = st.in(stage_in[0], segs, n * 64);
+    double* d_range = st.out(stage_out[0], out_range, n * 16);
+    double* d_form = st.out(stage_out[1], out_form, n * 24);
+    if ((rc = st.begin())) return rc;
+    hipLaunchKernelGGL(rm::affine_range_kernel, dim3(rm::grid_of(n)), dim3(rm::kAffineBlock), 0, lib_stream(), c.prog, mode, d_segs, n,
+                       d_range, d_form);
+    HIP_TRY(hipGetLastError());
+    return st.finish();
+}
+
+int rm_affine_march_rays(int scene_id, int mode, const RmIntervalConfig* cfg, const double* origins, const double* dirs, size_t n,
+                         double* t, int32_t* steps)
+{
+    rm::IntervalParams P;
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return affine_params(scene_id, mode, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_origins = st.in(stage_in[0], origins, n * 24);
+    const double* d_dirs = st.in(stage_in[1], dirs, n * 24);
+    double* d_t = st.out(stage_out[0], t, n * 8);
+    int32_t* d_steps = st.out(stage_out[1], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    hipLaunchKernelGGL(rm::affine_march_kernel, dim3(rm::grid_of(n)), dim3(rm::kAffineBlock), 0, lib_stream(), c.prog, mode, P, d_origins,
+                       d_dirs, n, d_t, d_steps);
+    HIP_TRY(hipGetLastError());
+    return st.finish();
+}
+
+int rm_affine_render(const RmFrameDesc* d, int mode, const RmIntervalConfig* cfg, double* depth, uint8_t* hit, int32_t* steps,
+                     RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    rm::IntervalParams P;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return affine_params(d->scene_id, mode, cfg, &P); }, d, timing, n, depth && hit,
+                    "depth and hit are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    double* d_depth = st.out(stage_out[0], depth, n * 8);
+    uint8_t* d_hit = st.out(stage_out[1], hit, n);
+    int32_t* d_steps = st.out(stage_out[2], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, lib_stream(), [&] {
+        hipLaunchKernelGGL(rm::affine_render_kernel, dim3(rm::grid_of(n)), dim3(rm::kAffineBlock), 0, lib_stream(), c.prog, mode, P, cam,
+                           d->width, d->height, d->row0, n, d_depth, d_hit, d_steps);
+        HIP_TRY(hipGetLastError());
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
+}
+
+}  // extern "C"

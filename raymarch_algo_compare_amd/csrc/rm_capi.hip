@@ -3,6 +3,10 @@
 // Owns the device selection, one HIP stream, a grow-only device workspace and the
 // (scene, strategy) -> kernel dispatch.  No CPU implementation of the path exists in
 // this library: without a usable gfx950 device every entry point returns an error.
+//
+// The entry points here are the frame path's: frames, batches, streams, the multi-GPU gather, capture and the debug
+// trace.  Those of the analysis subsystems sit below their kernels (rm_interval.hip ... rm_math_check.hip) and use this
+// file's lock, stream, staging and timing through rm_capi_internal.h.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <link.h>
@@ -16,7 +20,6 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <optional>
 #include <string>
 #include <vector>
 
@@ -25,15 +28,7 @@
 #include "rm_launch_plan.h"
 #include "rm_pipeline.h"
 #include "rm_scene_program.h"
-#include "rm_interval.h"
-#include "rm_interval_catalogue.h"
-#include "rm_exact.h"
-#include "rm_segment.h"
-#include "rm_certify.h"
-#include "rm_affine.h"
-#include "rm_score.h"
-#include "rm_ssim.h"
-#include "rm_features.h"
+#include "rm_capi_internal.h"
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
 static_assert(RM_NUM_SCENES == 20 && RM_NUM_STRATEGIES == 11 && RM_NUM_STRATEGY_KERNELS == 13, "registry size");
@@ -54,48 +49,6 @@ const SceneLaunchers* scene_launchers_program_ext() __attribute__((weak));
 const SceneLaunchers* scene_launchers_program();
 const SceneLaunchers* scene_launchers_program_ext();      // ... of programs with an op beyond primitives.py (SceneExtProgram)
 #endif
-// rm_math_check.hip: the device math routines one by one (rm_debug_math_eval)
-hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1,
-                             hipStream_t s);
-hipError_t launch_bail4_check(bool sparse, const double* s, size_t n, uint64_t lane_mask, double* decision, double* band, hipStream_t st);
-// rm_interval.hip: the interval first-hit oracle (rm_interval_*)
-hipError_t launch_interval_sdf(const void* prog, const double* lo, const double* hi, size_t n, double* out_lo, double* out_hi,
-                               hipStream_t s);
-hipError_t launch_interval_march(const void* prog, const IntervalParams& P, const double* origins, const double* dirs, size_t n,
-                                 double* t, int32_t* steps, double* normals, hipStream_t s);
-hipError_t launch_interval_render(const void* prog, const IntervalParams& P, const CameraParams& cam, int width, int height,
-                                  int row0, int rows, double* depth, uint8_t* hit, double* normal, int32_t* steps, hipStream_t s);
-// rm_exact.hip: the exact first hit (rm_exact_*)
-hipError_t launch_exact_march(const void* prog, const ExactParams& P, const double* origins, const double* dirs, size_t n, double* t,
-                              double* normals, int32_t* leaf, hipStream_t s);
-hipError_t launch_exact_render(const void* prog, const ExactParams& P, const CameraParams& cam, int width, int height, int row0,
-                               int rows, double* depth, uint8_t* hit, double* normal, int32_t* leaf, hipStream_t s);
-// rm_segment.hip: the sound segment tracer (rm_segment_*)
-hipError_t launch_segment_sdf(const void* prog, const double* segs, size_t n, double* out, hipStream_t s);
-hipError_t launch_segment_march(const void* prog, const SegmentParams& P, const double* origins, const double* dirs, size_t n,
-                                double* t, int32_t* iters, double* cursor, hipStream_t s);
-hipError_t launch_segment_render(const void* prog, const SegmentParams& P, const CameraParams& cam, int width, int height,
-                                 int row0, int rows, double* depth, uint8_t* hit, int32_t* iters, double* cursor, hipStream_t s);
-// rm_certify.hip: the certified first hit (rm_certify_*)
-hipError_t launch_certify_march(const void* prog, const CertifyParams& P, const double* origins, const double* dirs, size_t n,
-                                double* t_lo, double* t_hi, uint8_t* status, int32_t* steps, hipStream_t s);
-hipError_t launch_certify_render(const void* prog, const CertifyParams& P, const CameraParams& cam, int width, int height,
-                                 int row0, int rows, double* t_lo, double* t_hi, uint8_t* status, int32_t* steps, hipStream_t s);
-// rm_affine.hip: the affine range and its march (rm_affine_*)
-hipError_t launch_affine_range(const void* prog, int mode, const double* segs, size_t n, double* out_range, double* out_form,
-                               hipStream_t s);
-hipError_t launch_affine_march(const void* prog, int mode, const IntervalParams& P, const double* origins, const double* dirs,
-                               size_t n, double* t, int32_t* steps, hipStream_t s);
-hipError_t launch_affine_render(const void* prog, int mode, const IntervalParams& P, const CameraParams& cam, int width, int height,
-                                int row0, int rows, double* depth, uint8_t* hit, int32_t* steps, hipStream_t s);
-// rm_ssim.hip
-hipError_t launch_ssim(const SsimLaunch& a, hipStream_t s);
-// rm_score.hip
-hipError_t launch_score(const ScoreLaunch& a, hipStream_t s);
-// rm_features.hip: the sample points, then (after the scene's sdf_eval) gradients, runs and selections; the view features
-hipError_t launch_feature_points(const IntrinsicLaunch& a, hipStream_t s);
-hipError_t launch_feature_reduce(const IntrinsicLaunch& a, hipStream_t s);
-hipError_t launch_view_features(const ViewLaunch& a, hipStream_t s);
 
 static const SceneLaunchers* scene(int id)
 {
@@ -112,11 +65,13 @@ static const SceneLaunchers* scene(int id)
 }
 }  // namespace rm
 
-namespace {
+// What the other translation units' entry points use as well (rm_capi_internal.h) is defined in rm::capi; the rest of
+// this file's own state and helpers, and its kernels, in the unnamed namespace.
+using namespace rm::capi;
 
-thread_local char g_err[512] = "";
+static thread_local char g_err[512] = "";
 
-int fail(int code, const char* fmt, ...)
+int rm::capi::fail(int code, const char* fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -125,46 +80,15 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(RM_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+Buf* rm::capi::g_workspace_bufs = nullptr;   // freed by rm_shutdown
 
-// A grow-only device buffer.  Every Buf links itself into its owner's list when it is constructed, so "free all the
-// device memory this owner holds" is a walk of that list (release_all): a new buffer needs no second edit anywhere.
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    Buf* const next;
-    explicit Buf(Buf*& owner) : next(owner) { owner = this; }
-    Buf(const Buf&) = delete;
-    Buf& operator=(const Buf&) = delete;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return RM_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return fail(RM_E_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        cap = bytes;
-        return RM_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-    }
-};
+namespace {
 
 void release_all(Buf* owner)
 {
     for (Buf* b = owner; b; b = b->next) b->release();
 }
-Buf* g_workspace_bufs = nullptr;   // freed by rm_shutdown
 Buf* g_comm_bufs = nullptr;        // freed by rm_comm_destroy
-struct WsBuf : Buf { WsBuf() : Buf(g_workspace_bufs) {} };
 struct CommBuf : Buf { CommBuf() : Buf(g_comm_bufs) {} };
 
 // Everything one rm_init .. rm_shutdown life of the library knows, the device buffers aside: rm_shutdown destroys the
@@ -218,22 +142,22 @@ struct State : Session {
     WsBuf stats, depth, iters, hit, traw, fs, bvar, evals, tcost, torder, queue[rm::kQueues];
     WsBuf in[2], out[4];   // staging of the per-point / per-ray calls (Staged)
     WsBuf bstats;   // rm_render_batch: the device frame table
-    WsBuf ivprog;   // rm_interval_*: the device image of a catalogue scene's program
-    WsBuf ctl;      // single-launch pipeline: its hot counters, one per 128-byte line
+    WsBuf ctl;     // single-launch pipeline: its hot counters, one per 128-byte line
     WsBuf busy;     // rm_march_rays_team: the counter its filler workgroups watch (its own word: a frame in flight owns `ctl`)
     WsBuf trace, trace_start, trace_detach;   // development trace of single-launch frames (rm_debug_set_trace)
     WsBuf ccost, corder;   // single-launch pipeline: the centre-out tile order of the frame shape `corder_key`
-    WsBuf ssim_depth, ssim_normal, ssim_color, ssim_hit;   // rm_ssim_scores: the methods' maps, then the reference's
-    WsBuf ssim_ref, ssim_part, ssim_ssd, ssim_out;         // its reference images, partial sums and scores
-    WsBuf score_depth, score_normal, score_hit, score_caps;   // rm_score_captures: the methods' maps, then the reference's
-    WsBuf score_band, score_keys, score_small, score_part;    // its band, sample keys, counts / selections / results, partial sums
     WsBuf cap_out[5], cap_cams;   // rm_capture / rm_shade_frames: geom, normal, depth, color, evals maps; the frames' cameras
-    WsBuf feat_in[4], feat_xyz, feat_f, feat_keys, feat_slabs;   // rm_intrinsic_features: pts / chords / seglen / ts, points, values, keys
-    WsBuf feat_counts, feat_gmag, feat_out;                      // its run counts, optional gmag, results
-    WsBuf view_map[4], view_tab, view_cams, view_small;          // rm_view_features: depth / normal / evals / hit, the table, partials + results
 } g;
 
 std::mutex g_mu;
+
+}  // namespace
+
+hipStream_t rm::capi::lib_stream() { return g.stream; }
+WsBuf (&rm::capi::stage_in)[2] = g.in;
+WsBuf (&rm::capi::stage_out)[4] = g.out;
+
+namespace {
 
 // ---- scene programs (rm_scene_program.h) ----------------------------------------------------------------------------
 // A registered program: its validated device image on the host, and the device copy the first frame that renders it
@@ -248,8 +172,6 @@ std::mutex g_prog_mu;                          // guards g_programs and g_next_p
 std::map<int32_t, Program> g_programs;
 int32_t g_next_program = RM_SCENE_PROGRAM_BASE;   // ids are never reused: no per-scene cache can outlive its program
 
-bool is_program_id(int id) { return id >= RM_SCENE_PROGRAM_BASE; }
-
 const rm::SceneLaunchers* program_launchers(bool ext)
 {
 #if defined(RM_DEV_STRATEGIES)
@@ -260,7 +182,11 @@ const rm::SceneLaunchers* program_launchers(bool ext)
 #endif
 }
 
-bool program_exists(int id, bool* ext = nullptr)
+}  // namespace
+
+namespace rm::capi {
+
+bool program_exists(int id, bool* ext)
 {
     std::lock_guard<std::mutex> lk(g_prog_mu);
     auto it = g_programs.find(id);
@@ -269,17 +195,28 @@ bool program_exists(int id, bool* ext = nullptr)
     return true;
 }
 
+bool with_program_image(int id, const std::function<void(const ProgramImage&)>& look)
+{
+    std::lock_guard<std::mutex> lk(g_prog_mu);
+    auto it = g_programs.find(id);
+    if (it == g_programs.end()) return false;
+    look(*it->second.img);
+    return true;
+}
+
 // The kernels of scene `id` (a catalogue scene or a program; check_scene has accepted the id): a program that holds an
 // op beyond primitives.py (RM_SOP_SCALE .. RM_SOP_MIRROR) has its own instantiation of the interpreter
 // (looked up by id again rather than carried out of check_scene through plan_for / launch_frame; the program cannot
 // vanish in between: the caller holds g_mu, which rm_scene_program_destroy takes first)
-const rm::SceneLaunchers* launchers(int id)
+static const rm::SceneLaunchers* launchers(int id)
 {
     if (!is_program_id(id)) return rm::scene(id);
     bool ext = false;
     (void)program_exists(id, &ext);
     return program_launchers(ext);
 }
+
+SdfEval sdf_eval_of(int id) { return launchers(id)->sdf_eval; }
 
 int no_such_program(int id) { return fail(RM_E_BAD_SCENE, "scene program %d does not exist (never created, or destroyed)", id); }
 
@@ -319,6 +256,10 @@ int scene_data(int id, const void** data)
     *data = p.dev;
     return RM_OK;
 }
+
+}  // namespace rm::capi
+
+namespace {
 
 constexpr size_t kStatsBlockBytes = sizeof(unsigned long long) * rm::kStatsWords;   // the canonical block (what the host reads)
 constexpr size_t kStatsBytes = kStatsBlockBytes * rm::kStatsBlocks;                 // + the partial blocks (device buffer size)
@@ -387,89 +328,23 @@ int select_device()
     return RM_OK;
 }
 
-// An entry point's way to the workspace and the device.  Constructing one takes g_mu, refuses a library without a device
-// (RM_E_NO_DEVICE) and selects the device, in that order; while rc() is RM_OK the lock is held until the Entry goes out
-// of scope.  Whatever enqueues on the workspace (Staged, timed, read_stats, shard_open, interval_program) asks for an
-// Entry, so it cannot be reached without the lock held and the device selected.
-class Entry {
-public:
-    Entry() : lk_(g_mu), rc_(check_ready())
-    {
-        if (!rc_) rc_ = select_device();
-        if (rc_) lk_.unlock();
-    }
-    int rc() const { return rc_; }
-    // The stream a call enqueues on: the caller's (checked: check_stream) or, for NULL, the library's own.
-    int stream(void* users, hipStream_t* s) const
-    {
-        if (int rc = check_stream(users)) return rc;
-        *s = users ? (hipStream_t)users : g.stream;
-        return RM_OK;
-    }
+}  // namespace
 
-private:
-    std::unique_lock<std::mutex> lk_;
-    int rc_;
-};
+namespace rm::capi {
 
-// The staging of a call that takes host arrays and returns host arrays: inputs and outputs are declared with the
-// workspace buffer that carries them (every `ensure` happens here, before anything is enqueued; scratch() sizes a
-// buffer that is not copied), begin() reports an allocation failure or enqueues the uploads, download() enqueues the
-// copies back in declaration order and finish() waits for them.  A NULL host output is an optional one the caller did
-// not ask for: nothing is allocated or copied and its device pointer is NULL.  Everything runs on the library's stream.
-class Staged {
-public:
-    explicit Staged(const Entry&) {}
-    template <class T>
-    const T* in(Buf& b, const T* host, size_t bytes)
-    {
-        return (const T*)add(b, const_cast<T*>(host), bytes, 0, true);
-    }
-    template <class T>
-    T* out(Buf& b, T* host, size_t bytes, size_t slack = 0)
-    {
-        return host ? (T*)add(b, host, bytes, slack, false) : nullptr;
-    }
-    // a buffer the call's kernels hand to each other: sized here like every other one, never copied
-    template <class T>
-    T* scratch(Buf& b, size_t bytes, size_t slack = 0)
-    {
-        if (rc_ || (rc_ = b.ensure(bytes + slack))) return nullptr;
-        return (T*)b.p;
-    }
-    int begin()
-    {
-        if (rc_) return rc_;
-        for (int i = 0; i < n_; ++i)
-            if (v_[i].upload) HIP_TRY(hipMemcpyAsync(v_[i].dev, v_[i].host, v_[i].bytes, hipMemcpyHostToDevice, g.stream));
-        return RM_OK;
-    }
-    int download()
-    {
-        for (int i = 0; i < n_; ++i)
-            if (!v_[i].upload && v_[i].bytes) HIP_TRY(hipMemcpyAsync(v_[i].host, v_[i].dev, v_[i].bytes, hipMemcpyDeviceToHost, g.stream));
-        return RM_OK;
-    }
-    int finish()
-    {
-        if (int rc = download()) return rc;
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        return RM_OK;
-    }
+// (g_mu, check_ready, select_device, in that order; read_stats and shard_open ask for an Entry as well)
+Entry::Entry() : lk_(g_mu), rc_(check_ready())
+{
+    if (!rc_) rc_ = select_device();
+    if (rc_) lk_.unlock();
+}
 
-private:
-    void* add(Buf& b, void* host, size_t bytes, size_t slack, bool upload)
-    {
-        if (rc_) return nullptr;
-        if (n_ == kMax) { rc_ = fail(RM_E_BAD_ARG, "more than %d staged arrays", kMax); return nullptr; }
-        if ((rc_ = b.ensure(bytes + slack))) return nullptr;
-        v_[n_++] = { host, b.p, bytes, upload };
-        return b.p;
-    }
-    static constexpr int kMax = 8;
-    struct Array { void* host; void* dev; size_t bytes; bool upload; } v_[kMax];
-    int n_ = 0, rc_ = RM_OK;
-};
+int Entry::stream(void* users, hipStream_t* s) const
+{
+    if (int rc = check_stream(users)) return rc;
+    *s = users ? (hipStream_t)users : g.stream;
+    return RM_OK;
+}
 
 // The rows [row0, row0 + rows) of a width x height frame; a band-cyclic slice (check_desc) has its own test of the last row.
 int check_slice(const RmFrameDesc* d, bool band_cyclic)
@@ -479,6 +354,18 @@ int check_slice(const RmFrameDesc* d, bool band_cyclic)
     if ((long long)d->width * d->height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "frame too large");
     return RM_OK;
 }
+
+// The camera record of 14 doubles as the kernels take it.
+rm::CameraParams camera_of(const double* cam14)
+{
+    rm::CameraParams c;
+    for (int i = 0; i < 14; ++i) c.v[i] = cam14[i];
+    return c;
+}
+
+}  // namespace rm::capi
+
+namespace {
 
 int check_desc(const RmFrameDesc* d)
 {
@@ -548,14 +435,6 @@ rm::LaunchPlan plan_for(const RmFrameDesc* d, int batch_frames = 0, const RmMarc
         return e == hipSuccess ? n : 0;
     };
     return rm::plan_launch(*d, f, batch_frames, configs);
-}
-
-// The camera record of 14 doubles as the kernels take it.
-rm::CameraParams camera_of(const double* cam14)
-{
-    rm::CameraParams c;
-    for (int i = 0; i < 14; ++i) c.v[i] = cam14[i];
-    return c;
 }
 
 // Kernel arguments of one frame of `d` (a batch sets frames / nframes / full / evals itself): pointers and plan fields.
@@ -979,7 +858,9 @@ int ensure_events()
     return RM_OK;
 }
 
-int check_timing(const RmTiming* t)
+}  // namespace
+
+int rm::capi::check_timing(const RmTiming* t)
 {
     if (t->repeats < 1 || t->repeats > RM_MAX_TIMED || t->warmup < 0)
         return fail(RM_E_BAD_ARG, "timing: repeats must be 1..%d, warmup >= 0", RM_MAX_TIMED);
@@ -988,8 +869,7 @@ int check_timing(const RmTiming* t)
 
 // Runs `once` (one enqueue on `s`, returning an RM_ code) warmup + repeats times, each timed run bracketed by events
 // on `s`; waits for the stream and fills ms_each and the summary of `t`.
-template <class Once>
-int timed(const Entry&, RmTiming* t, hipStream_t s, Once once)
+int rm::capi::timed(const Entry&, RmTiming* t, hipStream_t s, const std::function<int()>& once)
 {
     int rc = check_timing(t);
     if (rc || (rc = ensure_events())) return rc;
@@ -1006,12 +886,7 @@ int timed(const Entry&, RmTiming* t, hipStream_t s, Once once)
     return RM_OK;
 }
 
-// `once` alone, or under timed() when the caller asked for a timing.
-template <class Once>
-int once_or_timed(const Entry& e, RmTiming* t, hipStream_t s, Once once)
-{
-    return t ? timed(e, t, s, once) : once();
-}
+namespace {
 
 // The events of timed() bracket one whole frame: stats reset, optional tile ordering, render kernel.
 int timed_launches(const Entry& e, const RmFrameDesc* d, const rm::LaunchPlan& p, const rm::KernelArgs& a, RmTiming* t)
@@ -1842,44 +1717,6 @@ int rm_debug_poison_queues(uint32_t word_offset, uint32_t* next_generation)
     return RM_OK;
 }
 
-int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1)
-{
-    Entry e;
-    int rc = e.rc();
-    if (rc) return rc;
-    if (fn < 0 || fn >= RM_MATH_COUNT) return fail(RM_E_BAD_ARG, "fn %d out of range [0, %d)", (int)fn, (int)RM_MATH_COUNT);
-    if (lane_mask == 0) return fail(RM_E_BAD_ARG, "lane_mask is 0: no live lane");
-    const bool two_in = fn == RM_MATH_POW || fn == RM_MATH_ATAN2 || fn == RM_MATH_ATAN2_U;
-    const bool two_out = fn == RM_MATH_POW2 || fn == RM_MATH_POW_HALF_GUARD || fn == RM_MATH_SINCOS || fn == RM_MATH_SINCOS_U;
-    if (n == 0) return RM_OK;
-    if (!a || !out0 || (two_in && !b) || (two_out && !out1)) return fail(RM_E_BAD_ARG, "NULL buffer");
-    Staged st(e);
-    const double* d_a = st.in(g.in[0], a, n * 8);
-    const double* d_b = two_in ? st.in(g.in[1], b, n * 8) : nullptr;
-    double* d_out0 = st.out(g.out[0], out0, n * 8);
-    double* d_out1 = st.out(g.out[1], two_out ? out1 : nullptr, n * 8);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_math_check(fn, d_a, d_b, n, lane_mask, d_out0, d_out1, g.stream));
-    return st.finish();
-}
-
-int rm_debug_bail4_eval(const double* s, size_t n, uint64_t lane_mask, int32_t sparse, double* decision, double* band)
-{
-    Entry e;
-    int rc = e.rc();
-    if (rc) return rc;
-    if (lane_mask == 0) return fail(RM_E_BAD_ARG, "lane_mask is 0: no live lane");
-    if (n == 0) return RM_OK;
-    if (!s || !decision || !band) return fail(RM_E_BAD_ARG, "NULL buffer");
-    Staged st(e);
-    const double* d_s = st.in(g.in[0], s, n * 8);
-    double* d_out0 = st.out(g.out[0], decision, n * 8);
-    double* d_out1 = st.out(g.out[1], band, n * 8);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_bail4_check(sparse != 0, d_s, n, lane_mask, d_out0, d_out1, g.stream));
-    return st.finish();
-}
-
 int rm_debug_set_trace(int enable)
 {
     Entry e;
@@ -1987,579 +1824,6 @@ int rm_bench_store_path(int32_t width, int32_t rows, void* d_depth, void* d_iter
     });
 }
 
-// ---- interval first-hit oracle (rm_interval.h, rm_interval.hip) ----------------------------------------------------
-
-namespace {
-
-// The encoded programs of the restated catalogue scenes (program_encode of rm_interval_catalogue.h, made once).
-const rm::ProgramImage* interval_catalogue_image(int id)
-{
-    static std::once_flag once;
-    static std::unique_ptr<rm::ProgramImage> imgs[RM_NUM_SCENES];
-    std::call_once(once, [] {
-        for (int i = 0; i < RM_NUM_SCENES; ++i) {
-            int32_t n = 0;
-            const RmSceneOp* ops = rm::interval_catalogue_ops(i, &n);
-            if (!ops) continue;
-            std::unique_ptr<rm::ProgramImage> img(new rm::ProgramImage);
-            char why[160];
-            if (rm::program_encode(ops, n, img.get(), why, sizeof why)) imgs[i] = std::move(img);
-        }
-    });
-    return id >= 0 && id < RM_NUM_SCENES ? imgs[id].get() : nullptr;
-}
-
-int interval_check_scene(int id)
-{
-    if (is_program_id(id)) return program_exists(id) ? RM_OK : no_such_program(id);
-    if (!interval_catalogue_image(id)) return fail(RM_E_BAD_SCENE, "scene %d has no interval extension", id);
-    return RM_OK;
-}
-
-int interval_params(int id, const RmIntervalConfig* cfg, rm::IntervalParams* P)
-{
-    char why[160];
-    if (!rm::interval_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
-        return fail(RM_E_BAD_ARG, "RmIntervalConfig: %s", why);
-    return RM_OK;
-}
-
-// the device image of scene `id` (under g_mu with the device selected): a program's own copy, or the catalogue
-// scene's image copied into the library's buffer on the stream
-int interval_program(const Entry&, int id, const void** prog)
-{
-    if (is_program_id(id)) return scene_data(id, prog);
-    const rm::ProgramImage* img = interval_catalogue_image(id);
-    int rc = g.ivprog.ensure(sizeof(rm::ProgramImage));
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(g.ivprog.p, img, sizeof(rm::ProgramImage), hipMemcpyHostToDevice, g.stream));
-    *prog = g.ivprog.p;
-    return RM_OK;
-}
-
-// The common head of the rm_interval_* / rm_segment_* calls, in the order every one of them checks: the scene, the
-// call's configuration (`resolve`, an RM_ code), for a render its slice `d` and `timing`, then the Entry, nothing to do
-// for n == 0, the required buffers (`have`, else `missing` is the error) and the device image of the program.  After
-// RM_OK `prog` is NULL exactly when n == 0.
-extern "C++" struct SoundCall {
-    std::optional<Entry> e;
-    const void* prog = nullptr;
-    template <class Resolve>
-    int open(int scene_id, Resolve resolve, const RmFrameDesc* d, const RmTiming* timing, size_t n, bool have, const char* missing)
-    {
-        int rc = interval_check_scene(scene_id);
-        if (rc || (rc = resolve())) return rc;
-        if (d && (rc = check_slice(d, false))) return rc;       // not check_desc: most of its fields mean nothing here
-        if (timing && (rc = check_timing(timing))) return rc;
-        e.emplace();
-        if ((rc = e->rc()) || n == 0) return rc;
-        if (!have) return fail(RM_E_BAD_ARG, "%s", missing);
-        return interval_program(*e, scene_id, &prog);
-    }
-};
-
-int no_config() { return RM_OK; }
-
-}  // namespace
-
-int rm_interval_supported(int scene_id)
-{
-    if (is_program_id(scene_id)) return program_exists(scene_id) ? 1 : 0;
-    return interval_catalogue_image(scene_id) ? 1 : 0;
-}
-
-int rm_interval_sdf_eval(int scene_id, const double* lo, const double* hi, size_t n, double* out_lo, double* out_hi)
-{
-    SoundCall c;
-    int rc = c.open(scene_id, no_config, nullptr, nullptr, n, lo && hi && out_lo && out_hi, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_lo = st.in(g.in[0], lo, n * 24);
-    const double* d_hi = st.in(g.in[1], hi, n * 24);
-    double* d_out_lo = st.out(g.out[0], out_lo, n * 8);
-    double* d_out_hi = st.out(g.out[1], out_hi, n * 8);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_interval_sdf(c.prog, d_lo, d_hi, n, d_out_lo, d_out_hi, g.stream));
-    return st.finish();
-}
-
-int rm_interval_march_rays(int scene_id, const RmIntervalConfig* cfg, const double* origins, const double* dirs, size_t n,
-                           double* t, int32_t* steps, double* normals)
-{
-    rm::IntervalParams P;
-    SoundCall c;
-    int rc = c.open(scene_id, [&] { return interval_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_origins = st.in(g.in[0], origins, n * 24);
-    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
-    double* d_t = st.out(g.out[0], t, n * 8);
-    int32_t* d_steps = st.out(g.out[1], steps, n * 4);
-    double* d_normals = st.out(g.out[2], normals, n * 24);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_interval_march(c.prog, P, d_origins, d_dirs, n, d_t, d_steps, d_normals, g.stream));
-    return st.finish();
-}
-
-int rm_interval_render(const RmFrameDesc* d, const RmIntervalConfig* cfg, double* depth, uint8_t* hit, double* normal,
-                       int32_t* steps, RmTiming* timing)
-{
-    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    rm::IntervalParams P;
-    const size_t n = (size_t)d->width * (size_t)d->rows;
-    SoundCall c;
-    int rc = c.open(d->scene_id, [&] { return interval_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
-                    "depth and hit are required");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    double* d_depth = st.out(g.out[0], depth, n * 8);
-    uint8_t* d_hit = st.out(g.out[1], hit, n);
-    double* d_normal = st.out(g.out[2], normal, n * 24);
-    int32_t* d_steps = st.out(g.out[3], steps, n * 4);
-    if ((rc = st.begin())) return rc;
-    const rm::CameraParams cam = camera_of(d->cam);
-    // (a timed call waits twice: timed() before it reads its events, finish() for the maps)
-    rc = once_or_timed(*c.e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_interval_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_normal, d_steps, g.stream));
-        return (int)RM_OK;
-    });
-    return rc ? rc : st.finish();
-}
-
-// ---- exact first hit (rm_exact.h, rm_exact.hip): the interval oracle's scenes that pass exact_supported ---------------
-
-namespace {
-
-// RM_OK when the scene has an exact form; RM_E_BAD_SCENE with the reason otherwise.  Host only.
-int exact_check_scene(int id)
-{
-    char why[160];
-    if (is_program_id(id)) {
-        std::lock_guard<std::mutex> lk(g_prog_mu);
-        auto it = g_programs.find(id);
-        if (it == g_programs.end()) return no_such_program(id);
-        if (!rm::exact_supported(*it->second.img, why, sizeof why)) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: %s", id, why);
-        return RM_OK;
-    }
-    const rm::ProgramImage* img = interval_catalogue_image(id);
-    if (!img) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: it is no composition of primitives", id);
-    if (!rm::exact_supported(*img, why, sizeof why)) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: %s", id, why);
-    return RM_OK;
-}
-
-int exact_params(int id, const RmExactConfig* cfg, rm::ExactParams* P)
-{
-    int rc = exact_check_scene(id);
-    if (rc) return rc;
-    char why[160];
-    if (!rm::exact_resolve(cfg, P, why, sizeof why)) return fail(RM_E_BAD_ARG, "RmExactConfig: %s", why);
-    return RM_OK;
-}
-
-}  // namespace
-
-int rm_exact_supported(int scene_id) { return exact_check_scene(scene_id) == RM_OK ? 1 : 0; }
-
-int rm_exact_march_rays(int scene_id, const RmExactConfig* cfg, const double* origins, const double* dirs, size_t n, double* t,
-                        double* normals, int32_t* leaf)
-{
-    rm::ExactParams P;
-    SoundCall c;
-    int rc = c.open(scene_id, [&] { return exact_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_origins = st.in(g.in[0], origins, n * 24);
-    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
-    double* d_t = st.out(g.out[0], t, n * 8);
-    double* d_normals = st.out(g.out[1], normals, n * 24);
-    int32_t* d_leaf = st.out(g.out[2], leaf, n * 4);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_exact_march(c.prog, P, d_origins, d_dirs, n, d_t, d_normals, d_leaf, g.stream));
-    return st.finish();
-}
-
-int rm_exact_render(const RmFrameDesc* d, const RmExactConfig* cfg, double* depth, uint8_t* hit, double* normal, int32_t* leaf,
-                    RmTiming* timing)
-{
-    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    rm::ExactParams P;
-    const size_t n = (size_t)d->width * (size_t)d->rows;
-    SoundCall c;
-    int rc = c.open(d->scene_id, [&] { return exact_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
-                    "depth and hit are required");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    double* d_depth = st.out(g.out[0], depth, n * 8);
-    uint8_t* d_hit = st.out(g.out[1], hit, n);
-    double* d_normal = st.out(g.out[2], normal, n * 24);
-    int32_t* d_leaf = st.out(g.out[3], leaf, n * 4);
-    if ((rc = st.begin())) return rc;
-    const rm::CameraParams cam = camera_of(d->cam);
-    rc = once_or_timed(*c.e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_exact_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_normal, d_leaf, g.stream));
-        return (int)RM_OK;
-    });
-    return rc ? rc : st.finish();
-}
-
-// ---- sound segment tracer (rm_segment.h, rm_segment.hip): scenes and programs as the interval oracle ------------------
-
-namespace {
-
-int segment_params(int id, const RmSegmentConfig* cfg, rm::SegmentParams* P)
-{
-    char why[160];
-    if (!rm::segment_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
-        return fail(RM_E_BAD_ARG, "RmSegmentConfig: %s", why);
-    return RM_OK;
-}
-
-}  // namespace
-
-int rm_segment_supported(int scene_id) { return rm_interval_supported(scene_id); }
-
-int rm_segment_sdf_eval(int scene_id, const double* segs, size_t n, double* out)
-{
-    SoundCall c;
-    int rc = c.open(scene_id, no_config, nullptr, nullptr, n, segs && out, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_segs = st.in(g.in[0], segs, n * 64);
-    double* d_out = st.out(g.out[0], out, n * 32);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_segment_sdf(c.prog, d_segs, n, d_out, g.stream));
-    return st.finish();
-}
-
-int rm_segment_march_rays(int scene_id, const RmSegmentConfig* cfg, const double* origins, const double* dirs, size_t n,
-                          double* t, int32_t* iters, double* cursor)
-{
-    rm::SegmentParams P;
-    SoundCall c;
-    int rc = c.open(scene_id, [&] { return segment_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_origins = st.in(g.in[0], origins, n * 24);
-    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
-    double* d_t = st.out(g.out[0], t, n * 8);
-    int32_t* d_iters = st.out(g.out[1], iters, n * 4);
-    double* d_cursor = st.out(g.out[2], cursor, n * 8);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_segment_march(c.prog, P, d_origins, d_dirs, n, d_t, d_iters, d_cursor, g.stream));
-    return st.finish();
-}
-
-int rm_segment_render(const RmFrameDesc* d, const RmSegmentConfig* cfg, double* depth, uint8_t* hit, int32_t* iters,
-                      double* cursor, RmTiming* timing)
-{
-    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    rm::SegmentParams P;
-    const size_t n = (size_t)d->width * (size_t)d->rows;
-    SoundCall c;
-    int rc = c.open(d->scene_id, [&] { return segment_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
-                    "depth and hit are required");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    double* d_depth = st.out(g.out[0], depth, n * 8);
-    uint8_t* d_hit = st.out(g.out[1], hit, n);
-    int32_t* d_iters = st.out(g.out[2], iters, n * 4);
-    double* d_cursor = st.out(g.out[3], cursor, n * 8);
-    if ((rc = st.begin())) return rc;
-    const rm::CameraParams cam = camera_of(d->cam);
-    rc = once_or_timed(*c.e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_segment_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_iters, d_cursor, g.stream));
-        return (int)RM_OK;
-    });
-    return rc ? rc : st.finish();
-}
-
-// ---- certified first hit (rm_certify.h, rm_certify.hip): scenes and programs as the interval oracle --------------------
-
-namespace {
-
-int certify_params(int id, const RmCertifyConfig* cfg, rm::CertifyParams* P)
-{
-    char why[160];
-    if (!rm::certify_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
-        return fail(RM_E_BAD_ARG, "RmCertifyConfig: %s", why);
-    return RM_OK;
-}
-
-}  // namespace
-
-int rm_certify_supported(int scene_id) { return rm_segment_supported(scene_id); }
-
-int rm_certify_march_rays(int scene_id, const RmCertifyConfig* cfg, const double* origins, const double* dirs, size_t n,
-                          double* t_lo, double* t_hi, uint8_t* status, int32_t* steps)
-{
-    rm::CertifyParams P;
-    SoundCall c;
-    int rc = c.open(scene_id, [&] { return certify_params(scene_id, cfg, &P); }, nullptr, nullptr, n,
-                    origins && dirs && t_lo && t_hi && status, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_origins = st.in(g.in[0], origins, n * 24);
-    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
-    double* d_lo = st.out(g.out[0], t_lo, n * 8);
-    double* d_hi = st.out(g.out[1], t_hi, n * 8);
-    uint8_t* d_status = st.out(g.out[2], status, n);
-    int32_t* d_steps = st.out(g.out[3], steps, n * 4);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_certify_march(c.prog, P, d_origins, d_dirs, n, d_lo, d_hi, d_status, d_steps, g.stream));
-    return st.finish();
-}
-
-int rm_certify_render(const RmFrameDesc* d, const RmCertifyConfig* cfg, double* t_lo, double* t_hi, uint8_t* status, int32_t* steps,
-                      RmTiming* timing)
-{
-    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    rm::CertifyParams P;
-    const size_t n = (size_t)d->width * (size_t)d->rows;
-    SoundCall c;
-    int rc = c.open(d->scene_id, [&] { return certify_params(d->scene_id, cfg, &P); }, d, timing, n, t_lo && t_hi && status,
-                    "t_lo, t_hi and status are required");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    double* d_lo = st.out(g.out[0], t_lo, n * 8);
-    double* d_hi = st.out(g.out[1], t_hi, n * 8);
-    uint8_t* d_status = st.out(g.out[2], status, n);
-    int32_t* d_steps = st.out(g.out[3], steps, n * 4);
-    if ((rc = st.begin())) return rc;
-    const rm::CameraParams cam = camera_of(d->cam);
-    rc = once_or_timed(*c.e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_certify_render(c.prog, P, cam, d->width, d->height, d->row0, d->rows, d_lo, d_hi, d_status, d_steps, g.stream));
-        return (int)RM_OK;
-    });
-    return rc ? rc : st.finish();
-}
-
-// ---- affine range (rm_affine.h, rm_affine.hip): scenes and programs as the interval oracle -----------------------------
-
-namespace {
-
-int affine_mode(int mode)
-{
-    if (!rm::affine_mode_ok(mode))
-        return fail(RM_E_BAD_ARG, "mode %d is neither RM_RANGE_AFFINE (%d) nor RM_RANGE_MEET (%d)", mode, RM_RANGE_AFFINE, RM_RANGE_MEET);
-    return RM_OK;
-}
-
-// the mode, then the march's constants
-int affine_params(int id, int mode, const RmIntervalConfig* cfg, rm::IntervalParams* P)
-{
-    int rc = affine_mode(mode);
-    return rc ? rc : interval_params(id, cfg, P);
-}
-
-}  // namespace
-
-int rm_affine_supported(int scene_id) { return rm_interval_supported(scene_id); }
-
-int rm_affine_range_eval(int scene_id, int mode, const double* segs, size_t n, double* out_range, double* out_form)
-{
-    SoundCall c;
-    int rc = c.open(scene_id, [&] {
-        int r = affine_mode(mode);
-        if (!r && mode == RM_RANGE_MEET && out_form) r = fail(RM_E_BAD_ARG, "out_form must be NULL in RM_RANGE_MEET: the meet is no form's range");
-        return r;
-    }, nullptr, nullptr, n, segs && out_range, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_segs = st.in(g.in[0], segs, n * 64);
-    double* d_range = st.out(g.out[0], out_range, n * 16);
-    double* d_form = st.out(g.out[1], out_form, n * 24);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_affine_range(c.prog, mode, d_segs, n, d_range, d_form, g.stream));
-    return st.finish();
-}
-
-int rm_affine_march_rays(int scene_id, int mode, const RmIntervalConfig* cfg, const double* origins, const double* dirs, size_t n,
-                         double* t, int32_t* steps)
-{
-    rm::IntervalParams P;
-    SoundCall c;
-    int rc = c.open(scene_id, [&] { return affine_params(scene_id, mode, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    const double* d_origins = st.in(g.in[0], origins, n * 24);
-    const double* d_dirs = st.in(g.in[1], dirs, n * 24);
-    double* d_t = st.out(g.out[0], t, n * 8);
-    int32_t* d_steps = st.out(g.out[1], steps, n * 4);
-    if ((rc = st.begin())) return rc;
-    HIP_TRY(rm::launch_affine_march(c.prog, mode, P, d_origins, d_dirs, n, d_t, d_steps, g.stream));
-    return st.finish();
-}
-
-int rm_affine_render(const RmFrameDesc* d, int mode, const RmIntervalConfig* cfg, double* depth, uint8_t* hit, int32_t* steps,
-                     RmTiming* timing)
-{
-    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
-    rm::IntervalParams P;
-    const size_t n = (size_t)d->width * (size_t)d->rows;
-    SoundCall c;
-    int rc = c.open(d->scene_id, [&] { return affine_params(d->scene_id, mode, cfg, &P); }, d, timing, n, depth && hit,
-                    "depth and hit are required");
-    if (rc || !c.prog) return rc;
-    Staged st(*c.e);
-    double* d_depth = st.out(g.out[0], depth, n * 8);
-    uint8_t* d_hit = st.out(g.out[1], hit, n);
-    int32_t* d_steps = st.out(g.out[2], steps, n * 4);
-    if ((rc = st.begin())) return rc;
-    const rm::CameraParams cam = camera_of(d->cam);
-    rc = once_or_timed(*c.e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_affine_render(c.prog, mode, P, cam, d->width, d->height, d->row0, d->rows, d_depth, d_hit, d_steps, g.stream));
-        return (int)RM_OK;
-    });
-    return rc ? rc : st.finish();
-}
-
-// ---- SSIM and colour-RMSE scoring of captures (rm_ssim.h, rm_ssim.hip) ------------------------------------------------
-
-namespace {
-
-int ssim_check_maps(const RmCaptureMaps& c, const RmCaptureMaps& ref, const char* who, int index)
-{
-    if (!c.depth || !c.hit) return fail(RM_E_BAD_ARG, "%s %d: depth and hit are required", who, index);
-    if (!c.normal != !ref.normal) return fail(RM_E_BAD_ARG, "%s %d: normal is NULL on one side only", who, index);
-    if (!c.color != !ref.color) return fail(RM_E_BAD_ARG, "%s %d: color is NULL on one side only", who, index);
-    return RM_OK;
-}
-
-}  // namespace
-
-int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference, const RmCaptureMaps* methods, int32_t nmethods,
-                   double* out, RmTiming* timing)
-{
-    if (!reference || !methods || !out) return fail(RM_E_BAD_ARG, "reference, methods or out is NULL");
-    if (nmethods <= 0 || nmethods > rm::kSsimMaxMethods)
-        return fail(RM_E_BAD_ARG, "nmethods %d outside [1, %d]", nmethods, rm::kSsimMaxMethods);
-    if (width < rm::kSsimWin || height < rm::kSsimWin)
-        return fail(RM_E_BAD_DIMS, "a %dx%d image holds no %dx%d window", width, height, rm::kSsimWin, rm::kSsimWin);
-    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
-    int rc = ssim_check_maps(*reference, *reference, "reference", 0);
-    for (int m = 0; !rc && m < nmethods; ++m) rc = ssim_check_maps(methods[m], *reference, "method", m);
-    if (rc || (timing && (rc = check_timing(timing)))) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-
-    const size_t npix = (size_t)width * (size_t)height, caps = (size_t)nmethods + 1;      // the reference is capture `nmethods`
-    const size_t ntiles = (size_t)rm::ssim_tiles_x(width) * (size_t)rm::ssim_tiles_y(height);
-    const bool has_normal = reference->normal != nullptr, has_color = reference->color != nullptr;
-    if ((rc = g.ssim_depth.ensure(caps * npix * 4)) || (rc = g.ssim_hit.ensure(caps * npix)) ||
-        (has_normal && (rc = g.ssim_normal.ensure(caps * npix * 12))) || (has_color && (rc = g.ssim_color.ensure(caps * npix * 12))) ||
-        (rc = g.ssim_ref.ensure(rm::kSsimChannels * npix)) || (rc = g.ssim_part.ensure((size_t)nmethods * rm::kSsimChannels * ntiles * 8)) ||
-        (rc = g.ssim_ssd.ensure((size_t)nmethods * 3 * ntiles * 8)) || (rc = g.ssim_out.ensure((size_t)nmethods * 32)))
-        return rc;
-    for (size_t m = 0; m < caps; ++m) {
-        const RmCaptureMaps& c = m < (size_t)nmethods ? methods[m] : *reference;
-        HIP_TRY(hipMemcpyAsync((float*)g.ssim_depth.p + m * npix, c.depth, npix * 4, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync((uint8_t*)g.ssim_hit.p + m * npix, c.hit, npix, hipMemcpyHostToDevice, g.stream));
-        if (has_normal) HIP_TRY(hipMemcpyAsync((float*)g.ssim_normal.p + m * npix * 3, c.normal, npix * 12, hipMemcpyHostToDevice, g.stream));
-        if (has_color) HIP_TRY(hipMemcpyAsync((float*)g.ssim_color.p + m * npix * 3, c.color, npix * 12, hipMemcpyHostToDevice, g.stream));
-    }
-    double lo, hi;
-    rm::ssim_depth_minmax(reference->depth, reference->hit, npix, &lo, &hi);
-    rm::SsimLaunch a;
-    a.width = width; a.height = height; a.nmethods = nmethods; a.has_normal = has_normal; a.has_color = has_color;
-    a.range = rm::ssim_depth_range(lo, hi);
-    a.depth = (const float*)g.ssim_depth.p; a.hit = (const uint8_t*)g.ssim_hit.p;
-    a.normal = has_normal ? (const float*)g.ssim_normal.p : nullptr;
-    a.color = has_color ? (const float*)g.ssim_color.p : nullptr;
-    a.ref_depth = a.depth + (size_t)nmethods * npix; a.ref_hit = a.hit + (size_t)nmethods * npix;
-    a.ref_normal = has_normal ? a.normal + (size_t)nmethods * npix * 3 : nullptr;
-    a.ref_color = has_color ? a.color + (size_t)nmethods * npix * 3 : nullptr;
-    a.ref_img = (uint8_t*)g.ssim_ref.p;
-    a.part = (double*)g.ssim_part.p; a.ssd = (long long*)g.ssim_ssd.p; a.out = (double*)g.ssim_out.p;
-    rc = once_or_timed(e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_ssim(a, g.stream));
-        return (int)RM_OK;
-    });
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)nmethods * 32, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
-}
-
-// ---- hit-mask, depth and normal scoring of captures (rm_score.h, rm_score.hip) --------------------------------------
-
-static_assert(sizeof(RmScoreResult) == sizeof(rm::ScoreResult) && offsetof(RmScoreResult, depth_mae) == offsetof(rm::ScoreResult, depth_mae) &&
-              offsetof(RmScoreResult, normal_p95_deg) == offsetof(rm::ScoreResult, normal_p95_deg), "rm::ScoreResult is RmScoreResult");
-
-namespace {
-
-int score_check_maps(const RmScoreMaps& c, const RmScoreMaps& ref, const char* who, int index)
-{
-    if (!c.depth || !c.hit) return fail(RM_E_BAD_ARG, "%s %d: depth and hit are required", who, index);
-    if (!c.normal != !ref.normal) return fail(RM_E_BAD_ARG, "%s %d: normal is NULL on one side only", who, index);
-    return RM_OK;
-}
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-}  // namespace
-
-int rm_score_captures(int32_t width, int32_t height, int32_t band_k, const RmScoreMaps* reference, const RmScoreMaps* methods,
-                      int32_t nmethods, RmScoreResult* out, RmTiming* timing)
-{
-    if (!reference || !methods || !out) return fail(RM_E_BAD_ARG, "reference, methods or out is NULL");
-    if (nmethods <= 0 || nmethods > rm::kScoreMaxMethods)
-        return fail(RM_E_BAD_ARG, "nmethods %d outside [1, %d]", nmethods, rm::kScoreMaxMethods);
-    if (band_k > rm::kScoreMaxBand) return fail(RM_E_BAD_ARG, "band_k %d above %d", band_k, rm::kScoreMaxBand);
-    if (width <= 0 || height <= 0) return fail(RM_E_BAD_DIMS, "a %dx%d image has no pixel", width, height);
-    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
-    int rc = score_check_maps(*reference, *reference, "reference", 0);
-    for (int m = 0; !rc && m < nmethods; ++m) rc = score_check_maps(methods[m], *reference, "method", m);
-    if (rc || (timing && (rc = check_timing(timing)))) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-
-    const size_t npix = (size_t)width * (size_t)height, nm = (size_t)nmethods, caps = nm + 1;   // the reference is capture `nmethods`
-    const size_t ntiles = (size_t)rm::score_tiles_x(width) * (size_t)rm::score_tiles_y(height);
-    const bool has_normal = reference->normal != nullptr;
-    // one small buffer: counts, selections, histograms, least keys above, results
-    const size_t o_counts = 0, o_sel = align256(o_counts + nm * rm::kScoreCounts * 8);
-    const size_t o_hist = align256(o_sel + nm * rm::kScoreSelects * sizeof(rm::ScoreSelect));
-    const size_t o_above = align256(o_hist + nm * rm::kScoreSelects * 256 * 4);
-    const size_t o_out = align256(o_above + nm * rm::kScoreSelects * 8), small = o_out + nm * sizeof(rm::ScoreResult);
-    // every capture has a slot of W*H doubles (and 3 W*H for the normals), whichever type it holds
-    if ((rc = g.score_depth.ensure(caps * npix * 8)) || (rc = g.score_hit.ensure(caps * npix)) ||
-        (has_normal && (rc = g.score_normal.ensure(caps * npix * 24))) || (rc = g.score_caps.ensure(caps * sizeof(rm::ScoreMaps))) ||
-        (band_k >= 0 && (rc = g.score_band.ensure(npix))) || (rc = g.score_keys.ensure(nm * (has_normal ? 2 : 1) * npix * 8)) ||
-        (rc = g.score_small.ensure(small)) || (rc = g.score_part.ensure(nm * rm::kScoreSums * ntiles * 8)))
-        return rc;
-    std::vector<rm::ScoreMaps> table(caps);
-    for (size_t m = 0; m < caps; ++m) {
-        const RmScoreMaps& c = m < nm ? methods[m] : *reference;
-        const size_t elem = c.fp64 ? 8 : 4;
-        rm::ScoreMaps& d = table[m];
-        d.depth = (char*)g.score_depth.p + m * npix * 8;
-        d.normal = has_normal ? (char*)g.score_normal.p + m * npix * 24 : nullptr;
-        d.hit = (uint8_t*)g.score_hit.p + m * npix;
-        d.fp64 = c.fp64 != 0;
-        HIP_TRY(hipMemcpyAsync((void*)d.depth, c.depth, npix * elem, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync((void*)d.hit, c.hit, npix, hipMemcpyHostToDevice, g.stream));
-        if (has_normal) HIP_TRY(hipMemcpyAsync((void*)d.normal, c.normal, npix * 3 * elem, hipMemcpyHostToDevice, g.stream));
-    }
-    HIP_TRY(hipMemcpyAsync(g.score_caps.p, table.data(), caps * sizeof(rm::ScoreMaps), hipMemcpyHostToDevice, g.stream));
-    rm::ScoreLaunch a;
-    a.width = width; a.height = height; a.nmethods = nmethods; a.has_normal = has_normal; a.band_k = band_k < 0 ? -1 : band_k;
-    a.caps = (const rm::ScoreMaps*)g.score_caps.p;
-    a.band = (uint8_t*)g.score_band.p;
-    a.keys = (uint64_t*)g.score_keys.p;
-    char* sm = (char*)g.score_small.p;
-    a.counts = (unsigned long long*)(sm + o_counts); a.sel = (rm::ScoreSelect*)(sm + o_sel); a.hist = (uint32_t*)(sm + o_hist);
-    a.above = (unsigned long long*)(sm + o_above); a.out = (rm::ScoreResult*)(sm + o_out);
-    a.part = (double*)g.score_part.p;
-    rc = once_or_timed(e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_score(a, g.stream));
-        return (int)RM_OK;
-    });
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, a.out, nm * sizeof(rm::ScoreResult), hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
-}
-
 // ---- capture on the device: hit normals and shading (rm_capture.h, capture_kernel) ------------------------------------
 
 int rm_capture(const RmFrameDesc* d, const RmCaptureOutputs* o, RmStats* stats, RmTiming* timing)
@@ -2654,113 +1918,6 @@ int rm_shade_frames(int scene_id, int32_t width, int32_t height, int32_t nframes
     });
     if (rc) return rc;
     return st.finish();
-}
-
-// ---- discovery features (rm_features.h, rm_features.hip) -----------------------------------------------------------------
-
-static_assert(sizeof(RmIntrinsicFeatures) == sizeof(rm::IntrinsicFeatures) && offsetof(RmIntrinsicFeatures, n_slabs) == offsetof(rm::IntrinsicFeatures, n_slabs),
-              "rm::IntrinsicFeatures is RmIntrinsicFeatures");
-static_assert(sizeof(RmViewFeatures) == sizeof(rm::ViewFeatures) && offsetof(RmViewFeatures, hit_rate) == offsetof(rm::ViewFeatures, hit_rate) &&
-              offsetof(RmViewFeatures, box_hi) == offsetof(rm::ViewFeatures, box_hi), "rm::ViewFeatures is RmViewFeatures");
-static_assert(sizeof(RmViewMaps) == sizeof(rm::ViewMaps), "rm::ViewMaps is RmViewMaps");
-
-int rm_intrinsic_features(int scene_id, int32_t nsets, int32_t n_lip, const double* pts, double lip_eps, int32_t n_chords,
-                          const double* chords, const double* seglen, int32_t chord_steps, const double* ts, RmIntrinsicFeatures* out,
-                          double* gmag_out, int32_t* slab_counts_out, RmTiming* timing)
-{
-    if (const char* why = rm::feat_check_intrinsic(nsets, n_lip, pts, lip_eps, n_chords, chords, seglen, chord_steps, ts, out))
-        return fail(RM_E_BAD_ARG, "rm_intrinsic_features: %s", why);
-    if (const char* why = rm::feat_check_seglen(nsets, n_chords, seglen)) return fail(RM_E_BAD_ARG, "rm_intrinsic_features: %s", why);
-    int rc = check_scene(scene_id);
-    if (rc || (timing && (rc = check_timing(timing)))) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-
-    const void* data = nullptr;
-    if ((rc = scene_data(scene_id, &data))) return rc;
-    const size_t ns = (size_t)nsets, nl = ns * (size_t)n_lip, nc = ns * (size_t)n_chords;
-    const size_t npts = rm::feat_lip_points(nsets, n_lip) + rm::feat_chord_points(nsets, n_chords, chord_steps);
-    Staged st(e);
-    rm::IntrinsicLaunch a;
-    memset(&a, 0, sizeof a);
-    a.nsets = nsets; a.n_lip = n_lip; a.n_chords = n_chords; a.chord_steps = chord_steps; a.eps = lip_eps;
-    if (nl) a.pts = st.in(g.feat_in[0], pts, nl * 24);
-    if (nc) a.chords = st.in(g.feat_in[1], chords, nc * 48);
-    if (nc) a.seglen = st.in(g.feat_in[2], seglen, nc * 8);
-    a.ts = st.in(g.feat_in[3], ts, (size_t)chord_steps * 8);
-    a.xyz = st.scratch<double>(g.feat_xyz, npts * 24, 16);
-    a.f = st.scratch<double>(g.feat_f, npts * 8, 16);
-    a.gkeys = st.scratch<uint64_t>(g.feat_keys, nl * 8, 16);
-    a.slabs = st.scratch<uint64_t>(g.feat_slabs, nc * (size_t)rm::feat_max_runs(chord_steps) * 8, 16);
-    a.counts = nc && slab_counts_out ? st.out(g.feat_counts, slab_counts_out, nc * 4) : st.scratch<int32_t>(g.feat_counts, nc * 4, 16);
-    a.gmag_out = nl ? st.out(g.feat_gmag, gmag_out, nl * 8) : nullptr;
-    a.out = (rm::IntrinsicFeatures*)st.out(g.feat_out, out, ns * sizeof(RmIntrinsicFeatures));
-    if ((rc = st.begin())) return rc;
-    const rm::SceneLaunchers* const sc = launchers(scene_id);
-    rc = once_or_timed(e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_feature_points(a, g.stream));
-        HIP_TRY(sc->sdf_eval(a.xyz, npts, a.f, data, g.stream));
-        HIP_TRY(rm::launch_feature_reduce(a, g.stream));
-        return (int)RM_OK;
-    });
-    if (rc) return rc;
-    return st.finish();
-}
-
-int rm_view_features(int32_t width, int32_t height, int32_t nviews, const double* cams, const RmViewMaps* maps, RmViewFeatures* out,
-                     RmTiming* timing)
-{
-    if (const char* why = rm::feat_check_view(nviews, cams, maps, out)) return fail(RM_E_BAD_ARG, "rm_view_features: %s", why);
-    if (width <= 0 || height <= 0) return fail(RM_E_BAD_DIMS, "a %dx%d image has no pixel", width, height);
-    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
-    for (int v = 0; v < nviews; ++v)
-        if (!maps[v].depth || !maps[v].normal || !maps[v].evals || !maps[v].hit)
-            return fail(RM_E_BAD_ARG, "rm_view_features: view %d: depth, normal, evals and hit are required", v);
-    for (size_t i = 0; i < (size_t)nviews * 14; ++i)
-        if (!rm::feat_is_finite(cams[i])) return fail(RM_E_BAD_ARG, "rm_view_features: camera %zu: field %zu is not finite", i / 14, i % 14);
-    int rc = timing ? check_timing(timing) : RM_OK;
-    if (rc) return rc;
-    Entry e;
-    if ((rc = e.rc())) return rc;
-
-    const size_t npix = (size_t)width * (size_t)height, nv = (size_t)nviews;
-    const size_t ntiles = (size_t)rm::score_tiles_x(width) * (size_t)rm::score_tiles_y(height);
-    const size_t o_counts = 0, o_box = align256(o_counts + nv * rm::kViewCounts * ntiles * 8), o_mean = align256(o_box + nv * 6 * ntiles * 8);
-    const size_t o_part = align256(o_mean + nv * 8), o_out = align256(o_part + nv * ntiles * 8), small = o_out + nv * sizeof(rm::ViewFeatures);
-    static_assert(sizeof(rm::CameraParams) == 14 * sizeof(double), "cams is an array of CameraParams");
-    if ((rc = g.view_map[0].ensure(nv * npix * 4)) || (rc = g.view_map[1].ensure(nv * npix * 12)) || (rc = g.view_map[2].ensure(nv * npix * 4)) ||
-        (rc = g.view_map[3].ensure(nv * npix)) || (rc = g.view_tab.ensure(nv * sizeof(rm::ViewMaps))) ||
-        (rc = g.view_cams.ensure(nv * sizeof(rm::CameraParams))) || (rc = g.view_small.ensure(small)))
-        return rc;
-    std::vector<rm::ViewMaps> table(nv);
-    for (size_t v = 0; v < nv; ++v) {
-        rm::ViewMaps& d = table[v];
-        d.depth = (const float*)g.view_map[0].p + v * npix;
-        d.normal = (const float*)g.view_map[1].p + v * npix * 3;
-        d.evals = (const float*)g.view_map[2].p + v * npix;
-        d.hit = (const uint8_t*)g.view_map[3].p + v * npix;
-        HIP_TRY(hipMemcpyAsync((void*)d.depth, maps[v].depth, npix * 4, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync((void*)d.normal, maps[v].normal, npix * 12, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync((void*)d.evals, maps[v].evals, npix * 4, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync((void*)d.hit, maps[v].hit, npix, hipMemcpyHostToDevice, g.stream));
-    }
-    HIP_TRY(hipMemcpyAsync(g.view_tab.p, table.data(), nv * sizeof(rm::ViewMaps), hipMemcpyHostToDevice, g.stream));
-    HIP_TRY(hipMemcpyAsync(g.view_cams.p, cams, nv * sizeof(rm::CameraParams), hipMemcpyHostToDevice, g.stream));
-    rm::ViewLaunch a;
-    a.width = width; a.height = height; a.nviews = nviews;
-    a.maps = (const rm::ViewMaps*)g.view_tab.p;
-    a.cams = (const rm::CameraParams*)g.view_cams.p;
-    char* sm = (char*)g.view_small.p;
-    a.icounts = (long long*)(sm + o_counts); a.box = (double*)(sm + o_box); a.mean = (double*)(sm + o_mean);
-    a.part = (double*)(sm + o_part); a.out = (rm::ViewFeatures*)(sm + o_out);
-    rc = once_or_timed(e, timing, g.stream, [&] {
-        HIP_TRY(rm::launch_view_features(a, g.stream));
-        return (int)RM_OK;
-    });
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, a.out, nv * sizeof(rm::ViewFeatures), hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return RM_OK;
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 // (RM_INTERVAL_MAX_STEPS).
 #include "rm_kernels.h"
 #include "rm_certify.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -56,22 +57,74 @@ __global__ __launch_bounds__(kCertifyBlock) void certify_render_kernel(const voi
 
 static unsigned grid_of(size_t n) { return (unsigned)((n + kCertifyBlock - 1) / kCertifyBlock); }
 
-// rm_capi.hip has validated the arguments; `prog` is the device copy of the scene's ProgramImage, n > 0
-hipError_t launch_certify_march(const void* prog, const CertifyParams& P, const double* origins, const double* dirs, size_t n,
-                                double* t_lo, double* t_hi, uint8_t* status, int32_t* steps, hipStream_t s)
-{
-    hipLaunchKernelGGL(certify_march_kernel, dim3(grid_of(n)), dim3(kCertifyBlock), 0, s, prog, P, origins, dirs, n, t_lo, t_hi,
-                       status, steps);
-    return hipGetLastError();
-}
-
-hipError_t launch_certify_render(const void* prog, const CertifyParams& P, const CameraParams& cam, int width, int height,
-                                 int row0, int rows, double* t_lo, double* t_hi, uint8_t* status, int32_t* steps, hipStream_t s)
-{
-    const size_t n = (size_t)width * (size_t)rows;
-    hipLaunchKernelGGL(certify_render_kernel, dim3(grid_of(n)), dim3(kCertifyBlock), 0, s, prog, P, cam, width, height, row0, n,
-                       t_lo, t_hi, status, steps);
-    return hipGetLastError();
-}
-
 }  // namespace rm
+
+// ---- rm_certify_* of the C ABI: scenes and programs as the interval oracle ------------------------------------------------
+// (every launch below: the arguments are validated, `prog` is the device copy of the scene's ProgramImage, n > 0)
+using namespace rm::capi;
+
+namespace {
+
+int certify_params(int id, const RmCertifyConfig* cfg, rm::CertifyParams* P)
+{
+    char why[160];
+    if (!rm::certify_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
+        return fail(RM_E_BAD_ARG, "RmCertifyConfig: %s", why);
+    return RM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rm_certify_supported(int scene_id) { return rm_segment_supported(scene_id); }
+
+int rm_certify_march_rays(int scene_id, const RmCertifyConfig* cfg, const double* origins, const double* dirs, size_t n,
+                          double* t_lo, double* t_hi, uint8_t* status, int32_t* steps)
+{
+    rm::CertifyParams P;
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return certify_params(scene_id, cfg, &P); }, nullptr, nullptr, n,
+                    origins && dirs && t_lo && t_hi && status, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_origins = st.in(stage_in[0], origins, n * 24);
+    const double* d_dirs = st.in(stage_in[1], dirs, n * 24);
+    double* d_lo = st.out(stage_out[0], t_lo, n * 8);
+    double* d_hi = st.out(stage_out[1], t_hi, n * 8);
+    uint8_t* d_status = st.out(stage_out[2], status, n);
+    int32_t* d_steps = st.out(stage_out[3], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    hipLaunchKernelGGL(rm::certify_march_kernel, dim3(rm::grid_of(n)), dim3(rm::kCertifyBlock), 0, lib_stream(), c.prog, P, d_origins,
+                       d_dirs, n, d_lo, d_hi, d_status, d_steps);
+    HIP_TRY(hipGetLastError());
+    return st.finish();
+}
+
+int rm_certify_render(const RmFrameDesc* d, const RmCertifyConfig* cfg, double* t_lo, double* t_hi, uint8_t* status, int32_t* steps,
+                      RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    rm::CertifyParams P;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return certify_params(d->scene_id, cfg, &P); }, d, timing, n, t_lo && t_hi && status,
+                    "t_lo, t_hi and status are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    double* d_lo = st.out(stage_out[0], t_lo, n * 8);
+    double* d_hi = st.out(stage_out[1], t_hi, n * 8);
+    uint8_t* d_status = st.out(stage_out[2], status, n);
+    int32_t* d_steps = st.out(stage_out[3], steps, n * 4);
+    if ((rc = st.begin())) return rc;
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, lib_stream(), [&] {
+        hipLaunchKernelGGL(rm::certify_render_kernel, dim3(rm::grid_of(n)), dim3(rm::kCertifyBlock), 0, lib_stream(), c.prog, P, cam,
+                           d->width, d->height, d->row0, n, d_lo, d_hi, d_status, d_steps);
+        HIP_TRY(hipGetLastError());
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
+}
+
+}  // extern "C"

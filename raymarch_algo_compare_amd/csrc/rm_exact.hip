@@ -8,6 +8,7 @@
 // stack is one 32-bit word, the saved points are register slots (Slots, rm_scene_program.h).
 #include "rm_kernels.h"
 #include "rm_exact.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -60,21 +61,90 @@ __global__ __launch_bounds__(kExactBlock) void exact_render_kernel(const void* p
 
 static unsigned grid_of(size_t n) { return (unsigned)((n + kExactBlock - 1) / kExactBlock); }
 
-// rm_capi.hip has validated the arguments; `prog` is the device copy of the scene's ProgramImage, n > 0
-hipError_t launch_exact_march(const void* prog, const ExactParams& P, const double* origins, const double* dirs, size_t n, double* t,
-                              double* normals, int32_t* leaf, hipStream_t s)
-{
-    hipLaunchKernelGGL(exact_march_kernel, dim3(grid_of(n)), dim3(kExactBlock), 0, s, prog, P, origins, dirs, n, t, normals, leaf);
-    return hipGetLastError();
-}
-
-hipError_t launch_exact_render(const void* prog, const ExactParams& P, const CameraParams& cam, int width, int height, int row0,
-                               int rows, double* depth, uint8_t* hit, double* normal, int32_t* leaf, hipStream_t s)
-{
-    const size_t n = (size_t)width * (size_t)rows;
-    hipLaunchKernelGGL(exact_render_kernel, dim3(grid_of(n)), dim3(kExactBlock), 0, s, prog, P, cam, width, height, row0, n, depth,
-                       hit, normal, leaf);
-    return hipGetLastError();
-}
-
 }  // namespace rm
+
+// ---- rm_exact_* of the C ABI: the interval oracle's scenes that pass exact_supported --------------------------------------
+// (every launch below: the arguments are validated, `prog` is the device copy of the scene's ProgramImage, n > 0)
+using namespace rm::capi;
+
+namespace {
+
+// RM_OK when the scene has an exact form; RM_E_BAD_SCENE with the reason otherwise.  Host only.
+int exact_check_scene(int id)
+{
+    char why[160];
+    if (is_program_id(id)) {
+        bool ok = false;
+        if (!with_program_image(id, [&](const rm::ProgramImage& img) { ok = rm::exact_supported(img, why, sizeof why); }))
+            return no_such_program(id);
+        if (!ok) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: %s", id, why);
+        return RM_OK;
+    }
+    const rm::ProgramImage* img = interval_catalogue_image(id);
+    if (!img) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: it is no composition of primitives", id);
+    if (!rm::exact_supported(*img, why, sizeof why)) return fail(RM_E_BAD_SCENE, "scene %d has no exact form: %s", id, why);
+    return RM_OK;
+}
+
+int exact_params(int id, const RmExactConfig* cfg, rm::ExactParams* P)
+{
+    int rc = exact_check_scene(id);
+    if (rc) return rc;
+    char why[160];
+    if (!rm::exact_resolve(cfg, P, why, sizeof why)) return fail(RM_E_BAD_ARG, "RmExactConfig: %s", why);
+    return RM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rm_exact_supported(int scene_id) { return exact_check_scene(scene_id) == RM_OK ? 1 : 0; }
+
+int rm_exact_march_rays(int scene_id, const RmExactConfig* cfg, const double* origins, const double* dirs, size_t n, double* t,
+                        double* normals, int32_t* leaf)
+{
+    rm::ExactParams P;
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return exact_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_origins = st.in(stage_in[0], origins, n * 24);
+    const double* d_dirs = st.in(stage_in[1], dirs, n * 24);
+    double* d_t = st.out(stage_out[0], t, n * 8);
+    double* d_normals = st.out(stage_out[1], normals, n * 24);
+    int32_t* d_leaf = st.out(stage_out[2], leaf, n * 4);
+    if ((rc = st.begin())) return rc;
+    hipLaunchKernelGGL(rm::exact_march_kernel, dim3(rm::grid_of(n)), dim3(rm::kExactBlock), 0, lib_stream(), c.prog, P, d_origins, d_dirs,
+                       n, d_t, d_normals, d_leaf);
+    HIP_TRY(hipGetLastError());
+    return st.finish();
+}
+
+int rm_exact_render(const RmFrameDesc* d, const RmExactConfig* cfg, double* depth, uint8_t* hit, double* normal, int32_t* leaf,
+                    RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    rm::ExactParams P;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return exact_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
+                    "depth and hit are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    double* d_depth = st.out(stage_out[0], depth, n * 8);
+    uint8_t* d_hit = st.out(stage_out[1], hit, n);
+    double* d_normal = st.out(stage_out[2], normal, n * 24);
+    int32_t* d_leaf = st.out(stage_out[3], leaf, n * 4);
+    if ((rc = st.begin())) return rc;
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, lib_stream(), [&] {
+        hipLaunchKernelGGL(rm::exact_render_kernel, dim3(rm::grid_of(n)), dim3(rm::kExactBlock), 0, lib_stream(), c.prog, P, cam, d->width,
+                           d->height, d->row0, n, d_depth, d_hit, d_normal, d_leaf);
+        HIP_TRY(hipGetLastError());
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
+}
+
+}  // extern "C"

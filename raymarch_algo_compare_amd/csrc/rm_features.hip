@@ -1,7 +1,7 @@
 // rm_features.hip -- the discovery features of a (scene, viewpoint) on the device (rm_features.h; rm_intrinsic_features and
 // rm_view_features in include/rm_hip.h).
 //
-// Intrinsic features, all on one stream; the scene's own sdf_eval launcher runs between the first two (rm_capi.hip):
+// Intrinsic features, all on one stream; the scene's own sdf_eval launcher runs between the first two (rm_intrinsic_features):
 //   feat_points_kernel    one point per thread: the six offset points of every Lipschitz sample, then every chord sample
 //   feat_grad_kernel      one Lipschitz sample per thread: gmag and its key (kScoreNoKey when it is not finite)
 //   feat_chord_kernel     one wavefront per chord: `f < 0` as one ballot per 64 samples, run starts and ends from the masks
@@ -19,7 +19,11 @@
 // No atomics on floating-point values, no slot that depends on scheduling: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+#include <vector>
+
 #include "rm_features.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(256) void feat_select_kernel(IntrinsicLaunch a)
 }
 
 // the kernels before the scene's sdf_eval: the points
-hipError_t launch_feature_points(const IntrinsicLaunch& a, hipStream_t s)
+static hipError_t launch_feature_points(const IntrinsicLaunch& a, hipStream_t s)
 {
     const size_t n = feat_lip_points(a.nsets, a.n_lip) + feat_chord_points(a.nsets, a.n_chords, a.chord_steps);
     if (n) hipLaunchKernelGGL(feat_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, n);
@@ -181,7 +185,7 @@ hipError_t launch_feature_points(const IntrinsicLaunch& a, hipStream_t s)
 }
 
 // ... and after it: gradients, runs, selections
-hipError_t launch_feature_reduce(const IntrinsicLaunch& a, hipStream_t s)
+static hipError_t launch_feature_reduce(const IntrinsicLaunch& a, hipStream_t s)
 {
     const size_t nl = (size_t)a.nsets * (size_t)a.n_lip, nc = (size_t)a.nsets * (size_t)a.n_chords;
     if (nl) hipLaunchKernelGGL(feat_grad_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, a, nl);
@@ -300,8 +304,8 @@ __global__ __launch_bounds__(64) void view_finish_kernel(ViewLaunch a)
     feat_view_combine(a.width, a.height, counts, ssq, lo, hi, a.out + v);
 }
 
-// rm_capi.hip has validated the arguments: sides >= 1, nviews in [1, kFeatMaxViews], every buffer sized for them
-hipError_t launch_view_features(const ViewLaunch& a, hipStream_t s)
+// rm_view_features has validated the arguments: sides >= 1, nviews in [1, kFeatMaxViews], every buffer sized for them
+static hipError_t launch_view_features(const ViewLaunch& a, hipStream_t s)
 {
     const unsigned ntiles = (unsigned)(score_tiles_x(a.width) * score_tiles_y(a.height)), nv = (unsigned)a.nviews;
     hipLaunchKernelGGL(view_tile_kernel, dim3(ntiles, nv), dim3(kSsimTile), 0, s, a);
@@ -312,3 +316,126 @@ hipError_t launch_view_features(const ViewLaunch& a, hipStream_t s)
 }
 
 }  // namespace rm
+
+// ---- rm_intrinsic_features and rm_view_features of the C ABI --------------------------------------------------------------
+
+static_assert(sizeof(RmIntrinsicFeatures) == sizeof(rm::IntrinsicFeatures) && offsetof(RmIntrinsicFeatures, n_slabs) == offsetof(rm::IntrinsicFeatures, n_slabs),
+              "rm::IntrinsicFeatures is RmIntrinsicFeatures");
+static_assert(sizeof(RmViewFeatures) == sizeof(rm::ViewFeatures) && offsetof(RmViewFeatures, hit_rate) == offsetof(rm::ViewFeatures, hit_rate) &&
+              offsetof(RmViewFeatures, box_hi) == offsetof(rm::ViewFeatures, box_hi), "rm::ViewFeatures is RmViewFeatures");
+static_assert(sizeof(RmViewMaps) == sizeof(rm::ViewMaps), "rm::ViewMaps is RmViewMaps");
+
+using namespace rm::capi;
+
+namespace {
+
+WsBuf feat_in[4], feat_xyz, feat_f, feat_keys, feat_slabs;   // rm_intrinsic_features: pts / chords / seglen / ts, points, values, keys
+WsBuf feat_counts, feat_gmag, feat_out;                      // its run counts, optional gmag, results
+WsBuf view_map[4], view_tab, view_cams, view_small;          // rm_view_features: depth / normal / evals / hit, the table, partials + results
+
+}  // namespace
+
+extern "C" {
+
+int rm_intrinsic_features(int scene_id, int32_t nsets, int32_t n_lip, const double* pts, double lip_eps, int32_t n_chords,
+                          const double* chords, const double* seglen, int32_t chord_steps, const double* ts, RmIntrinsicFeatures* out,
+                          double* gmag_out, int32_t* slab_counts_out, RmTiming* timing)
+{
+    if (const char* why = rm::feat_check_intrinsic(nsets, n_lip, pts, lip_eps, n_chords, chords, seglen, chord_steps, ts, out))
+        return fail(RM_E_BAD_ARG, "rm_intrinsic_features: %s", why);
+    if (const char* why = rm::feat_check_seglen(nsets, n_chords, seglen)) return fail(RM_E_BAD_ARG, "rm_intrinsic_features: %s", why);
+    int rc = check_scene(scene_id);
+    if (rc || (timing && (rc = check_timing(timing)))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const hipStream_t s = lib_stream();
+    const void* data = nullptr;
+    if ((rc = scene_data(scene_id, &data))) return rc;
+    const size_t ns = (size_t)nsets, nl = ns * (size_t)n_lip, nc = ns * (size_t)n_chords;
+    const size_t npts = rm::feat_lip_points(nsets, n_lip) + rm::feat_chord_points(nsets, n_chords, chord_steps);
+    Staged st(e);
+    rm::IntrinsicLaunch a;
+    memset(&a, 0, sizeof a);
+    a.nsets = nsets; a.n_lip = n_lip; a.n_chords = n_chords; a.chord_steps = chord_steps; a.eps = lip_eps;
+    if (nl) a.pts = st.in(feat_in[0], pts, nl * 24);
+    if (nc) a.chords = st.in(feat_in[1], chords, nc * 48);
+    if (nc) a.seglen = st.in(feat_in[2], seglen, nc * 8);
+    a.ts = st.in(feat_in[3], ts, (size_t)chord_steps * 8);
+    a.xyz = st.scratch<double>(feat_xyz, npts * 24, 16);
+    a.f = st.scratch<double>(feat_f, npts * 8, 16);
+    a.gkeys = st.scratch<uint64_t>(feat_keys, nl * 8, 16);
+    a.slabs = st.scratch<uint64_t>(feat_slabs, nc * (size_t)rm::feat_max_runs(chord_steps) * 8, 16);
+    a.counts = nc && slab_counts_out ? st.out(feat_counts, slab_counts_out, nc * 4) : st.scratch<int32_t>(feat_counts, nc * 4, 16);
+    a.gmag_out = nl ? st.out(feat_gmag, gmag_out, nl * 8) : nullptr;
+    a.out = (rm::IntrinsicFeatures*)st.out(feat_out, out, ns * sizeof(RmIntrinsicFeatures));
+    if ((rc = st.begin())) return rc;
+    const SdfEval sdf_eval = sdf_eval_of(scene_id);
+    rc = once_or_timed(e, timing, s, [&] {
+        HIP_TRY(rm::launch_feature_points(a, s));
+        HIP_TRY(sdf_eval(a.xyz, npts, a.f, data, s));
+        HIP_TRY(rm::launch_feature_reduce(a, s));
+        return (int)RM_OK;
+    });
+    if (rc) return rc;
+    return st.finish();
+}
+
+int rm_view_features(int32_t width, int32_t height, int32_t nviews, const double* cams, const RmViewMaps* maps, RmViewFeatures* out,
+                     RmTiming* timing)
+{
+    if (const char* why = rm::feat_check_view(nviews, cams, maps, out)) return fail(RM_E_BAD_ARG, "rm_view_features: %s", why);
+    if (width <= 0 || height <= 0) return fail(RM_E_BAD_DIMS, "a %dx%d image has no pixel", width, height);
+    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
+    for (int v = 0; v < nviews; ++v)
+        if (!maps[v].depth || !maps[v].normal || !maps[v].evals || !maps[v].hit)
+            return fail(RM_E_BAD_ARG, "rm_view_features: view %d: depth, normal, evals and hit are required", v);
+    for (size_t i = 0; i < (size_t)nviews * 14; ++i)
+        if (!rm::feat_is_finite(cams[i])) return fail(RM_E_BAD_ARG, "rm_view_features: camera %zu: field %zu is not finite", i / 14, i % 14);
+    int rc = timing ? check_timing(timing) : RM_OK;
+    if (rc) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const hipStream_t s = lib_stream();
+    const size_t npix = (size_t)width * (size_t)height, nv = (size_t)nviews;
+    const size_t ntiles = (size_t)rm::score_tiles_x(width) * (size_t)rm::score_tiles_y(height);
+    const size_t o_counts = 0, o_box = align256(o_counts + nv * rm::kViewCounts * ntiles * 8), o_mean = align256(o_box + nv * 6 * ntiles * 8);
+    const size_t o_part = align256(o_mean + nv * 8), o_out = align256(o_part + nv * ntiles * 8), small = o_out + nv * sizeof(rm::ViewFeatures);
+    static_assert(sizeof(rm::CameraParams) == 14 * sizeof(double), "cams is an array of CameraParams");
+    if ((rc = view_map[0].ensure(nv * npix * 4)) || (rc = view_map[1].ensure(nv * npix * 12)) || (rc = view_map[2].ensure(nv * npix * 4)) ||
+        (rc = view_map[3].ensure(nv * npix)) || (rc = view_tab.ensure(nv * sizeof(rm::ViewMaps))) ||
+        (rc = view_cams.ensure(nv * sizeof(rm::CameraParams))) || (rc = view_small.ensure(small)))
+        return rc;
+    std::vector<rm::ViewMaps> table(nv);
+    for (size_t v = 0; v < nv; ++v) {
+        rm::ViewMaps& d = table[v];
+        d.depth = (const float*)view_map[0].p + v * npix;
+        d.normal = (const float*)view_map[1].p + v * npix * 3;
+        d.evals = (const float*)view_map[2].p + v * npix;
+        d.hit = (const uint8_t*)view_map[3].p + v * npix;
+        HIP_TRY(hipMemcpyAsync((void*)d.depth, maps[v].depth, npix * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync((void*)d.normal, maps[v].normal, npix * 12, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync((void*)d.evals, maps[v].evals, npix * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync((void*)d.hit, maps[v].hit, npix, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(view_tab.p, table.data(), nv * sizeof(rm::ViewMaps), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(view_cams.p, cams, nv * sizeof(rm::CameraParams), hipMemcpyHostToDevice, s));
+    rm::ViewLaunch a;
+    a.width = width; a.height = height; a.nviews = nviews;
+    a.maps = (const rm::ViewMaps*)view_tab.p;
+    a.cams = (const rm::CameraParams*)view_cams.p;
+    char* sm = (char*)view_small.p;
+    a.icounts = (long long*)(sm + o_counts); a.box = (double*)(sm + o_box); a.mean = (double*)(sm + o_mean);
+    a.part = (double*)(sm + o_part); a.out = (rm::ViewFeatures*)(sm + o_out);
+    rc = once_or_timed(e, timing, s, [&] {
+        HIP_TRY(rm::launch_view_features(a, s));
+        return (int)RM_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, a.out, nv * sizeof(rm::ViewFeatures), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 // leave, so the ballots of the wave-uniform forms (rm_band_needed<true>, rm_pow_half<true>) see exactly the live lanes.
 #include "rm_kernels.h"
 #include "../../include/rm_hip.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -90,8 +91,8 @@ static hipError_t launch_math(const double* a, const double* b, size_t n, uint64
     return hipGetLastError();
 }
 
-// rm_capi.hip (rm_debug_math_eval) has checked fn, lane_mask != 0, n > 0 and the buffers the routine uses
-hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1,
+// rm_debug_math_eval has checked fn, lane_mask != 0, n > 0 and the buffers the routine uses
+static hipError_t launch_math_check(int fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1,
                              hipStream_t s)
 {
     switch (fn) {
@@ -124,8 +125,8 @@ __global__ __launch_bounds__(64 * kWavesPerWG) void bail4_check_kernel(const dou
     band[e] = rm_bail4_band(x) ? 1.0 : 0.0;
 }
 
-// rm_capi.hip (rm_debug_bail4_eval) has checked lane_mask != 0, n > 0 and the buffers
-hipError_t launch_bail4_check(bool sparse, const double* s, size_t n, uint64_t lane_mask, double* decision, double* band, hipStream_t st)
+// rm_debug_bail4_eval has checked lane_mask != 0, n > 0 and the buffers
+static hipError_t launch_bail4_check(bool sparse, const double* s, size_t n, uint64_t lane_mask, double* decision, double* band, hipStream_t st)
 {
     const int live = __builtin_popcountll(lane_mask);
     const size_t waves = (n + live - 1) / live;
@@ -136,3 +137,48 @@ hipError_t launch_bail4_check(bool sparse, const double* s, size_t n, uint64_t l
 }
 
 }  // namespace rm
+
+// ---- rm_debug_math_eval and rm_debug_bail4_eval of the C ABI ---------------------------------------------------------------
+using namespace rm::capi;
+
+extern "C" {
+
+int rm_debug_math_eval(int32_t fn, const double* a, const double* b, size_t n, uint64_t lane_mask, double* out0, double* out1)
+{
+    Entry e;
+    int rc = e.rc();
+    if (rc) return rc;
+    if (fn < 0 || fn >= RM_MATH_COUNT) return fail(RM_E_BAD_ARG, "fn %d out of range [0, %d)", (int)fn, (int)RM_MATH_COUNT);
+    if (lane_mask == 0) return fail(RM_E_BAD_ARG, "lane_mask is 0: no live lane");
+    const bool two_in = fn == RM_MATH_POW || fn == RM_MATH_ATAN2 || fn == RM_MATH_ATAN2_U;
+    const bool two_out = fn == RM_MATH_POW2 || fn == RM_MATH_POW_HALF_GUARD || fn == RM_MATH_SINCOS || fn == RM_MATH_SINCOS_U;
+    if (n == 0) return RM_OK;
+    if (!a || !out0 || (two_in && !b) || (two_out && !out1)) return fail(RM_E_BAD_ARG, "NULL buffer");
+    Staged st(e);
+    const double* d_a = st.in(stage_in[0], a, n * 8);
+    const double* d_b = two_in ? st.in(stage_in[1], b, n * 8) : nullptr;
+    double* d_out0 = st.out(stage_out[0], out0, n * 8);
+    double* d_out1 = st.out(stage_out[1], two_out ? out1 : nullptr, n * 8);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_math_check(fn, d_a, d_b, n, lane_mask, d_out0, d_out1, lib_stream()));
+    return st.finish();
+}
+
+int rm_debug_bail4_eval(const double* s, size_t n, uint64_t lane_mask, int32_t sparse, double* decision, double* band)
+{
+    Entry e;
+    int rc = e.rc();
+    if (rc) return rc;
+    if (lane_mask == 0) return fail(RM_E_BAD_ARG, "lane_mask is 0: no live lane");
+    if (n == 0) return RM_OK;
+    if (!s || !decision || !band) return fail(RM_E_BAD_ARG, "NULL buffer");
+    Staged st(e);
+    const double* d_s = st.in(stage_in[0], s, n * 8);
+    double* d_out0 = st.out(stage_out[0], decision, n * 8);
+    double* d_out1 = st.out(stage_out[1], band, n * 8);
+    if ((rc = st.begin())) return rc;
+    HIP_TRY(rm::launch_bail4_check(sparse != 0, d_s, n, lane_mask, d_out0, d_out1, lib_stream()));
+    return st.finish();
+}
+
+}  // extern "C"

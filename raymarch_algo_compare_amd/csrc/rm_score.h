@@ -211,7 +211,7 @@ RM_HD void score_combine(const int64_t* counts, const double* sums, const ScoreR
     if (counts[SC_NAN_ANGLE] == 0) out->normal_p95_deg = score_canonical(score_p95(score_unkey(k.lo[2]), score_unkey(k.hi[2]), n));
 }
 
-// ---- the device call (launch_score of rm_score.hip) -----------------------------------------------------------------------
+// ---- the device call (rm_score_captures and its launch_score, both in rm_score.hip) ---------------------------------------
 
 // the state of one radix selection: the digits chosen so far, the rank left inside their group, the keys below the
 // group and, after the last pass, the keys equal to the selected one

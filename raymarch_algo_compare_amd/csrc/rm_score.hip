@@ -19,7 +19,10 @@
 // No atomics on floating-point values and no order that depends on scheduling: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "rm_score.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -233,9 +236,9 @@ __global__ __launch_bounds__(64) void score_finish_kernel(ScoreLaunch a)
     score_combine(counts, sums, k, a.has_normal != 0, a.out + m);
 }
 
-// rm_capi.hip has validated the arguments: sides >= 1, nmethods in [1, kScoreMaxMethods], band_k <= kScoreMaxBand,
+// rm_score_captures has validated the arguments: sides >= 1, nmethods in [1, kScoreMaxMethods], band_k <= kScoreMaxBand,
 // every buffer sized for them
-hipError_t launch_score(const ScoreLaunch& a, hipStream_t s)
+static hipError_t launch_score(const ScoreLaunch& a, hipStream_t s)
 {
     const size_t npix = (size_t)a.width * (size_t)a.height;
     const unsigned ntiles = (unsigned)(score_tiles_x(a.width) * score_tiles_y(a.height));
@@ -257,3 +260,87 @@ hipError_t launch_score(const ScoreLaunch& a, hipStream_t s)
 }
 
 }  // namespace rm
+
+// ---- rm_score_captures of the C ABI ---------------------------------------------------------------------------------------
+
+static_assert(sizeof(RmScoreResult) == sizeof(rm::ScoreResult) && offsetof(RmScoreResult, depth_mae) == offsetof(rm::ScoreResult, depth_mae) &&
+              offsetof(RmScoreResult, normal_p95_deg) == offsetof(rm::ScoreResult, normal_p95_deg), "rm::ScoreResult is RmScoreResult");
+
+using namespace rm::capi;
+
+namespace {
+
+WsBuf score_depth, score_normal, score_hit, score_caps;   // the methods' maps, then the reference's
+WsBuf score_band, score_keys, score_small, score_part;    // the band, sample keys, counts / selections / results, partial sums
+
+int score_check_maps(const RmScoreMaps& c, const RmScoreMaps& ref, const char* who, int index)
+{
+    if (!c.depth || !c.hit) return fail(RM_E_BAD_ARG, "%s %d: depth and hit are required", who, index);
+    if (!c.normal != !ref.normal) return fail(RM_E_BAD_ARG, "%s %d: normal is NULL on one side only", who, index);
+    return RM_OK;
+}
+
+}  // namespace
+
+extern "C" int rm_score_captures(int32_t width, int32_t height, int32_t band_k, const RmScoreMaps* reference, const RmScoreMaps* methods,
+                                 int32_t nmethods, RmScoreResult* out, RmTiming* timing)
+{
+    if (!reference || !methods || !out) return fail(RM_E_BAD_ARG, "reference, methods or out is NULL");
+    if (nmethods <= 0 || nmethods > rm::kScoreMaxMethods)
+        return fail(RM_E_BAD_ARG, "nmethods %d outside [1, %d]", nmethods, rm::kScoreMaxMethods);
+    if (band_k > rm::kScoreMaxBand) return fail(RM_E_BAD_ARG, "band_k %d above %d", band_k, rm::kScoreMaxBand);
+    if (width <= 0 || height <= 0) return fail(RM_E_BAD_DIMS, "a %dx%d image has no pixel", width, height);
+    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
+    int rc = score_check_maps(*reference, *reference, "reference", 0);
+    for (int m = 0; !rc && m < nmethods; ++m) rc = score_check_maps(methods[m], *reference, "method", m);
+    if (rc || (timing && (rc = check_timing(timing)))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const hipStream_t s = lib_stream();
+    const size_t npix = (size_t)width * (size_t)height, nm = (size_t)nmethods, caps = nm + 1;   // the reference is capture `nmethods`
+    const size_t ntiles = (size_t)rm::score_tiles_x(width) * (size_t)rm::score_tiles_y(height);
+    const bool has_normal = reference->normal != nullptr;
+    // one small buffer: counts, selections, histograms, least keys above, results
+    const size_t o_counts = 0, o_sel = align256(o_counts + nm * rm::kScoreCounts * 8);
+    const size_t o_hist = align256(o_sel + nm * rm::kScoreSelects * sizeof(rm::ScoreSelect));
+    const size_t o_above = align256(o_hist + nm * rm::kScoreSelects * 256 * 4);
+    const size_t o_out = align256(o_above + nm * rm::kScoreSelects * 8), small = o_out + nm * sizeof(rm::ScoreResult);
+    // every capture has a slot of W*H doubles (and 3 W*H for the normals), whichever type it holds
+    if ((rc = score_depth.ensure(caps * npix * 8)) || (rc = score_hit.ensure(caps * npix)) ||
+        (has_normal && (rc = score_normal.ensure(caps * npix * 24))) || (rc = score_caps.ensure(caps * sizeof(rm::ScoreMaps))) ||
+        (band_k >= 0 && (rc = score_band.ensure(npix))) || (rc = score_keys.ensure(nm * (has_normal ? 2 : 1) * npix * 8)) ||
+        (rc = score_small.ensure(small)) || (rc = score_part.ensure(nm * rm::kScoreSums * ntiles * 8)))
+        return rc;
+    std::vector<rm::ScoreMaps> table(caps);
+    for (size_t m = 0; m < caps; ++m) {
+        const RmScoreMaps& c = m < nm ? methods[m] : *reference;
+        const size_t elem = c.fp64 ? 8 : 4;
+        rm::ScoreMaps& d = table[m];
+        d.depth = (char*)score_depth.p + m * npix * 8;
+        d.normal = has_normal ? (char*)score_normal.p + m * npix * 24 : nullptr;
+        d.hit = (uint8_t*)score_hit.p + m * npix;
+        d.fp64 = c.fp64 != 0;
+        HIP_TRY(hipMemcpyAsync((void*)d.depth, c.depth, npix * elem, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync((void*)d.hit, c.hit, npix, hipMemcpyHostToDevice, s));
+        if (has_normal) HIP_TRY(hipMemcpyAsync((void*)d.normal, c.normal, npix * 3 * elem, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(score_caps.p, table.data(), caps * sizeof(rm::ScoreMaps), hipMemcpyHostToDevice, s));
+    rm::ScoreLaunch a;
+    a.width = width; a.height = height; a.nmethods = nmethods; a.has_normal = has_normal; a.band_k = band_k < 0 ? -1 : band_k;
+    a.caps = (const rm::ScoreMaps*)score_caps.p;
+    a.band = (uint8_t*)score_band.p;
+    a.keys = (uint64_t*)score_keys.p;
+    char* sm = (char*)score_small.p;
+    a.counts = (unsigned long long*)(sm + o_counts); a.sel = (rm::ScoreSelect*)(sm + o_sel); a.hist = (uint32_t*)(sm + o_hist);
+    a.above = (unsigned long long*)(sm + o_above); a.out = (rm::ScoreResult*)(sm + o_out);
+    a.part = (double*)score_part.p;
+    rc = once_or_timed(e, timing, s, [&] {
+        HIP_TRY(rm::launch_score(a, s));
+        return (int)RM_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, a.out, nm * sizeof(rm::ScoreResult), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RM_OK;
+}

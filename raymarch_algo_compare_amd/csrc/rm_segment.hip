@@ -7,6 +7,7 @@
 // most `budget` trips (RM_SEGMENT_MAX_STEPS).
 #include "rm_kernels.h"
 #include "rm_segment.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -69,28 +70,86 @@ __global__ __launch_bounds__(kSegmentBlock) void segment_render_kernel(const voi
 
 static unsigned grid_of(size_t n) { return (unsigned)((n + kSegmentBlock - 1) / kSegmentBlock); }
 
-// rm_capi.hip has validated the arguments; `prog` is the device copy of the scene's ProgramImage, n > 0
-hipError_t launch_segment_sdf(const void* prog, const double* segs, size_t n, double* out, hipStream_t s)
-{
-    hipLaunchKernelGGL(segment_sdf_kernel, dim3(grid_of(n)), dim3(kSegmentBlock), 0, s, prog, segs, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_segment_march(const void* prog, const SegmentParams& P, const double* origins, const double* dirs, size_t n,
-                                double* t, int32_t* iters, double* cursor, hipStream_t s)
-{
-    hipLaunchKernelGGL(segment_march_kernel, dim3(grid_of(n)), dim3(kSegmentBlock), 0, s, prog, P, origins, dirs, n, t, iters,
-                       cursor);
-    return hipGetLastError();
-}
-
-hipError_t launch_segment_render(const void* prog, const SegmentParams& P, const CameraParams& cam, int width, int height,
-                                 int row0, int rows, double* depth, uint8_t* hit, int32_t* iters, double* cursor, hipStream_t s)
-{
-    const size_t n = (size_t)width * (size_t)rows;
-    hipLaunchKernelGGL(segment_render_kernel, dim3(grid_of(n)), dim3(kSegmentBlock), 0, s, prog, P, cam, width, height, row0, n,
-                       depth, hit, iters, cursor);
-    return hipGetLastError();
-}
-
 }  // namespace rm
+
+// ---- rm_segment_* of the C ABI: scenes and programs as the interval oracle ------------------------------------------------
+// (every launch below: the arguments are validated, `prog` is the device copy of the scene's ProgramImage, n > 0)
+using namespace rm::capi;
+
+namespace {
+
+int segment_params(int id, const RmSegmentConfig* cfg, rm::SegmentParams* P)
+{
+    char why[160];
+    if (!rm::segment_resolve(cfg, rm::interval_scene_bound(id), P, why, sizeof why))
+        return fail(RM_E_BAD_ARG, "RmSegmentConfig: %s", why);
+    return RM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rm_segment_supported(int scene_id) { return rm_interval_supported(scene_id); }
+
+int rm_segment_sdf_eval(int scene_id, const double* segs, size_t n, double* out)
+{
+    SoundCall c;
+    int rc = c.open(scene_id, no_config, nullptr, nullptr, n, segs && out, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_segs = st.in(stage_in[0], segs, n * 64);
+    double* d_out = st.out(stage_out[0], out, n * 32);
+    if ((rc = st.begin())) return rc;
+    hipLaunchKernelGGL(rm::segment_sdf_kernel, dim3(rm::grid_of(n)), dim3(rm::kSegmentBlock), 0, lib_stream(), c.prog, d_segs, n, d_out);
+    HIP_TRY(hipGetLastError());
+    return st.finish();
+}
+
+int rm_segment_march_rays(int scene_id, const RmSegmentConfig* cfg, const double* origins, const double* dirs, size_t n,
+                          double* t, int32_t* iters, double* cursor)
+{
+    rm::SegmentParams P;
+    SoundCall c;
+    int rc = c.open(scene_id, [&] { return segment_params(scene_id, cfg, &P); }, nullptr, nullptr, n, origins && dirs && t, "NULL buffer");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    const double* d_origins = st.in(stage_in[0], origins, n * 24);
+    const double* d_dirs = st.in(stage_in[1], dirs, n * 24);
+    double* d_t = st.out(stage_out[0], t, n * 8);
+    int32_t* d_iters = st.out(stage_out[1], iters, n * 4);
+    double* d_cursor = st.out(stage_out[2], cursor, n * 8);
+    if ((rc = st.begin())) return rc;
+    hipLaunchKernelGGL(rm::segment_march_kernel, dim3(rm::grid_of(n)), dim3(rm::kSegmentBlock), 0, lib_stream(), c.prog, P, d_origins,
+                       d_dirs, n, d_t, d_iters, d_cursor);
+    HIP_TRY(hipGetLastError());
+    return st.finish();
+}
+
+int rm_segment_render(const RmFrameDesc* d, const RmSegmentConfig* cfg, double* depth, uint8_t* hit, int32_t* iters,
+                      double* cursor, RmTiming* timing)
+{
+    if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
+    rm::SegmentParams P;
+    const size_t n = (size_t)d->width * (size_t)d->rows;
+    SoundCall c;
+    int rc = c.open(d->scene_id, [&] { return segment_params(d->scene_id, cfg, &P); }, d, timing, n, depth && hit,
+                    "depth and hit are required");
+    if (rc || !c.prog) return rc;
+    Staged st(*c.e);
+    double* d_depth = st.out(stage_out[0], depth, n * 8);
+    uint8_t* d_hit = st.out(stage_out[1], hit, n);
+    int32_t* d_iters = st.out(stage_out[2], iters, n * 4);
+    double* d_cursor = st.out(stage_out[3], cursor, n * 8);
+    if ((rc = st.begin())) return rc;
+    const rm::CameraParams cam = camera_of(d->cam);
+    rc = once_or_timed(*c.e, timing, lib_stream(), [&] {
+        hipLaunchKernelGGL(rm::segment_render_kernel, dim3(rm::grid_of(n)), dim3(rm::kSegmentBlock), 0, lib_stream(), c.prog, P, cam,
+                           d->width, d->height, d->row0, n, d_depth, d_hit, d_iters, d_cursor);
+        HIP_TRY(hipGetLastError());
+        return (int)RM_OK;
+    });
+    return rc ? rc : st.finish();
+}
+
+}  // extern "C"

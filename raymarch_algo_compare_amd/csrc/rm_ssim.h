@@ -124,7 +124,7 @@ RM_HD double ssim_pixel(int32_t sx, int32_t sy, int32_t sxx, int32_t syy, int32_
     return (A1 * A2) / (B1 * B2);
 }
 
-// ---- the device call (launch_ssim of rm_ssim.hip) -----------------------------------------------------------------------
+// ---- the device call (rm_ssim_scores and its launch_ssim, both in rm_ssim.hip) ------------------------------------------
 
 constexpr int kSsimMaxMethods = 65535;                     // a grid's z extent
 

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rm_ssim.h"
+#include "rm_capi_internal.h"
 
 namespace rm {
 
@@ -130,8 +131,8 @@ __global__ __launch_bounds__(64) void ssim_finish_kernel(SsimLaunch a)
     if (t == 0) ssim_combine(s_sum, ssd, a.width, a.height, a.has_normal != 0, a.has_color != 0, a.out + 4 * (size_t)m);
 }
 
-// rm_capi.hip has validated the arguments: sides >= 7, nmethods in [1, kSsimMaxMethods], every buffer sized for them
-hipError_t launch_ssim(const SsimLaunch& a, hipStream_t s)
+// rm_ssim_scores has validated the arguments: sides >= 7, nmethods in [1, kSsimMaxMethods], every buffer sized for them
+static hipError_t launch_ssim(const SsimLaunch& a, hipStream_t s)
 {
     const size_t npix = (size_t)a.width * (size_t)a.height;
     const unsigned ntiles = (unsigned)(ssim_tiles_x(a.width) * ssim_tiles_y(a.height));
@@ -142,3 +143,75 @@ hipError_t launch_ssim(const SsimLaunch& a, hipStream_t s)
 }
 
 }  // namespace rm
+
+// ---- rm_ssim_scores of the C ABI ------------------------------------------------------------------------------------------
+using namespace rm::capi;
+
+namespace {
+
+WsBuf ssim_depth, ssim_normal, ssim_color, ssim_hit;   // the methods' maps, then the reference's
+WsBuf ssim_ref, ssim_part, ssim_ssd, ssim_out;         // the reference images, partial sums and scores
+
+int ssim_check_maps(const RmCaptureMaps& c, const RmCaptureMaps& ref, const char* who, int index)
+{
+    if (!c.depth || !c.hit) return fail(RM_E_BAD_ARG, "%s %d: depth and hit are required", who, index);
+    if (!c.normal != !ref.normal) return fail(RM_E_BAD_ARG, "%s %d: normal is NULL on one side only", who, index);
+    if (!c.color != !ref.color) return fail(RM_E_BAD_ARG, "%s %d: color is NULL on one side only", who, index);
+    return RM_OK;
+}
+
+}  // namespace
+
+extern "C" int rm_ssim_scores(int32_t width, int32_t height, const RmCaptureMaps* reference, const RmCaptureMaps* methods,
+                              int32_t nmethods, double* out, RmTiming* timing)
+{
+    if (!reference || !methods || !out) return fail(RM_E_BAD_ARG, "reference, methods or out is NULL");
+    if (nmethods <= 0 || nmethods > rm::kSsimMaxMethods)
+        return fail(RM_E_BAD_ARG, "nmethods %d outside [1, %d]", nmethods, rm::kSsimMaxMethods);
+    if (width < rm::kSsimWin || height < rm::kSsimWin)
+        return fail(RM_E_BAD_DIMS, "a %dx%d image holds no %dx%d window", width, height, rm::kSsimWin, rm::kSsimWin);
+    if ((long long)width * height > (1ll << 31) - 1) return fail(RM_E_BAD_DIMS, "image too large");
+    int rc = ssim_check_maps(*reference, *reference, "reference", 0);
+    for (int m = 0; !rc && m < nmethods; ++m) rc = ssim_check_maps(methods[m], *reference, "method", m);
+    if (rc || (timing && (rc = check_timing(timing)))) return rc;
+    Entry e;
+    if ((rc = e.rc())) return rc;
+
+    const hipStream_t s = lib_stream();
+    const size_t npix = (size_t)width * (size_t)height, caps = (size_t)nmethods + 1;      // the reference is capture `nmethods`
+    const size_t ntiles = (size_t)rm::ssim_tiles_x(width) * (size_t)rm::ssim_tiles_y(height);
+    const bool has_normal = reference->normal != nullptr, has_color = reference->color != nullptr;
+    if ((rc = ssim_depth.ensure(caps * npix * 4)) || (rc = ssim_hit.ensure(caps * npix)) ||
+        (has_normal && (rc = ssim_normal.ensure(caps * npix * 12))) || (has_color && (rc = ssim_color.ensure(caps * npix * 12))) ||
+        (rc = ssim_ref.ensure(rm::kSsimChannels * npix)) || (rc = ssim_part.ensure((size_t)nmethods * rm::kSsimChannels * ntiles * 8)) ||
+        (rc = ssim_ssd.ensure((size_t)nmethods * 3 * ntiles * 8)) || (rc = ssim_out.ensure((size_t)nmethods * 32)))
+        return rc;
+    for (size_t m = 0; m < caps; ++m) {
+        const RmCaptureMaps& c = m < (size_t)nmethods ? methods[m] : *reference;
+        HIP_TRY(hipMemcpyAsync((float*)ssim_depth.p + m * npix, c.depth, npix * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync((uint8_t*)ssim_hit.p + m * npix, c.hit, npix, hipMemcpyHostToDevice, s));
+        if (has_normal) HIP_TRY(hipMemcpyAsync((float*)ssim_normal.p + m * npix * 3, c.normal, npix * 12, hipMemcpyHostToDevice, s));
+        if (has_color) HIP_TRY(hipMemcpyAsync((float*)ssim_color.p + m * npix * 3, c.color, npix * 12, hipMemcpyHostToDevice, s));
+    }
+    double lo, hi;
+    rm::ssim_depth_minmax(reference->depth, reference->hit, npix, &lo, &hi);
+    rm::SsimLaunch a;
+    a.width = width; a.height = height; a.nmethods = nmethods; a.has_normal = has_normal; a.has_color = has_color;
+    a.range = rm::ssim_depth_range(lo, hi);
+    a.depth = (const float*)ssim_depth.p; a.hit = (const uint8_t*)ssim_hit.p;
+    a.normal = has_normal ? (const float*)ssim_normal.p : nullptr;
+    a.color = has_color ? (const float*)ssim_color.p : nullptr;
+    a.ref_depth = a.depth + (size_t)nmethods * npix; a.ref_hit = a.hit + (size_t)nmethods * npix;
+    a.ref_normal = has_normal ? a.normal + (size_t)nmethods * npix * 3 : nullptr;
+    a.ref_color = has_color ? a.color + (size_t)nmethods * npix * 3 : nullptr;
+    a.ref_img = (uint8_t*)ssim_ref.p;
+    a.part = (double*)ssim_part.p; a.ssd = (long long*)ssim_ssd.p; a.out = (double*)ssim_out.p;
+    rc = once_or_timed(e, timing, s, [&] {
+        HIP_TRY(rm::launch_ssim(a, s));
+        return (int)RM_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, a.out, (size_t)nmethods * 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RM_OK;
+}

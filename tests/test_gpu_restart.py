@@ -1,17 +1,20 @@
 """rm_shutdown() then rm_init() on the same device: the library comes back with nothing left over from its first life.
-A default frame, a single-launch frame that parks rays, a scene-program frame, explicit rays and interval rays give
-bit-identical arrays and statistics before and after the restart; a program registered before the shutdown is still
-registered after it (its device copy is made again)."""
+A default frame, a single-launch frame that parks rays, a scene-program frame, explicit rays, the rays of the five sound
+tracers, two segment ranges, a capture and its SSIM scores, capture scores and view features against itself, and one
+set of intrinsic features give bit-identical arrays and statistics before and after the restart; a program registered
+before the shutdown is still registered after it (its device copy is made again)."""
 import numpy as np
 import pytest
 
-from raymarch_algo_compare_amd import _native, registry
+import features_cases
+from raymarch_algo_compare_amd import _native, features, registry
 from raymarch_algo_compare_amd import scene_program as sp
 from raymarch_algo_compare_amd.camera import Camera
 
 pytestmark = pytest.mark.gpu
 
 W, H = 96, 64
+EXACT_SCENE = 6   # a catalogue scene with an exact form (rm_exact_supported)
 
 
 def _cam(sid):
@@ -46,7 +49,35 @@ def _round(hip, program):
         out[f"march_rays: {k}"] = v
     for k, v in zip(("t", "steps", "normals"), hip.interval_march_rays(0, o, d)):
         out[f"interval_march_rays: {k}"] = v
+    # the subsystems whose workspace buffers are declared next to their kernels, not where rm_shutdown lives
+    for k, v in zip(("t", "normals", "leaf"), hip.exact_march_rays(EXACT_SCENE, o, d)):
+        out[f"exact_march_rays: {k}"] = v
+    for k, v in zip(("t", "iters", "cursor"), hip.segment_march_rays(0, o, d)):
+        out[f"segment_march_rays: {k}"] = v
+    for k, v in zip(("t_lo", "t_hi", "status", "steps"), hip.certify_march_rays(0, o, d)):
+        out[f"certify_march_rays: {k}"] = v
+    for k, v in zip(("t", "steps"), hip.affine_march_rays(0, o, d)):
+        out[f"affine_march_rays: {k}"] = v
+    segs = np.concatenate([o[::32], d[::32], np.full((6, 1), 0.5), np.linspace(1.0, 4.0, 6)[:, None]], axis=1)
+    out["affine_range_eval: range"], out["affine_range_eval: form"] = hip.affine_range_eval(0, segs)
+    out["segment_sdf_eval"] = hip.segment_sdf_eval(0, segs)
+    cap = hip.capture(frames["default"])
+    for k in ("geom", "normal", "depth", "color", "evals", "hit"):
+        out[f"capture: {k}"] = cap[k]
+    out["capture: stats"] = cap["stats"]
+    out["ssim_scores"] = hip.ssim_scores(W, H, cap, [cap])
+    out["score_captures"] = _values(hip.score_captures(W, H, cap, [cap])[0])
+    out["view_features"] = _values(hip.view_features(_cam(10)[None], [cap])[0])
+    _, case = min(features_cases.fixture_cases(), key=lambda c: c[1]["n_lip"] + c[1]["n_chords"] * c[1]["steps"])
+    r = features.intrinsic_features_device(case["scene"], [case["set"]], details=True)[0]
+    out["intrinsic_features: gmag"], out["intrinsic_features: slab_counts"] = r.pop("gmag"), r.pop("slab_counts")
+    out["intrinsic_features"] = _values(r)
     return out
+
+
+def _values(fields):
+    """a result dict's numbers (scalars and small arrays) as one float64 array, for the comparison of bits"""
+    return np.concatenate([np.atleast_1d(np.asarray(fields[k], np.float64)) for k in sorted(fields)])
 
 
 def _same_bits(a, b):
