@@ -1,8 +1,11 @@
 // rm_capi_internal.h -- what the entry points of the C ABI (include/rm_hip.h) share.  Host only.
 //
-// The entry points of an analysis subsystem sit below its kernels (rm_interval.hip ... rm_math_check.hip) and reach the
-// library's lock, stream, staging and timing through this header.  rm_capi.hip defines what is declared here, except the
-// interval oracle's part at the end (rm_interval.hip), and keeps the session to itself.
+// The entry points of a subsystem sit below its kernels -- the march's host side in rm_frame.hip, the RCCL exchange in
+// rm_gather.hip, the analysis calls in rm_interval.hip ... rm_math_check.hip -- and reach the library's lock, device,
+// stream, staging and timing through this header.  rm_capi.hip defines what is declared here, except check_desc and
+// frame_stream_destroyed (rm_frame.hip) and the interval oracle's part at the end (rm_interval.hip), and keeps the
+// session to itself.  What a unit makes or remembers for one rm_init .. rm_shutdown life it declares as a SessionItem
+// next to the code that uses it; rm_shutdown walks those, as it walks the workspace buffers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,7 +17,7 @@
 
 namespace rm {
 
-struct CameraParams; struct IntervalParams; struct ProgramImage;
+struct CameraParams; struct IntervalParams; struct ProgramImage; struct SceneLaunchers;
 
 namespace capi {
 
@@ -59,7 +62,68 @@ struct Buf {
 extern Buf* g_workspace_bufs;
 struct WsBuf : Buf { WsBuf() : Buf(g_workspace_bufs) {} };
 
+// What belongs to one rm_init .. rm_shutdown life of the library, the device memory aside: events and streams made on
+// first use, and host state that describes the session.  Like a Buf, every item links itself into a constant-initialised
+// list when it is constructed, and rm_shutdown ends them all in one walk (the device selected and run dry, in no
+// particular order): a unit that adds one needs no edit outside itself.
+struct SessionItem {
+    SessionItem* const next;
+    SessionItem() : next(head) { head = this; }
+    SessionItem(const SessionItem&) = delete;
+    SessionItem& operator=(const SessionItem&) = delete;
+    virtual void end() = 0;      // destroy what was made, forget what was remembered
+    static SessionItem* head;     // constant-initialised: valid during any translation unit's dynamic initialisation
+protected:
+    ~SessionItem() = default;
+};
+
+// N events, created together by the first ensure().
+template <int N>
+struct Events final : SessionItem {
+    hipEvent_t e[N] = {};
+    const unsigned flags;
+    bool made = false;
+    explicit Events(unsigned flags_ = hipEventDefault) : flags(flags_) {}
+    hipEvent_t operator[](int i) const { return e[i]; }
+    int ensure()
+    {
+        if (made) return RM_OK;
+        for (auto& x : e)
+            if (!x) HIP_TRY(hipEventCreateWithFlags(&x, flags));
+        made = true;
+        return RM_OK;
+    }
+    void end() override
+    {
+        for (auto& x : e)
+            if (x) { (void)hipEventDestroy(x); x = nullptr; }
+        made = false;
+    }
+};
+
+// A non-blocking stream of the library's own, created by the first ensure().
+struct SideStream final : SessionItem {
+    hipStream_t s = nullptr;
+    int ensure()
+    {
+        if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return RM_OK;
+    }
+    void end() override
+    {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+    }
+};
+
+// Host state of the session: the members of T start again from their initialisers, so a new member needs no line.
+template <class T>
+struct PerSession final : SessionItem, T {
+    void end() override { static_cast<T&>(*this) = T(); }
+};
+
 hipStream_t lib_stream();                            // the library's own stream (valid while an Entry's rc() is RM_OK)
+const hipDeviceProp_t& device_prop();                // ... and the device's properties
 extern WsBuf (&stage_in)[2], (&stage_out)[4];        // staging of the per-point / per-ray calls (Staged)
 
 // An entry point's way to the workspace and the device.  Constructing one takes the library's lock, refuses a library
@@ -76,6 +140,16 @@ public:
 private:
     std::unique_lock<std::mutex> lk_;
     int rc_;
+};
+
+// The lock alone, for the calls that touch the library's state without a device.
+class Lock {
+public:
+    Lock();
+    bool select_device() const;      // false: the library has no device (nothing selected)
+
+private:
+    std::lock_guard<std::mutex> lk_;
 };
 
 // The staging of a call that takes host arrays and returns host arrays: inputs and outputs are declared with the
@@ -144,10 +218,14 @@ int timed(const Entry&, RmTiming* t, hipStream_t s, const std::function<int()>& 
 inline int once_or_timed(const Entry& e, RmTiming* t, hipStream_t s, const std::function<int()>& once) { return t ? timed(e, t, s, once) : once(); }
 
 int check_slice(const RmFrameDesc* d, bool band_cyclic);
+int check_desc(const RmFrameDesc* d);               // every field of a frame descriptor (rm_frame.hip)
+void frame_stream_destroyed(hipStream_t s);          // rm_stream_destroy tells the frame engine, which remembers the latest frame's stream
 int check_scene(int id);
 int scene_data(int id, const void** data);
 // The sdf_eval launcher of scene `id` (check_scene has accepted it; under the lock).  Not its whole SceneLaunchers:
 // rm_kernels.h puts the libm tables of the kernels compiled after it into LDS, which rm_features.hip's do not fill.
+// The kernels of scene `id` (check_scene has accepted it; under the lock), for the units that include rm_kernels.h.
+const SceneLaunchers* launchers(int id);
 using SdfEval = hipError_t (*)(const double* xyz, size_t n, double* out, const void* scene_data, hipStream_t s);
 SdfEval sdf_eval_of(int id);
 inline bool is_program_id(int id) { return id >= RM_SCENE_PROGRAM_BASE; }

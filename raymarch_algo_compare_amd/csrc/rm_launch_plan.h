@@ -1,7 +1,9 @@
 // rm_launch_plan.h -- the launch policy of a frame: how many launches, which budgets, grids, team share, tile order and
-// knobs.  One pure function of the frame descriptor and a few device facts; no HIP call, no HIP include.  rm_capi.hip
-// performs the plan (buffers, caches, enqueues); tests/native/plan_check.cpp and tests/test_launch_plan.py pin its
-// decisions on the CPU.  Schedules never change results, so nothing else would notice a slip here.
+// knobs.  One pure function of the frame descriptor and a few device facts; no HIP call, no HIP include.  rm_frame.hip
+// performs the plan (buffers, caches, enqueues) and takes the smaller rules at the end of this file -- the parked-ray
+// queues' clear, the filler count of a team chain, the keys of the tile-order caches -- from here as well;
+// tests/native/plan_check.cpp and tests/test_launch_plan.py pin all of it on the CPU.  Schedules never change results,
+// so nothing else would notice a slip here.
 //
 // Scene ids (registry.py): 0 Sphere, 1 Grazing Plane, 2 Cube, 3 Thin Torus, 4 Cylinder, 5 Near Miss, 6 Hollow Cube,
 // 10 Mandelbulb, 12 Pillar Forest, 13 Thin Planes Stack, 14 Sphere Cloud, 15 Bumpy Sphere, 18 Box Lattice,
@@ -10,6 +12,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cstddef>
 #include <functional>
 
 #include "../../include/rm_hip.h"
@@ -17,13 +20,14 @@
 
 namespace rm {
 
-enum class OccKernel { render, pipeline };
+enum class OccKernel { render, pipeline, split_producers, split_teams };      // the last two: the split form's two kernels
 
 // What the plan needs to know of the device and of the scene's kernels.
 struct DeviceFacts {
     int cus = 0;                  // compute units
     bool has_teams = false;       // the scene has a team form (SceneLaunchers.has_teams)
     bool has_resume_team = false; // ... and a team resume kernel (SceneLaunchers.resume_team)
+    bool has_split = false;       // ... and the split form of the single launch (SceneLaunchers.pipeline_producers / _teams)
     int entry_bytes = 0;          // one parked-ray queue entry of the strategy (SceneLaunchers.entry_bytes)
     // workgroups per compute unit the kernel reaches (<= 0: unknown); asked only where the plan needs it
     std::function<int(OccKernel kernel, int tile_h, int interleave, int batch)> per_cu;
@@ -50,6 +54,7 @@ struct LaunchPlan {
     int early_trips = 0, early_handover = 0, suspend_after2 = 0;
     int q0_detach = 0, q0_first = 0, q0_refill_min = 0, q0_retry = 0, team_retry = 0, team_steal = 0, team_prio = 0, max_spins = 0;
     int pipeline_grid = 0;
+    int form = 0;                     // how the single launch is performed (single_launch_form): 1 fused, 2 split side by side, 3 split in sequence
     // one launch per pass: passes 2 and 3
     int resume_grid = 0, resume_refill_min = 0, pass_keep_busy = 0, team_pass_grid = 0;
     bool pass_team[2] = { false, false };     // the pass runs the team resume kernel
@@ -156,11 +161,45 @@ inline int default_tile_order(const RmFrameDesc& d, int nframes)
     }
 }
 
+// How the single launch of plan `p` is performed (RmFrameDesc.pipeline_form): 1 = the fused pipeline_kernel, 2 = producers
+// and teams as two kernels side by side, 3 = the two kernels one after the other on the caller's stream (tests).
+// The split form covers the default schedule -- detach mode, every team resident from the start -- where a producer never
+// waits for a team; any other knob set keeps the fused kernel.  Library's choice (0): RM_SPLIT_BY_DEFAULT, and only where
+// each of the two kernels reaches at least the workgroups per compute unit the plan's grid counts on (`fused`: what the
+// fused kernel reaches, which sized that grid), so that together they occupy no more than the fused grid does.
+// Measured (parent, fused default and split default alternating three times on one MI355X, DESIGN.md section 3 "Split single
+// launch"): bench.py 270.5-272.5 Mrays/s with the fused kernel, 278.0-278.7 split.
+#ifndef RM_SPLIT_BY_DEFAULT
+#define RM_SPLIT_BY_DEFAULT 1      // (-DRM_SPLIT_BY_DEFAULT=0: the other default, for a same-box A/B of two libraries)
+#endif
+inline int single_launch_form(const RmFrameDesc& d, const DeviceFacts& dev, LaunchPlan& p, int fused)
+{
+    if (d.pipeline_form == 1) return 1;
+    const bool covered = dev.has_split && p.team_wgs > 0 && p.suspend_after2 > 0 && p.q0_detach != 0 && p.early_exit_wgs == 0 &&
+                         p.late_team_first == p.pipeline_grid;
+    if (d.pipeline_form >= 2) {
+        if (!covered && !p.refuse)
+            p.refuse = d.pipeline_form == 2
+                ? "pipeline_form 2: the split form exists for single launches with teams in detach mode without late teams"
+                : "pipeline_form 3: the split form exists for single launches with teams in detach mode without late teams";
+        return covered ? d.pipeline_form : 1;
+    }
+    if (!RM_SPLIT_BY_DEFAULT || !covered || p.batch) return 1;
+    // Skipping-Spheres and Adaptive-Hybrid keep the fused kernel: same alternation at 1920x1080, fused / split 8.91 / 8.99-9.00 ms
+    // and 4.61 / 4.68-4.76 (few of their rays reach the teams; the other nine of the registry gain or stay within the spread)
+    if (d.strategy_id == 7 || d.strategy_id == 9) return 1;
+    if (fused <= 0) return 1;      // occupancy unknown
+    const int per_cu = grid_per_cu(fused);
+    return dev.per_cu(OccKernel::split_producers, p.tile_h, p.interleave, 0) >= per_cu &&
+           dev.per_cu(OccKernel::split_teams, p.tile_h, p.interleave, 0) >= per_cu ? 2 : 1;
+}
+
 // The single launch (rm_pipeline.h): producers + queue-0 consumers + teams side by side.  Fills the single-launch fields.
 inline void plan_single_launch(const RmFrameDesc& d, const DeviceFacts& dev, LaunchPlan& p)
 {
     const bool teams = dev.has_teams && p.park[1] > 0 && d.resume_mode != 1;
-    const int per_cu = grid_per_cu(dev.per_cu(OccKernel::pipeline, p.tile_h, p.interleave, p.batch ? 1 : 0));
+    const int fused = dev.per_cu(OccKernel::pipeline, p.tile_h, p.interleave, p.batch ? 1 : 0);
+    const int per_cu = grid_per_cu(fused);
     const long long resident = (long long)dev.cus * per_cu;
     const long long ntiles = (long long)p.tiles_x * p.tiles_y * p.nframes;
     const long long rays = p.rays;
@@ -243,6 +282,7 @@ inline void plan_single_launch(const RmFrameDesc& d, const DeviceFacts& dev, Lau
     p.team_steal = (d.team_steal == 0 || d.team_steal == 1) ? 1 : 0;
     p.team_prio = 3;          // 0 / 1 / 3 measured alike (10.0-10.4 ms): what slows a ray next to producers is not the issue slot
     p.max_spins = 50000;      // ~50 ms of polling: only reached when part of the grid is not resident
+    p.form = single_launch_form(d, dev, p, fused);
 }
 
 // One launch per pass: pass 1 (render) parks rays beyond park[0] trips, pass 2 restarts them all at once and parks those
@@ -329,6 +369,56 @@ inline LaunchPlan plan_launch(const RmFrameDesc& d, const DeviceFacts& dev, int 
     p.render_grid = (int)std::max<long long>(1, std::min<long long>(wgs, cap));
     if (p.park[0] > 0) plan_passes(d, dev, p);
     return p;
+}
+
+// ---- the smaller rules of a frame's host side ---------------------------------------------------------------------------------
+
+// Who wrote a parked-ray queue last.  A single-launch consumer takes an entry for published when the word at the
+// entry's `ready` offset equals the launch's generation tag; a frame with another entry stride (another strategy), or
+// one that follows a multi-pass frame (entries without tags), would put those offsets on stale payload words -- old
+// output indices, counts, halves of doubles -- that can equal a small tag.  The span a different writer may have
+// touched is therefore cleared before a single launch uses the queue.
+struct QueueKey {
+    int stride = 0;
+    int writer = 0;       // 1 = pass per launch, 2 = single launch, 3 = unknown (rm_debug_poison_queues)
+    size_t used = 0;      // bytes from the buffer's start that a writer may have touched since the last clear
+};
+struct QueueStep { size_t clear; QueueKey key; };     // bytes to zero from the buffer's start before the launch; the key to remember
+
+// The queue's step for a launch of `writer` with entries of `stride` bytes that needs `need` bytes of a buffer which
+// held cap_before bytes and, grown where that was too little, holds cap_after.
+inline QueueStep queue_step(QueueKey prev, int writer, int stride, size_t need, size_t cap_before, size_t cap_after)
+{
+    size_t clear = 0;
+    if (need > cap_before) {
+        // fresh memory: no word of it may look like a published entry of a later launch (QEntry.ready)
+        clear = need;
+        prev.used = 0;
+    } else if (writer == 2 && prev.used > 0 && (prev.writer != 2 || prev.stride != stride)) {
+        // another layout wrote here: stale payload words now sit at this launch's `ready` offsets
+        clear = std::min(prev.used, cap_after);
+        prev.used = 0;
+    }
+    return { clear, { stride, writer, std::max(prev.used, need) } };
+}
+
+// rm_march_rays_team: the teams of a few rays are all that runs, so filler workgroups (two per compute unit in all) keep
+// the chip at the speed a frame's teams run at (KEEP BUSY, rm_kernels.h).
+inline int team_fillers(int cus, long long nteams) { return (int)std::max<long long>(0, 2ll * cus - nteams); }
+
+// The frame shape whose per-tile costs the longest-first order (tile_order 1) may reuse ...
+inline void frame_key(const RmFrameDesc& d, int tile_h, long long* k /* 10 words */)
+{
+    k[0] = d.scene_id; k[1] = d.strategy_id; k[2] = d.width; k[3] = d.height; k[4] = d.row0; k[5] = d.rows;
+    k[6] = d.band_rows; k[7] = d.band_stride; k[8] = d.band_offset; k[9] = tile_h;
+}
+
+// ... and the one whose static permutation (tile_order 2 and 4) is kept: pure geometry, the same for every scene and strategy.
+inline void static_order_key(const RmFrameDesc& d, int tile_h, int nframes, int order, long long* k /* 12 words */)
+{
+    frame_key(d, tile_h, k);
+    k[0] = k[1] = 0;
+    k[10] = nframes; k[11] = order;
 }
 
 }  // namespace rm

@@ -4,7 +4,7 @@
 librm_hip.so is started with RM_RCCL_LIBRARY naming the loop-back stand-in (tests/native/rccl_loopback.cpp), and this
 one process plays every rank in turn: rm_comm_init(id, N, r) .. rm_comm_destroy() per rank, the stand-in keeping what
 was sent in between.  What is checked is the library's own decision of WHAT is sent, HOW MANY bytes, and WHERE it lands
-(rm_gather_frame, rm_gather_frame_root in csrc/rm_capi.hip): every gathered frame must equal the unsharded render bit
+(rm_gather_frame, rm_gather_frame_root in csrc/rm_gather.hip): every gathered frame must equal the unsharded render bit
 for bit, four poisoned rows behind the frame must stay poisoned, and the stand-in's call and byte counts must be the
 plan's.  A fresh process because the library caches the RCCL handle; no torch (its wheel maps a second HIP runtime).
 

@@ -1,4 +1,4 @@
-// A loop-back stand-in for the nine RCCL symbols librm_hip.so resolves (rm_capi.hip, rccl_load), so that the N > 1
+// A loop-back stand-in for the nine RCCL symbols librm_hip.so resolves (rm_gather.hip, rccl_load), so that the N > 1
 // paths of rm_gather_frame / rm_gather_frame_root run on ONE GPU: one process drives the ranks one after another, each
 // with its own rm_comm_init .. rm_comm_destroy.  Named to the library with RM_RCCL_LIBRARY.  Plain C++: host calls of
 // the HIP runtime only, no kernels.  tests/test_gpu_loopback_gather.py and tests/test_loopback_host.py build it.

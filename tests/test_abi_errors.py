@@ -1,5 +1,5 @@
 """The error contract of the C ABI as a table: an invalid or degenerate call per early return of the host layer
-(csrc/rm_capi.hip and the entry points below the kernels of csrc/rm_*.hip), the code it returns and -- where the wording is stable -- a piece of rm_last_error().  Which
+(csrc/rm_capi.hip, the march's host side csrc/rm_frame.hip, the gather csrc/rm_gather.hip and the entry points below the kernels of the other csrc/rm_*.hip), the code it returns and -- where the wording is stable -- a piece of rm_last_error().  Which
 check fires FIRST when several would is part of the contract (no device before a bad argument in rm_render, a bad
 scene before no device in rm_interval_*), so rows combine faults on purpose.
 

@@ -1,4 +1,4 @@
-"""The N > 1 paths of rm_gather_frame / rm_gather_frame_root (csrc/rm_capi.hip) on the one GPU there is: the library
+"""The N > 1 paths of rm_gather_frame / rm_gather_frame_root (csrc/rm_gather.hip) on the one GPU there is: the library
 loads the loop-back stand-in tests/native/rccl_loopback.cpp instead of RCCL (RM_RCCL_LIBRARY) and one child process,
 tests/loopback_gather_check.py, plays the ranks in turn.  Its docstring lists the cases and what each reaches: landing
 slots of every rank (N = 2, 3, 4, 8; both plans), the send / receive pairing with empty ranks, the padded short shard,

@@ -2,7 +2,13 @@
 A default frame, a single-launch frame that parks rays, a scene-program frame, explicit rays, the rays of the five sound
 tracers, two segment ranges, a capture and its SSIM scores, capture scores and view features against itself, and one
 set of intrinsic features give bit-identical arrays and statistics before and after the restart; a program registered
-before the shutdown is still registered after it (its device copy is made again)."""
+before the shutdown is still registered after it (its device copy is made again).  So do the frames that go through
+what the frame engine (csrc/rm_frame.hip) keeps from one frame to the next: two single-launch frames in a row ordered by
+tile costs (the second by the first one's), a frame with pass timing on (the same number of passes) and a traced
+single-launch frame (the same number of records), whose longest ray ran past the second budget, so that the team kernel
+and its side stream were used in both lives."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -44,6 +50,33 @@ def _round(hip, program):
         for k in ("depth", "iters", "hit", "t_raw", "final_sdf", "block_var", "evals"):
             out[f"{name}: {k}"] = r[k]
         out[f"{name}: stats"] = r["stats"]
+    maps = ("depth", "iters", "hit", "t_raw", "final_sdf", "block_var", "evals", "stats")
+    L = hip.load()
+    # the longest-first tile order: the first frame leaves its tile costs, the second is ordered by them
+    ordered = hip.make_desc(10, 4, _cam(10), W, H, full=True, pipeline=2, suspend_after=(6, 40), tile_order_mode=1)
+    for turn in ("first", "second"):
+        r = hip.render(ordered, **want)
+        out.update({f"ordered by costs, {turn}: {k}": r[k] for k in maps})
+    # pass timing: a frame of three launches, after two single launches in the same queues
+    hip.check(L.rm_set_pass_timing(1))
+    try:
+        r = hip.render(hip.make_desc(10, 4, _cam(10), W, H, full=True, pipeline=1, suspend_after=(6, 40)), **want)
+        n, ms = ctypes.c_int32(0), (ctypes.c_float * 4)()
+        hip.check(L.rm_get_pass_ms(None, ctypes.byref(n), ms))
+    finally:
+        hip.check(L.rm_set_pass_timing(0))
+    out.update({f"pass timing: {k}": r[k] for k in maps})
+    out["pass timing: passes"] = np.array([n.value])
+    # the development trace: one record per ray a team finished (no early hand-over: the rays beyond the second budget)
+    hip.check(L.rm_debug_set_trace(1))
+    try:
+        r = hip.render(hip.make_desc(10, 4, _cam(10), W, H, full=True, pipeline=2, suspend_after=(6, 40), early_handover=-1), **want)
+        nrec = ctypes.c_int64(0)
+        hip.check(L.rm_debug_get_trace(None, 0, ctypes.byref(nrec), None, None, 0, None))
+    finally:
+        hip.check(L.rm_debug_set_trace(0))
+    out.update({f"traced: {k}": r[k] for k in maps})
+    out["traced: records"] = np.array([nrec.value])
     o, d = _rays()
     for k, v in zip(("hit", "t", "iters", "final_sdf"), hip.march_rays(10, 0, o, d)):
         out[f"march_rays: {k}"] = v
@@ -91,6 +124,9 @@ def test_the_library_restarts_clean(hip):
     try:
         first = _round(hip, program)
         assert first["single launch: stats"]["total_rays"] == W * H and first["default: stats"]["hit_count"] > 0
+        # some ray ran past the second budget: teams finished it, on the stream of the library's own
+        assert first["traced: stats"]["iter_max"] > 40 and first["traced: records"][0] > 0
+        assert first["pass timing: passes"][0] == 3
         device = _native._device
         L.rm_shutdown()
         _native._device = None                          # what _native.init does on a device switch

@@ -28,14 +28,16 @@ def lib():
 
 
 def plan(scene, strategy, width=1920, height=1080, *, batch=0, configs=None, occ=2, occ_batch=None, occ_pipeline=None,
-         has_teams=None, has_resume_team=None, entry_bytes=224, max_iterations=512, **desc):
-    """The plan of one descriptor as a dict (refuse: the plan refuses it)."""
+         has_teams=None, has_resume_team=None, entry_bytes=224, max_iterations=512, has_split=None, occ_producers=None,
+         occ_teams=None, **desc):
+    """The plan of one descriptor as a dict (refuse: the plan refuses it).  The split form's two kernels exist where teams
+    do and reach the fused kernel's occupancy unless a case says otherwise."""
     L = lib()
     d = _native.make_desc(scene, strategy, [0.0] * 14, width, height, max_iterations=max_iterations, **desc)
     teams = scene in (MANDELBULB, SPHERE_CLOUD, BUMPY) if has_teams is None else has_teams
     names = ["refuse"] + [n for n in L.rmplan_fields().decode().split(",") if n]
     out = (ctypes.c_int64 * len(names))()
-    asked = (ctypes.c_int * 2)()
+    asked = (ctypes.c_int * 4)()
     cfg = None
     if configs is not None:
         cfg = (_native.RmMarchConfig * len(configs))()
@@ -43,11 +45,14 @@ def plan(scene, strategy, width=1920, height=1080, *, batch=0, configs=None, occ
             c.max_iterations = it
     L.rmplan(ctypes.byref(d), batch, cfg, CUS, occ, occ if occ_batch is None else occ_batch,
              occ if occ_pipeline is None else occ_pipeline, int(teams), int(teams if has_resume_team is None else has_resume_team),
-             entry_bytes, out, asked)
+             entry_bytes, out, asked, int(teams if has_split is None else has_split),
+             (occ if occ_pipeline is None else occ_pipeline) if occ_producers is None else occ_producers,
+             (occ if occ_pipeline is None else occ_pipeline) if occ_teams is None else occ_teams)
     p = dict(zip(names, out))
     p["park"] = (p.pop("park[0]"), p.pop("park[1]"))
     p["pass_team"] = (p.pop("pass_team[0]"), p.pop("pass_team[1]"))
-    p["asked"] = tuple(asked)
+    p["asked"] = tuple(asked[:2])
+    p["asked_split"] = tuple(asked[2:])      # the split form's producers / teams
     return p
 
 
@@ -293,3 +298,141 @@ def test_one_row_tiles_exist_for_the_team_single_launch_only():
     # the single launch of a scene without teams keeps 64x4 tiles
     p = plan(MANDELBULB, STANDARD, tile_order_mode=1, has_teams=False)
     assert p["single"] == 1 and p["tile_h"] == 4 and p["team_wgs"] == 0
+
+
+# ---- how the single launch is performed (single_launch_form) --------------------------------------------------------------
+
+def test_default_single_launch_is_split():
+    # "bench.py 270.5-272.5 Mrays/s with the fused kernel, 278.0-278.7 split"
+    p = plan(MANDELBULB, STANDARD)
+    assert p["form"] == 2 and p["refuse"] == 0
+    assert p["asked"] == (0, 1) and p["asked_split"] == (1, 1)      # the fused occupancy is the one that sized the grid
+
+
+@pytest.mark.parametrize("strategy", [SKIPPING, HYBRID])
+def test_strategies_that_keep_the_fused_kernel(strategy):
+    # "Skipping-Spheres and Adaptive-Hybrid keep the fused kernel"
+    p = plan(MANDELBULB, strategy)
+    assert p["single"] == 1 and p["form"] == 1 and p["asked_split"] == (0, 0)
+
+
+def test_batches_keep_the_fused_kernel():
+    p = plan(MANDELBULB, STANDARD, 384, 384, batch=4)
+    assert p["single"] == 1 and p["form"] == 1 and p["asked_split"] == (0, 0)
+
+
+@pytest.mark.parametrize("occ_pipeline, split, form", [(2, (2, 2), 2), (2, (1, 2), 1), (2, (2, 1), 1), (3, (3, 2), 1), (3, (2, 3), 1),
+                                                       (5, (3, 3), 2), (2, (0, 0), 1), (0, (2, 2), 1)])
+def test_split_needs_the_fused_grids_occupancy(occ_pipeline, split, form):
+    # "only where each of the two kernels reaches at least the workgroups per compute unit the plan's grid counts on"
+    # (grid_per_cu: three at most); an unknown occupancy keeps the fused kernel
+    p = plan(MANDELBULB, STANDARD, occ_pipeline=occ_pipeline, occ_producers=split[0], occ_teams=split[1])
+    assert p["form"] == form and p["refuse"] == 0
+
+
+def test_no_split_where_the_schedule_is_not_covered():
+    # "detach mode, every team resident from the start"; a scene without the two kernels
+    assert plan(MANDELBULB, STANDARD, queue_first=2)["form"] == 1
+    assert plan(MANDELBULB, STANDARD, late_teams=64)["form"] == 1
+    assert plan(MANDELBULB, STANDARD, resume_mode=1)["form"] == 1            # no teams
+    assert plan(MANDELBULB, STANDARD, has_split=False)["form"] == 1
+    for kw in (dict(queue_first=2), dict(late_teams=64), dict(has_split=False)):
+        assert plan(MANDELBULB, STANDARD, **kw)["asked_split"] == (0, 0)
+
+
+def test_explicit_forms():
+    for form in (1, 2, 3):
+        p = plan(MANDELBULB, STANDARD, pipeline_form=form, occ_producers=1, occ_teams=1)      # no occupancy test
+        assert p["form"] == form and p["refuse"] == 0 and p["asked_split"] == (0, 0)
+    # an explicit form holds for the strategies and the batches the library would keep fused
+    assert plan(MANDELBULB, SKIPPING, pipeline_form=2)["form"] == 2
+    assert plan(MANDELBULB, STANDARD, 384, 384, batch=4, pipeline_form=2)["form"] == 2
+    # "the split form exists for single launches with teams in detach mode without late teams"
+    for form in (2, 3):
+        assert plan(MANDELBULB, STANDARD, pipeline_form=form, late_teams=64)["refuse"] == 1
+        assert plan(MANDELBULB, STANDARD, pipeline_form=form, queue_first=2)["refuse"] == 1
+        assert plan(MANDELBULB, STANDARD, pipeline_form=form, has_split=False)["refuse"] == 1
+    assert plan(MANDELBULB, STANDARD, pipeline_form=1, late_teams=64)["refuse"] == 0
+
+
+def test_no_occupancy_is_asked_of_the_split_kernels_outside_a_single_launch():
+    for p in (plan(0, STANDARD), plan(0, STANDARD, grid_waves=100), plan(MANDELBULB, STANDARD, pipeline=1),
+              plan(MANDELBULB, STANDARD, 7680, 4320), plan(SPHERE_CLOUD, STANDARD), plan(0, STANDARD, pipeline_form=2),
+              plan(MANDELBULB, STANDARD, 384, 384, batch=4, pipeline=1)):
+        assert p["single"] == 0 and p["form"] == 0 and p["refuse"] == 0
+        assert p["asked"][1] == 0 and p["asked_split"] == (0, 0)
+
+
+# ---- the parked-ray queues' clear (queue_step) ----------------------------------------------------------------------------
+
+def queue_step(prev, writer, stride, need, cap_before, cap_after=None):
+    """(bytes to clear, (stride, writer, used) to remember) for the previous key (stride, writer, used)"""
+    out = (ctypes.c_uint64 * 4)()
+    u64 = ctypes.c_uint64
+    lib().rmplan_queue(prev[0], prev[1], u64(prev[2]), writer, stride, u64(need), u64(cap_before),
+                       u64(cap_before if cap_after is None else cap_after), out)
+    return out[0], (out[1], out[2], out[3])
+
+
+@pytest.mark.parametrize("writer", [1, 2])
+def test_a_fresh_or_grown_queue_is_cleared_as_far_as_needed(writer):
+    # "fresh memory: no word of it may look like a published entry of a later launch"
+    assert queue_step((0, 0, 0), writer, 224, 1000, 0, 1000) == (1000, (224, writer, 1000))
+    # grown: what the old buffer held is gone with it
+    assert queue_step((224, 2, 4000), writer, 224, 5000, 4000, 5000) == (5000, (224, writer, 5000))
+    assert queue_step((160, 1, 4000), writer, 224, 5000, 4000, 8192) == (5000, (224, writer, 5000))
+
+
+def test_the_same_single_launch_layout_clears_nothing():
+    assert queue_step((224, 2, 3000), 2, 224, 2000, 4000) == (0, (224, 2, 3000))
+    assert queue_step((224, 2, 3000), 2, 224, 4000, 4000) == (0, (224, 2, 4000))
+
+
+@pytest.mark.parametrize("prev", [(224, 1, 3000), (224, 3, 3000), (160, 2, 3000), (160, 1, 3000)])
+def test_a_single_launch_after_another_writer_clears_what_that_one_used(prev):
+    # "another layout wrote here: stale payload words now sit at this launch's `ready` offsets"
+    assert queue_step(prev, 2, 224, 2000, 4000) == (3000, (224, 2, 2000))
+    assert queue_step(prev, 2, 224, 3500, 4000) == (3000, (224, 2, 3500))
+    assert queue_step((prev[0], prev[1], 9000), 2, 224, 2000, 4000) == (4000, (224, 2, 2000))     # min(used, cap)
+    assert queue_step((prev[0], prev[1], 0), 2, 224, 2000, 4000) == (0, (224, 2, 2000))           # nothing was touched
+
+
+@pytest.mark.parametrize("prev", [(224, 2, 3000), (160, 2, 3000), (224, 3, 3000), (224, 1, 3000), (0, 0, 0)])
+def test_a_pass_per_launch_frame_never_clears_but_records_itself(prev):
+    assert queue_step(prev, 1, 192, 2000, 4000) == (0, (192, 1, max(prev[2], 2000)))
+
+
+def test_used_is_the_running_maximum():
+    key = (0, 0, 0)
+    seen = []
+    for writer, stride, need in [(2, 224, 1000), (2, 224, 3000), (2, 224, 500), (1, 224, 3500), (1, 160, 100)]:
+        _, key = queue_step(key, writer, stride, need, 4000)
+        seen.append(key[2])
+    assert seen == [1000, 3000, 3000, 3500, 3500]
+    # the unknown writer of rm_debug_poison_queues touches the whole buffer; the next single launch clears all of it
+    clear, key = queue_step(key, 3, key[0], 4000, 4000)
+    assert clear == 0 and key == (160, 3, 4000)
+    assert queue_step(key, 2, 160, 100, 4000) == (4000, (160, 2, 100))
+
+
+# ---- filler workgroups of rm_march_rays_team, tile-order cache keys -------------------------------------------------------
+
+def test_team_fillers():
+    # "filler workgroups (two per compute unit in all)"
+    L = lib()
+    L.rmplan_fillers.argtypes = [ctypes.c_int, ctypes.c_int64]
+    assert L.rmplan_fillers(CUS, 1) == 2 * CUS - 1
+    assert L.rmplan_fillers(CUS, 2 * CUS) == 0
+    assert L.rmplan_fillers(CUS, 2 * CUS + 1) == 0              # never negative
+    assert L.rmplan_fillers(CUS, 1 << 40) == 0
+    assert L.rmplan_fillers(CUS, 0) == 2 * CUS
+
+
+def test_tile_order_cache_keys():
+    d = _native.make_desc(MANDELBULB, ENHANCED, [0.0] * 14, 1920, 1080)
+    d.row0, d.rows, d.band_rows, d.band_stride, d.band_offset = 8, 540, 4, 2, 1
+    dyn, stat = (ctypes.c_int64 * 10)(), (ctypes.c_int64 * 12)()
+    lib().rmplan_keys(ctypes.byref(d), 1, 3, 4, dyn, stat)
+    assert list(dyn) == [MANDELBULB, ENHANCED, 1920, 1080, 8, 540, 4, 2, 1, 1]
+    # "pure geometry: the same permutation for every scene and strategy", per frame count and order
+    assert list(stat) == [0, 0, 1920, 1080, 8, 540, 4, 2, 1, 1, 3, 4]

@@ -1,4 +1,4 @@
-"""RM_RCCL_LIBRARY (csrc/rm_capi.hip, rccl_load) and the loop-back stand-in tests/native/rccl_loopback.cpp, without a
+"""RM_RCCL_LIBRARY (csrc/rm_gather.hip, rccl_load) and the loop-back stand-in tests/native/rccl_loopback.cpp, without a
 device: the stand-in compiles with g++ and exports what the library resolves; the variable names the ONE library that
 is tried (a missing file or a missing symbol is RM_E_RCCL with the path in the message, never a quiet fall-back to
 librccl.so.1); unset, the library behaves as before.  rm_comm_unique_id needs no device, and with the stand-in (or a

@@ -2,7 +2,7 @@
 """Compare the final gfx950 assembly of two builds kernel by kernel (CPU only).
 
     KEEP_ASM=1 make -C raymarch_algo_compare_amd/csrc -j16      # in both trees: keeps _build/<object>.s
-    python tools/kernel_isa_diff.py <old>/_build <new>/_build
+    python tools/kernel_isa_diff.py [--by-name] <old>/_build <new>/_build
 
 A refactor of the device headers must leave every kernel as it was.  For every <object>.s that either directory
 holds, the kernels (symbols with an .amdhsa_kernel block) are cut out: the text from the kernel's label to its
@@ -12,6 +12,10 @@ normalised is the function number in the compiler's local labels (.LBB<n>_<m>, a
 and .Lfunc_end<n>), and with it the padding between such a label and the comment the compiler aligns behind it.  Only
 kernels are compared: a __device__ function that is not inlined would have to be added (today every function is a kernel).  Prints every kernel
 that exists on one side only or differs in its instructions or its descriptor; exit status 1 if there is any.
+
+--by-name: for a change that moves kernels between translation units.  A kernel that its object holds on one side only is
+looked up by name in every object of the other side (an object that exists on one side only is then no finding by
+itself); it must be there exactly once.
 """
 import pathlib
 import re
@@ -45,29 +49,40 @@ def kernels(path):
 
 
 def main(argv):
+    by_name = "--by-name" in argv
+    argv = [x for x in argv if x != "--by-name"]
     if len(argv) != 3:
         sys.exit(__doc__)
     old, new = pathlib.Path(argv[1]), pathlib.Path(argv[2])
     files = sorted({p.name for d in (old, new) for p in d.glob("*.s") if not p.name.endswith(".raw.s")})
     if not files:
         sys.exit(f"no assembly in {old} or {new}: build with KEEP_ASM=1")
-    bad = total = 0
+    side = {d: {f: kernels(d / f) for f in files if (d / f).exists()} for d in (old, new)}
+    bad = total = moved = 0
     for f in files:
-        if not ((old / f).exists() and (new / f).exists()):
-            print(f"{f}: only in {old if (old / f).exists() else new}")
+        if not by_name and not (f in side[old] and f in side[new]):
+            print(f"{f}: only in {old if f in side[old] else new}")
             bad += 1
             continue
-        a, b = kernels(old / f), kernels(new / f)
+        a, b = side[old].get(f, {}), side[new].get(f, {})
         total += len(a)
         for k in sorted(set(a) | set(b)):
-            if k not in a or k not in b:
-                what = f"only in {old if k in a else new}"
+            x, y, where = a.get(k), b.get(k), f
+            if by_name and y is None:           # left this object: it must be in exactly one other
+                homes = [g for g in side[new] if k in side[new][g]]
+                if len(homes) == 1:
+                    y, where = side[new][homes[0]][k], f"{f} -> {homes[0]}"
+                    moved += 1
+            elif by_name and x is None and any(k in ks for ks in side[old].values()):
+                continue                        # came from another object: compared from there
+            if x is None or y is None:
+                what = f"only in {old if x is not None else new}"
             else:
-                what = ", ".join(w for w, x, y in (("instructions", a[k][0], b[k][0]), ("descriptor", a[k][1], b[k][1])) if x != y)
+                what = ", ".join(w for w, p, q in (("instructions", x[0], y[0]), ("descriptor", x[1], y[1])) if p != q)
             if what:
-                print(f"{f}: {k}: {what}")
+                print(f"{where}: {k}: {what}")
                 bad += 1
-    print(f"{len(files)} objects, {total} kernels, {bad} differ")
+    print(f"{len(files)} objects, {total} kernels" + (f", {moved} in another object" if by_name else "") + f", {bad} differ")
     return 1 if bad else 0
 
 
