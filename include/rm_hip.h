@@ -363,6 +363,81 @@ int rm_scene_program_create(const RmSceneOp* ops, int32_t nops, double lipschitz
 /* Frees the program and its device copy; its id is never handed out again.  RM_E_BAD_SCENE for an unknown id. */
 int rm_scene_program_destroy(int32_t scene_id);
 
+/* ---- Strategy programs: user-defined marching rules run by an interpreter in the render kernels -------------------------
+ * A strategy program is a jump-free register program that runs once per SDF evaluation of a ray (DESIGN.md section 3,
+ * "Strategy programs").  Its id is passed wherever a strategy id is (rm_render*, rm_render_outputs, rm_render_device,
+ * rm_render_batch*, rm_capture, rm_march_rays); rm_march_rays_team refuses it (RM_E_BAD_STRATEGY).  A frame with a program
+ * id is always ONE plain render pass: no parked rays, no single launch, no teams, whole evaluations, the library's
+ * static tile order (the descriptor's scheduling fields are ignored).
+ *
+ * Registers, all binary64, per ray:
+ *   s0 .. s15   state: persist between evaluations, all zero when a ray starts.  The machine reads seven after a block:
+ *                 s0  t          the ray parameter reported when the ray finishes
+ *                 s1  te         where the SDF is evaluated next
+ *                 s2  phase      which block consumes that value (0 .. 7; anything else names no block)
+ *                 s3  status     0 go on; non-zero finished; exactly 2.0: finished and, when the frame runs with `full`,
+ *                                evaluate once more at s0 and report that value as final_sdf (skipped without `full`)
+ *                 s4  hit        non-zero = hit
+ *                 s5  final_sdf
+ *                 s6  iterations converted to int32: NaN -> 0, clamped to [0, INT32_MAX], truncated
+ *               s7 .. s15 belong to the program.
+ *   t0 .. t15   temporaries: live within one block execution only; a block must write one before it reads it.
+ * Operand codes (RmStrategyOp.dst / a / b / c):
+ *   0 .. 15 = s0 .. s15, 16 .. 31 = t0 .. t15 (the only valid destinations), then read-only:
+ *   RM_STRATEGY_IN_D (the value just evaluated; not in the init block), RM_STRATEGY_IN_TE (where it was evaluated; not in
+ *   the init block), RM_STRATEGY_IN_HIT_THRESHOLD, _MAX_DISTANCE, _MAX_ITERATIONS (as a double), _LIPSCHITZ (the frame's
+ *   RmMarchConfig; RmStrategyParams is never read), and RM_STRATEGY_LITERAL = the op's own `k` (finite; a program may
+ *   hold RM_STRATEGY_PROGRAM_MAX_CONSTANTS distinct literals, compared by their bits).
+ * Ops (dst <- ...; unused operands must be 0; comparisons and logic yield 1.0 / 0.0, "true" is "!= 0"):
+ *   MOV a | ADD SUB MUL DIV a b (one IEEE operation each, never fused) | NEG ABS SQRT a | PYMAX PYMIN a b (Python's
+ *   max(a, b) / min(a, b): a unless b compares strictly greater / less) | LT LE GT GE EQ NE a b | AND OR a b | NOT a |
+ *   SELECT a b c (b where a != 0, else c).  There are no jumps: a conditional is a select, and a division whose result
+ *   is not selected is harmless (IEEE: inf or NaN, no trap).
+ * Blocks: RM_STOP_BLOCK with a = RM_STRATEGY_BLOCK_INIT (-1) or a phase 0 .. 7 opens a block; the ops up to the next
+ * marker are its body.  The array starts with a marker, the init block is required and each block may appear once.  The
+ * init block runs when a ray starts (it may finish the ray at once); a step runs the block of the ray's phase.
+ * Evaluation budget (a safety condition): a ray is force-finished at its (8 * max(max_iterations, 0) + 64)-th evaluation
+ * (the count clamped to INT32_MAX) if the program has not finished it by then -- hit 0, t = s0, final_sdf = the value of
+ * that evaluation, iterations from s6, no further evaluation.  A program that sets a non-zero status in the block of that
+ * very evaluation has finished the ray: its hit, t, final_sdf (s5) and iterations stand, and a status of 2 gets no tail
+ * evaluation there.  The compiled strategies stay far below the budget (at most 2 * max_iterations + 40).
+ * Ids start at RM_STRATEGY_PROGRAM_BASE, increase monotonically and are never reused within a process; ids in
+ * [RM_NUM_STRATEGY_KERNELS, RM_STRATEGY_PROGRAM_BASE) and destroyed or never-created program ids are RM_E_BAD_STRATEGY.
+ * rm_num_strategies() stays 11. */
+#define RM_STRATEGY_PROGRAM_BASE 1024
+#define RM_STRATEGY_PROGRAM_MAX_OPS 256        /* instructions of all blocks together (markers not counted) */
+#define RM_STRATEGY_PROGRAM_MAX_CONSTANTS 64
+#define RM_STRATEGY_PROGRAM_MAX_STATE 16
+#define RM_STRATEGY_PROGRAM_MAX_TEMPS 16
+#define RM_STRATEGY_PROGRAM_MAX_PHASES 8
+enum {
+    RM_STOP_MOV = 0, RM_STOP_ADD = 1, RM_STOP_SUB = 2, RM_STOP_MUL = 3, RM_STOP_DIV = 4, RM_STOP_NEG = 5, RM_STOP_ABS = 6,
+    RM_STOP_SQRT = 7, RM_STOP_PYMAX = 8, RM_STOP_PYMIN = 9, RM_STOP_LT = 10, RM_STOP_LE = 11, RM_STOP_GT = 12,
+    RM_STOP_GE = 13, RM_STOP_EQ = 14, RM_STOP_NE = 15, RM_STOP_AND = 16, RM_STOP_OR = 17, RM_STOP_NOT = 18,
+    RM_STOP_SELECT = 19,
+    RM_STOP_COUNT = 20,
+    RM_STOP_BLOCK = 32
+};
+enum {
+    RM_STRATEGY_IN_D = 32, RM_STRATEGY_IN_TE = 33, RM_STRATEGY_IN_HIT_THRESHOLD = 34, RM_STRATEGY_IN_MAX_DISTANCE = 35,
+    RM_STRATEGY_IN_MAX_ITERATIONS = 36, RM_STRATEGY_IN_LIPSCHITZ = 37,
+    RM_STRATEGY_LITERAL = 63,
+    RM_STRATEGY_BLOCK_INIT = -1
+};
+typedef struct RmStrategyOp {
+    int32_t op;          /* RM_STOP_* */
+    int32_t dst;         /* operand code 0 .. 31 (0 for RM_STOP_BLOCK) */
+    int32_t a, b, c;     /* operand codes; RM_STOP_BLOCK: a = RM_STRATEGY_BLOCK_INIT or the phase */
+    int32_t reserved;    /* 0 */
+    double k;            /* the value RM_STRATEGY_LITERAL operands of this op read; 0 when none does */
+} RmStrategyOp;
+/* Validates the program on the host (RM_E_BAD_ARG with the reason in rm_last_error: unknown op, operand out of range, a
+ * temporary read before its block wrote it, no init block, a phase above 7, a duplicate block, a non-finite literal, too
+ * many instructions or literals) and registers it; needs no device. */
+int rm_strategy_program_create(const RmStrategyOp* ops, int32_t nops, int32_t* strategy_id);
+/* Frees the program and its device copy; its id is never handed out again.  RM_E_BAD_STRATEGY for an unknown id. */
+int rm_strategy_program_destroy(int32_t strategy_id);
+
 /* ---- Interval first-hit oracle (gpu/interval_oracle.py, gpu/interval.py) ----------------------------------------------
  * A sound first hit by interval root isolation: each step evaluates an interval extension of the scene's SDF over the
  * box of the ray segment [t, t + h]; lo > 0 proves the segment empty (t += h, h = min(h * growth, h_max); a miss once

@@ -41,6 +41,7 @@ EXPORTS = [
     "rm_exact_supported", "rm_exact_march_rays", "rm_exact_render",
     "rm_ssim_scores", "rm_capture", "rm_shade_frames", "rm_score_captures",
     "rm_intrinsic_features", "rm_view_features",
+    "rm_strategy_program_create", "rm_strategy_program_destroy",
 ]
 RM_E_BAD_SCENE, RM_E_NO_DEVICE, RM_E_BAD_ARG = -1, -4, -6
 RM_INTERVAL_MAX_STEPS = 200000   # RmIntervalConfig.max_steps ceiling
@@ -48,6 +49,8 @@ RM_SEGMENT_MAX_STEPS = 40960     # RmSegmentConfig.budget ceiling
 RM_CERTIFY_MISS, RM_CERTIFY_HIT, RM_CERTIFY_OPEN = 0, 1, 2   # the `status` of the rm_certify_* calls
 RM_RANGE_AFFINE, RM_RANGE_MEET = 1, 2   # the `mode` of the rm_affine_* calls
 RM_SCENE_PROGRAM_BASE = 1024
+RM_STRATEGY_PROGRAM_BASE = 1024
+RM_E_BAD_STRATEGY = -2
 # RmMathFn (include/rm_hip.h): the device math routines rm_debug_math_eval evaluates
 MATH_FNS = {"POW": 0, "POW2": 1, "POW_HALF_DENSE": 2, "POW_HALF_SPARSE": 3, "POW_HALF_GUARD": 4, "SQRT": 5, "SIN": 6,
             "COS": 7, "SINCOS": 8, "SINCOS_U": 9, "ACOS": 10, "ACOS_U": 11, "ATAN2": 12, "ATAN2_U": 13, "LOG": 14}
@@ -155,6 +158,12 @@ class RmTiming(ctypes.Structure):
 class RmSceneOp(ctypes.Structure):
     """One instruction of a scene program (include/rm_hip.h; built by scene_program.py)."""
     _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("f", ctypes.c_double * 8)]
+
+
+class RmStrategyOp(ctypes.Structure):
+    """One instruction or block marker of a strategy program (include/rm_hip.h; built by strategy_program.py)."""
+    _fields_ = [("op", ctypes.c_int32), ("dst", ctypes.c_int32), ("a", ctypes.c_int32), ("b", ctypes.c_int32),
+                ("c", ctypes.c_int32), ("reserved", ctypes.c_int32), ("k", ctypes.c_double)]
 
 
 class RmIntervalConfig(ctypes.Structure):
@@ -267,6 +276,8 @@ def load() -> ctypes.CDLL:
         L.rm_scene_program_create.argtypes = [ctypes.POINTER(RmSceneOp), ctypes.c_int32, ctypes.c_double,
                                               ctypes.POINTER(ctypes.c_int32)]
         L.rm_scene_program_destroy.argtypes = [ctypes.c_int32]
+        L.rm_strategy_program_create.argtypes = [ctypes.POINTER(RmStrategyOp), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
+        L.rm_strategy_program_destroy.argtypes = [ctypes.c_int32]
         L.rm_march_rays.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(RmMarchConfig), dp, dp,
                                     ctypes.c_size_t, vp, dp, vp, dp]
         L.rm_march_rays_team.argtypes = L.rm_march_rays.argtypes
@@ -549,6 +560,18 @@ def scene_program_create(ops, nops: int, lipschitz: float = 1.0) -> int:
 
 def scene_program_destroy(scene_id: int) -> None:
     check(load().rm_scene_program_destroy(int(scene_id)))
+
+
+def strategy_program_create(ops, nops: int) -> int:
+    """rm_strategy_program_create: validate and register a step program (RmStrategyOp array); its strategy id.  Needs no GPU."""
+    L = load()
+    sid = ctypes.c_int32(-1)
+    check(L.rm_strategy_program_create(ops, int(nops), ctypes.byref(sid)))
+    return int(sid.value)
+
+
+def strategy_program_destroy(strategy_id: int) -> None:
+    check(load().rm_strategy_program_destroy(int(strategy_id)))
 
 
 def sdf_eval(scene_id: int, pts) -> np.ndarray:

@@ -10,7 +10,7 @@ llvm="${ROCM_LLVM:-/opt/rocm/lib/llvm/bin}"
 hipcc="${HIPCC:-hipcc}"
 base="${out%.o}"
 "$hipcc" "$@" -Wno-unused-command-line-argument --cuda-device-only -S "$src" -o "$base.raw.s"
-python3 "$here/rm_peephole.py" "$base.raw.s" "$base.s"
+python3 "$here/rm_peephole.py" ${RM_PEEPHOLE_FLAGS:-} "$base.raw.s" "$base.s"      # RM_PEEPHOLE_FLAGS: rm_peephole.py's options
 "$llvm/clang" -x assembler -target amdgcn-amd-amdhsa -mcpu=gfx950 -c "$base.s" -o "$base.dev.o"
 "$llvm/lld" -flavor gnu -m elf64_amdgpu --no-undefined -shared -o "$base.hsaco" "$base.dev.o"
 "$llvm/clang-offload-bundler" -type=o -bundle-align=4096 -targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950 \

@@ -18,13 +18,115 @@
 #include "rm_launch_plan.h"
 #include "rm_pipeline.h"
 #include "rm_scene_program.h"
+#include "rm_strategy_program.h"
 #include "rm_capi_internal.h"
+
+#include <map>
+#include <memory>
+#include <mutex>
 
 static_assert(RM_HIST_BINS == rm::kHistBins, "histogram size mismatch between ABI and kernels");
 
 using namespace rm::capi;
 
+// The strategy-program interpreter's kernels, one table per scene object (rm_strategy_tu.hip).
+namespace rm {
+#if defined(RM_DEV_STRATEGIES)
+#define RM_SP_DECL(name) const StrategyProgramLaunchers* name() __attribute__((weak));
+#else
+#define RM_SP_DECL(name) const StrategyProgramLaunchers* name();
+#endif
+#define RM_X(id, S) RM_SP_DECL(strategy_launchers_##id)
+RM_SCENE_LIST(RM_X)
+#undef RM_X
+RM_SP_DECL(strategy_launchers_program)
+RM_SP_DECL(strategy_launchers_program_ext)
+#undef RM_SP_DECL
+}  // namespace rm
+
 namespace {
+
+// ---- strategy programs (rm_strategy_program.h) --------------------------------------------------------------------------
+// A registered program: its validated image on the host, and the device copy the first launch that runs it makes (under
+// the library's lock; freed by rm_strategy_program_destroy and at the end of the session).  Nothing else is kept per
+// program id: a program frame plans without the caches that are keyed by strategy (rm_launch_plan.h).
+struct StrategyProgram {
+    std::unique_ptr<rm::StrategyImage> img;
+    void* dev = nullptr;
+};
+std::mutex g_sp_mu;                                   // guards the three below; taken after the library's lock where both are held
+std::map<int32_t, StrategyProgram> g_strategy_programs;
+int32_t g_next_strategy_program = RM_STRATEGY_PROGRAM_BASE;      // ids are never reused
+struct StrategyProgramCopies final : SessionItem {
+    void end() override      // programs stay registered; their device copies are made again after the next rm_init
+    {
+        std::lock_guard<std::mutex> lk(g_sp_mu);
+        for (auto& kv : g_strategy_programs)
+            if (kv.second.dev) { (void)hipFree(kv.second.dev); kv.second.dev = nullptr; }
+    }
+} g_strategy_program_copies;
+
+int no_such_strategy_program(int id)
+{
+    return fail(RM_E_BAD_STRATEGY, "strategy program %d does not exist (never created, or destroyed)", id);
+}
+
+// A compiled strategy kernel, or a live strategy program.
+int check_strategy(int id)
+{
+    if (rm::is_strategy_program(id)) {
+        std::lock_guard<std::mutex> lk(g_sp_mu);
+        return g_strategy_programs.count(id) ? RM_OK : no_such_strategy_program(id);
+    }
+    if (id < 0 || id >= RM_NUM_STRATEGY_KERNELS) return fail(RM_E_BAD_STRATEGY, "strategy_id %d out of range", id);
+    return RM_OK;
+}
+
+// The launch data of strategy `id` (KernelArgs.strategy_data; under the library's lock with the device selected): a
+// program's device image, copied by its first launch; nullptr for a compiled strategy.
+int strategy_data(int id, const void** data)
+{
+    *data = nullptr;
+    if (!rm::is_strategy_program(id)) return RM_OK;
+    std::lock_guard<std::mutex> lk(g_sp_mu);
+    auto it = g_strategy_programs.find(id);
+    if (it == g_strategy_programs.end()) return no_such_strategy_program(id);
+    StrategyProgram& p = it->second;
+    if (!p.dev) {
+        void* dev = nullptr;
+        HIP_TRY(hipMalloc(&dev, sizeof(rm::StrategyImage)));
+        const hipError_t e = hipMemcpy(dev, p.img.get(), sizeof(rm::StrategyImage), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(RM_E_HIP, "strategy program %d: copy to the device failed: %s", id, hipGetErrorString(e));
+        }
+        p.dev = dev;
+    }
+    *data = p.dev;
+    return RM_OK;
+}
+
+// The interpreter's kernels of scene `id` (check_scene has accepted it); nullptr in a development library without them.
+const rm::StrategyProgramLaunchers* strategy_launchers(int scene_id)
+{
+#if defined(RM_DEV_STRATEGIES)
+#define RM_SP_GET(name) (rm::name ? rm::name() : nullptr)
+#else
+#define RM_SP_GET(name) rm::name()
+#endif
+    if (is_program_id(scene_id)) {
+        bool ext = false;
+        (void)program_exists(scene_id, &ext);
+        return ext ? RM_SP_GET(strategy_launchers_program_ext) : RM_SP_GET(strategy_launchers_program);
+    }
+    switch (scene_id) {
+#define RM_X(id, S) case id: return RM_SP_GET(strategy_launchers_##id);
+        RM_SCENE_LIST(RM_X)
+#undef RM_X
+    }
+#undef RM_SP_GET
+    return nullptr;
+}
 
 constexpr size_t kStatsBlockBytes = sizeof(unsigned long long) * rm::kStatsWords;   // the canonical block (what the host reads)
 constexpr size_t kStatsBytes = kStatsBlockBytes * rm::kStatsBlocks;                 // + the partial blocks (device buffer size)
@@ -52,6 +154,14 @@ rm::LaunchPlan plan_for(const RmFrameDesc* d, int batch_frames = 0, const RmMarc
     const int strategy = d->strategy_id;
     rm::DeviceFacts f;
     f.cus = device_prop().multiProcessorCount;
+    if (rm::is_strategy_program(strategy)) {      // the interpreter has a render kernel and nothing else (plan_strategy_program)
+        const rm::StrategyProgramLaunchers* const sp = strategy_launchers(d->scene_id);
+        f.per_cu = [sp](rm::OccKernel, int, int, int batch) {
+            int n = 0;
+            return sp && sp->occupancy(batch, &n) == hipSuccess ? n : 0;
+        };
+        return rm::plan_launch(*d, f, batch_frames, configs);
+    }
     f.has_teams = sc->has_teams;
     f.has_split = sc->pipeline_teams && sc->pipeline_producers;
     f.has_resume_team = sc->resume_team != nullptr;
@@ -110,6 +220,7 @@ int make_args(const RmFrameDesc* d, const rm::LaunchPlan& p, float* depth, int32
 {
     memset(a, 0, sizeof *a);
     if (int rc = scene_data(d->scene_id, &a->scene_data)) return rc;
+    if (int rc = strategy_data(d->strategy_id, &a->strategy_data)) return rc;
     if (!stats)
         if (int rc = g_stats.get(&stats)) return rc;
     a->single.cam = camera_of(d->cam);
@@ -512,7 +623,8 @@ int launch_frame(const RmFrameDesc* d, const rm::LaunchPlan& p, rm::KernelArgs a
         g_passes.key.last_was_pipeline = true;
         g_passes.key.last_stats = a.stats;
     } else {                                                                             //    ... or render and the resume passes
-        HIP_TRY(sc->render(d->strategy_id, a, p.render_grid, s));
+        if (rm::is_strategy_program(d->strategy_id)) HIP_TRY(strategy_launchers(d->scene_id)->render(a, p.render_grid, s));
+        else HIP_TRY(sc->render(d->strategy_id, a, p.render_grid, s));
         if ((rc = g_passes.pass_done(s))) return rc;
         if (p.park[0] > 0 && (rc = resume_passes(d, p, a, sc, s))) return rc;
     }
@@ -607,8 +719,9 @@ int rm::capi::check_desc(const RmFrameDesc* d)
 {
     if (!d) return fail(RM_E_BAD_ARG, "desc is NULL");
     if (int rc = check_scene(d->scene_id)) return rc;
-    if (d->strategy_id < 0 || d->strategy_id >= RM_NUM_STRATEGY_KERNELS)
-        return fail(RM_E_BAD_STRATEGY, "strategy_id %d out of range", d->strategy_id);
+    if (int rc = check_strategy(d->strategy_id)) return rc;
+    if (rm::is_strategy_program(d->strategy_id) && !strategy_launchers(d->scene_id))
+        return fail(RM_E_BAD_STRATEGY, "the strategy-program kernels of scene %d are not built into this (development) library", d->scene_id);
     if (int rc = check_slice(d, d->band_rows > 0 && d->band_stride > 1)) return rc;
     if (d->tile_rows != 0 && d->tile_rows != 4 && d->tile_rows != 1) return fail(RM_E_BAD_ARG, "tile_rows must be 0, 4 or 1");
     if (d->tile_order_mode < 0 || d->tile_order_mode > 4) return fail(RM_E_BAD_ARG, "tile_order_mode must be 0 .. 4");
@@ -665,14 +778,19 @@ static int march_rays_impl(bool team, int scene_id, int strategy_id, const RmMar
     Entry e;
     int rc = e.rc();
     if (rc || (rc = check_scene(scene_id))) return rc;
-    if (strategy_id < 0 || strategy_id >= RM_NUM_STRATEGY_KERNELS)
-        return fail(RM_E_BAD_STRATEGY, "strategy_id %d out of range", strategy_id);
+    if ((rc = check_strategy(strategy_id))) return rc;
+    const bool program = rm::is_strategy_program(strategy_id);
+    if (program && team) return fail(RM_E_BAD_STRATEGY, "strategy program %d: a strategy program has no wavefront-team form", strategy_id);
+    if (program && !strategy_launchers(scene_id))
+        return fail(RM_E_BAD_STRATEGY, "the strategy-program kernels of scene %d are not built into this (development) library", scene_id);
     if (!cfg) return fail(RM_E_BAD_ARG, "cfg is NULL");
     if (team && !launchers(scene_id)->march_rays_team) return fail(RM_E_BAD_SCENE, "scene %d has no wavefront-team form", scene_id);
     if (n == 0) return RM_OK;
     if (!origins || !dirs || !hit || !t || !iters || !final_sdf) return fail(RM_E_BAD_ARG, "NULL buffer");
     const void* data = nullptr;
     if ((rc = scene_data(scene_id, &data))) return rc;
+    const void* sdata = nullptr;
+    if ((rc = strategy_data(strategy_id, &sdata))) return rc;
     Staged st(e);
     const double* d_origins = st.in(stage_in[0], origins, n * 24);
     const double* d_dirs = st.in(stage_in[1], dirs, n * 24);
@@ -691,10 +809,41 @@ static int march_rays_impl(bool team, int scene_id, int strategy_id, const RmMar
         const int fillers = rm::team_fillers(device_prop().multiProcessorCount, nteams);
         HIP_TRY(launchers(scene_id)->march_rays_team(strategy_id, c, d_origins, d_dirs, n, d_hit, d_t, d_iters, d_fs,
                                                      (unsigned long long*)g.busy.p, fillers, lib_stream()));
+    } else if (program) {
+        HIP_TRY(strategy_launchers(scene_id)->march_rays(c, d_origins, d_dirs, n, d_hit, d_t, d_iters, d_fs, data, sdata, lib_stream()));
     } else {
         HIP_TRY(launchers(scene_id)->march_rays(strategy_id, c, d_origins, d_dirs, n, d_hit, d_t, d_iters, d_fs, data, lib_stream()));
     }
     return st.finish();
+}
+
+int rm_strategy_program_create(const RmStrategyOp* ops, int32_t nops, int32_t* strategy_id)
+{
+    if (!strategy_id) return fail(RM_E_BAD_ARG, "strategy_id is NULL");
+    std::unique_ptr<rm::StrategyImage> img(new rm::StrategyImage());
+    char why[256];
+    if (!rm::strategy_encode(ops, nops, img.get(), why, sizeof why)) return fail(RM_E_BAD_ARG, "strategy program: %s", why);
+    std::lock_guard<std::mutex> lk(g_sp_mu);
+    if (g_next_strategy_program == INT32_MAX) return fail(RM_E_BAD_ARG, "strategy program ids exhausted");
+    const int32_t id = g_next_strategy_program++;
+    g_strategy_programs[id].img = std::move(img);
+    *strategy_id = id;
+    return RM_OK;
+}
+
+int rm_strategy_program_destroy(int32_t strategy_id)
+{
+    Lock lk;                                    // no call of this library is enqueueing a frame of the program meanwhile
+    void* dev = nullptr;
+    {
+        std::lock_guard<std::mutex> lp(g_sp_mu);
+        auto it = g_strategy_programs.find(strategy_id);
+        if (it == g_strategy_programs.end()) return no_such_strategy_program(strategy_id);
+        dev = it->second.dev;
+        g_strategy_programs.erase(it);
+    }
+    if (dev && lk.select_device()) HIP_TRY(hipFree(dev));      // (hipFree waits for the device: no launch still reads the copy)
+    return RM_OK;
 }
 
 int rm_march_rays(int scene_id, int strategy_id, const RmMarchConfig* cfg, const double* origins, const double* dirs,

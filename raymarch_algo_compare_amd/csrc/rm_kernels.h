@@ -176,6 +176,9 @@ struct KernelArgs {
     // Scenes with launch data (SceneProgram, rm_scene_program.h): the device image of the program the launch renders;
     // nullptr for the catalogue scenes.
     const void* scene_data;
+    // Strategies with launch data (StratProgram, rm_strategy_program.h): the device image of the step program the launch
+    // runs; nullptr for the compiled strategies.
+    const void* strategy_data;
 };
 
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -242,6 +245,17 @@ template <class Scene>
 __device__ __forceinline__ void rm_load_scene_data(const void* data)
 {
     if constexpr (SceneLaunchData<Scene>::value) Scene::load(data);
+}
+
+// The same for a strategy that reads data of the launch (Strat::kLaunchData: StratProgram, rm_strategy_program.h).
+template <class Strat, class = void>
+struct StratLaunchData : std::false_type {};
+template <class Strat>
+struct StratLaunchData<Strat, decltype((void)Strat::kLaunchData)> : std::integral_constant<bool, Strat::kLaunchData> {};
+template <class Strat>
+__device__ __forceinline__ void rm_load_strategy_data(const void* data)
+{
+    if constexpr (StratLaunchData<Strat>::value) Strat::load(data);
 }
 
 template <class Scene>
@@ -486,6 +500,7 @@ __global__ __launch_bounds__(64 * kWavesPerWG, 2) void render_kernel(const Kerne
 
     for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) s_hist[b] = 0u;
     rm_load_scene_data<Scene>(a.scene_data);
+    rm_load_strategy_data<Strat>(a.strategy_data);
     rm_load_tables<Scene>();
     __syncthreads();
 
@@ -892,9 +907,11 @@ __global__ __launch_bounds__(256) void sdf_eval_kernel(const double* __restrict_
 
 template <class Scene, class Strat>
 __global__ __launch_bounds__(64) void march_rays_kernel(MarchCfg cfg, const double* __restrict__ origins, const double* __restrict__ dirs,
-                                  size_t n, uint8_t* hit, double* t, int32_t* iters, double* final_sdf, const void* scene_data)
+                                  size_t n, uint8_t* hit, double* t, int32_t* iters, double* final_sdf, const void* scene_data,
+                                  const void* strategy_data)
 {
     rm_load_scene_data<Scene>(scene_data);
+    rm_load_strategy_data<Strat>(strategy_data);
     rm_load_tables<Scene>();
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

@@ -60,6 +60,31 @@ struct LaunchPlan {
     bool pass_team[2] = { false, false };     // the pass runs the team resume kernel
 };
 
+// A strategy program (rm_strategy_program.h; ids from RM_STRATEGY_PROGRAM_BASE) has exactly three kernels per scene: the
+// render kernel for one frame and for a batch, and the per-ray kernel.
+inline int default_tile_order(const RmFrameDesc& d, int nframes);
+inline bool is_strategy_program(int strategy_id) { return strategy_id >= RM_STRATEGY_PROGRAM_BASE; }
+
+// THE RULE FOR A STRATEGY PROGRAM: one plain render pass.  No parking levels and no single launch (there is no resume,
+// team or pipeline kernel, and the interpreter's registers live in the rendering workgroup's LDS, not in the strategy
+// record a queue entry would carry), whole evaluations (no interleaved form), 64x4 tiles, and the library's static tile
+// order (the longest-first order keeps per-strategy costs, which must not outlive a program).  The descriptor's
+// scheduling fields are ignored rather than refused, so one descriptor serves a compiled strategy and its twin.
+inline void plan_strategy_program(const RmFrameDesc& d, LaunchPlan& p)
+{
+    p.tile_h = 4;
+    p.tiles_y = (d.rows + 3) / 4;
+    p.interleave = 0;
+    p.mode = 1;
+    p.park[0] = p.park[1] = 0;
+    p.single = false;
+    p.fused_reduce = (p.nframes == 1 && d.rows > 0) ? 1 : 0;
+    p.refuse = nullptr;
+    p.static_order = default_tile_order(d, p.nframes);
+    p.tile_order = p.static_order;
+    p.queue_entry_bytes = 0;
+}
+
 // Workgroups per compute unit of a persistent grid: 2 where the occupancy is unknown, three at most -- the cheap scenes
 // fit four, and measured 10-16 % slower with four (Sphere 0.50 -> 0.45 ms, Cube 0.40 -> 0.34) while the long-ray
 // scenes are indifferent.
@@ -350,6 +375,7 @@ inline LaunchPlan plan_launch(const RmFrameDesc& d, const DeviceFacts& dev, int 
     p.static_order = default_tile_order(d, p.nframes);
     p.tile_order = d.tile_order_mode != 0 ? d.tile_order_mode : p.static_order;
     if (p.park[0] > 0) p.queue_entry_bytes = dev.entry_bytes;
+    if (is_strategy_program(d.strategy_id)) plan_strategy_program(d, p);
 
     if (p.single) {
         plan_single_launch(d, dev, p);

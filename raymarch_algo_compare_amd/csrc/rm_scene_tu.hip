@@ -212,7 +212,7 @@ static hipError_t march_rays(int strategy, const MarchCfg& cfg, const double* o,
 {
     if (n == 0) return hipSuccess;
     return with_strategy(strategy, hipErrorInvalidValue, [&](auto tag) {
-        return launch(march_rays_kernel<SceneT, typename decltype(tag)::type>, (int)((n + 63) / 64), 64, s, cfg, o, d, n, hit, t, iters, fs, scene_data);
+        return launch(march_rays_kernel<SceneT, typename decltype(tag)::type>, (int)((n + 63) / 64), 64, s, cfg, o, d, n, hit, t, iters, fs, scene_data, (const void*)nullptr);
     });
 }
 

@@ -229,6 +229,41 @@ def remove_program_scene(name: str) -> SceneInfo:
     return info
 
 
+# Strategies registered at run time (strategy_program.register_strategy): step programs of the library, ids from
+# RM_STRATEGY_PROGRAM_BASE.  Not part of STRATEGIES / list_strategies(), which stay the reference's eleven.
+_PROGRAM_STRATEGIES: List[StrategyInfo] = []
+
+
+def find_program_strategy(name: str) -> Optional[StrategyInfo]:
+    """A registered strategy by exact name, else case-insensitively."""
+    return next((s for s in _PROGRAM_STRATEGIES if s.key == name), None) or \
+        next((s for s in _PROGRAM_STRATEGIES if s.key.lower() == name.lower()), None)
+
+
+def check_new_strategy_name(name: str) -> None:
+    """ValueError if `name` would resolve to a compiled strategy (get_strategy_by_name's rules) or is registered."""
+    if not name or not name.strip():
+        raise ValueError("a strategy needs a name")
+    low = name.lower()
+    for key, short, _n, _l in _STRATEGY_ROWS + _SHADER_ONLY_ROWS:
+        if low == key.lower() or low in key.lower() or low == short.lower():
+            raise ValueError(f"strategy name {name!r} clashes with the compiled strategy {key!r}")
+    if find_program_strategy(name) is not None:
+        raise ValueError(f"strategy name {name!r} clashes with a registered strategy")
+
+
+def add_program_strategy(info: StrategyInfo) -> None:
+    _PROGRAM_STRATEGIES.append(info)
+
+
+def remove_program_strategy(name: str) -> StrategyInfo:
+    info = find_program_strategy(name)
+    if info is None:
+        raise KeyError(f"no registered strategy {name!r}")
+    _PROGRAM_STRATEGIES.remove(info)
+    return info
+
+
 def get_strategy_by_name(name: str, **ctor) -> Optional[StrategyInfo]:
     """Reference lookup rule (strategies/__init__.py:31-45): case-insensitive exact match on the
     registry KEYS, then substring.  A fresh record per call, like the reference's `strat_class()`.
@@ -245,6 +280,13 @@ def get_strategy_by_name(name: str, **ctor) -> Optional[StrategyInfo]:
     for i, row in enumerate(_STRATEGY_ROWS):
         if row[1].lower() == low:
             return _make_strategy(i, **ctor)
+    # a registered step program (strategy_program.register_strategy), after every rule of the reference: its tunables are
+    # constants of the program, so it takes no constructor arguments
+    st = find_program_strategy(name)
+    if st is not None:
+        if ctor:
+            raise TypeError(f"{st.key}: a registered strategy takes no constructor arguments")
+        return StrategyInfo(st.id, st.key, st.short_name, st.name, False)
     return None
 
 
